@@ -8,7 +8,14 @@ iteration of the reference's time loop (main.cpp:597-686): wall motion, periodic
 neighbour search, density/pressure sums, pressure/surface/viscous forces, gravity, kick, drift
 (+ elastic substeps when structure particles exist).  Inputs are resident in HBM before timing.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--case d1m] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--case d1m] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps and prints the headline line (`value`,
+`ms_per_step`, the workload).  `--dump-outputs DIR` also writes what the last timed step left
+(dump_outputs below) as DIR/<name>.npy.  Everything else described here -- the per-call pattern,
+per-kernel times and roofline, the developed flow, the reference's whole run, the CPU baseline
+(`--no-cpu-baseline` drops it) and, for N > 1, the partition and NeighborCount checks -- takes
+runs of its own after the timed steps and is measured only with `--full`.
 
 For N > 1 (torchrun, one rank per GPU) the ranks run BASELINE configs[4]: the 16,205,500-particle
 dam break cut into N z slabs (csrc/mph_dist.hip: RCCL ncclSend/Recv with the two
@@ -240,6 +247,30 @@ def run_whole(first, cfg, parts, n_total, end_time, profile_steps, device):
                     "steps after each segment are neither timed nor counted" % profile_steps}
 
 
+DUMP_FIELDS = ("Position", "Velocity", "Acceleration", "PressureP", "NeighborCount")
+DUMP_SAMPLE = 1 << 18       # particles per dumped field: 25 MB in all, under the 64 MB a dump may take
+
+
+def dump_outputs(solver, out_dir, rank=0, world=1):
+    """--dump-outputs: the state the timed path's last step left, as a caller reads it with
+    MphSolver.get() (original particle order), one float64 DIR/<name>.npy per DUMP_FIELDS entry.
+    Above DUMP_SAMPLE particles a fixed sample is written (seeded, ascending; its indices in
+    `particle_index`), so two builds given the same arguments write comparable files.  A slab rank
+    writes the sampled particles it owns as DIR/<name>.rank<r>.npy."""
+    import numpy as np
+    n = solver.n
+    idx = np.arange(n)
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    if world > 1:
+        idx = np.intersect1d(idx, solver.owned_ids())
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = ".npy" if world == 1 else ".rank%d.npy" % rank
+    np.save(os.path.join(out_dir, "particle_index" + suffix), idx.astype(np.float64))
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(out_dir, f + suffix), solver.get(f)[idx].astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -248,6 +279,11 @@ def main():
     ap.add_argument("--case", default="d1m")
     ap.add_argument("--profile-steps", type=int, default=4)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    # everything beyond the headline (full_report): --profile-steps, --no-cpu-baseline,
+    # --developed-steps and --run-average-end act only with it
+    ap.add_argument("--full", action="store_true")
+    # write the last timed step's outputs as DIR/<name>.npy (dump_outputs)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR")
     # the developed flow: after the headline measurement the same context runs on to
     # this many steps in all (D1M: t = 0.25 s of the reference's 1 s dam run, main.cpp:581 with
     # results/Dam/dam.data EndTime 1.0) and times --steps more there; 0 skips it
@@ -353,7 +389,54 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = n_total * args.steps / elapsed   # every particle of the whole job, once per step
+    if args.dump_outputs:
+        dump_outputs(solver, args.dump_outputs, rank, world)
 
+    out = {
+        "metric": "particle-steps/sec + achieved HBM GB/s, dam-break, 1/2/4/8 MI355X",
+        "value": value,
+        "unit": "particle-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak" if world == 1 else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (reference generator algorithm + results/Dam/dam.data parameters)",
+        "config": {"workload": "%s: %s, %d particles, ~%d per GPU"
+                               % (case_name, case.describe(), n_total, n_total // world),
+                   "particles": n_total, "dim": case.dim, "module": case.module, "dt": cfg.dt,
+                   "parallelism": "single" if world == 1 else "slab%d-%s (%s halo exchange, %s)" % (
+                       world, "xyz"[SLAB_AXIS[case.dim]],
+                       "host-staged" if os.environ.get("MPH_SLAB_TRANSPORT") == "host" or fallback else "RCCL",
+                       "equal widths" if cuts is None else "cuts at particle-count quantiles"),
+                "slab_cuts": None if cuts is None else [round(float(x), 9) for x in cuts]},
+        "achieved_hbm_gbps_alg": B_ALG_STEP * value / 1e9,
+        "gather_literal_gbps": {"value": (B_GATHER_3D if case.dim == 3 else 12e3) * value / 1e9,
+                                "note": "reference-literal gather bytes (SURVEY 8d B_gather, %.1f kB per "
+                                        "particle-step) x rate: a label for the north-star target, not "
+                                        "HBM traffic" % ((B_GATHER_3D if case.dim == 3 else 12e3) / 1e3)},
+        "full": bool(args.full),
+    }
+    if args.full:
+        out.update(full_report(args, solver, dist, barrier, case, case_name, cfg,
+                               parts if dist is None else None, rank, world, device, fallback,
+                               n_total, n_local, value, elapsed, elapsed_local))
+    elif fallback is not None:
+        out["slab"] = {"transport_fallback": fallback}
+    solver.close()
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_report(args, solver, dist, barrier, case, case_name, cfg, parts, rank, world, device, fallback,
+                n_total, n_local, value, elapsed, elapsed_local):
+    """--full: what the line holds beyond the headline, measured on the headline's context after
+    its timed steps (and its dump), each figure in runs of its own."""
     # the drop-in binding's own call pattern (INTEGRATION.md section 2): one mph_step(ctx, 1) per
     # time-loop iteration over the same number of steps, with step batching on as INTEGRATION.md
     # recommends (mph_set_step_batching: the steps run 8 per graph, flushed by the synchronize that
@@ -539,36 +622,11 @@ def main():
     if world == 1 and end_time > 0.0:
         run_average = run_whole(solver, cfg, parts, n_total, end_time, args.profile_steps, device)
     out = {
-        "metric": "particle-steps/sec + achieved HBM GB/s, dam-break, 1/2/4/8 MI355X",
-        "value": value,
-        "unit": "particle-steps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed * 1e3 / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak" if world == 1 else "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (reference generator algorithm + results/Dam/dam.data parameters)",
-        "config": {"workload": "%s: %s, %d particles, ~%d per GPU"
-                               % (case_name, case.describe(), n_total, n_total // world),
-                   "particles": n_total, "dim": case.dim, "module": case.module, "dt": cfg.dt,
-                   "parallelism": "single" if world == 1 else "slab%d-%s (%s halo exchange, %s)" % (
-                       world, "xyz"[SLAB_AXIS[case.dim]],
-                       "host-staged" if os.environ.get("MPH_SLAB_TRANSPORT") == "host" or fallback else "RCCL",
-                       "equal widths" if cuts is None else "cuts at particle-count quantiles"),
-                "slab_cuts": None if cuts is None else [round(float(x), 9) for x in cuts]},
-        "achieved_hbm_gbps_alg": B_ALG_STEP * value / 1e9,
         "achieved_hbm_gbps_measured": (step_bytes / (elapsed / args.steps) / 1e9) if step_bytes else None,
         "hbm_measured": ({"bytes_per_step": step_bytes, "bytes_per_particle_step": step_bytes / n_total,
                           "source": "profiles/pmc_traffic.json: 2 x FETCH_SIZE + WRITE_SIZE per kernel, "
                                     "8-step store pattern (calibrated: profiles/pmc_calib.json)"}
                          if step_bytes else None),
-        "gather_literal_gbps": {"value": (B_GATHER_3D if case.dim == 3 else 12e3) * value / 1e9,
-                                "note": "reference-literal gather bytes (SURVEY 8d B_gather, %.1f kB per "
-                                        "particle-step) x rate: a label for the north-star target, not "
-                                        "HBM traffic" % ((B_GATHER_3D if case.dim == 3 else 12e3) / 1e3)},
         "neighbors": {"mean": mean_nb, "max": max_nb},
         # bound: the resource the PMC summary measured as binding the dominant stage (not HBM, DESIGN.md
         # section 3); achieved / peak / frac stay the HBM roofline's (peak_of)
@@ -612,11 +670,7 @@ def main():
                                            "(main.cpp:878-882), ~100 GB at 16.2M particles"}
         else:
             out["cpu_baseline"] = cpu_baseline(args.case)
-    solver.close()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

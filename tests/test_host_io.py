@@ -76,11 +76,11 @@ def test_derived_constants_bit_identical_to_reference(case):
 
 
 def test_generator_reproduces_reference_dam_grid():
-    ref = "/root/reference/results/Dam/dam.grid"
+    # tests/golden/dam_reference.grid.gz: the reference's own results/Dam/dam.grid, byte for byte
+    ref = gzip.open(os.path.join(ROOT, "tests", "golden", "dam_reference.grid.gz")).read().decode()
     txt = cases.get("dam2d").grid_text()
-    if os.path.exists(ref):
-        assert txt == open(ref).read()
-    # independent of /root/reference: the golden .prof at step 0 holds the same particles
+    assert txt == ref
+    # and the golden .prof at step 0 holds the same particles
     prof = gzip.open(os.path.join(ROOT, "tests", "golden", "dam2d_000.prof.gz")).read().decode()
     body_grid = [l.split() for l in txt.splitlines()[2:]]
     body_prof = [l.split() for l in prof.splitlines()[2:]]

@@ -8,6 +8,6 @@ mkdir -p gpurun_out/configs
 for c in ${CASES:-bar2d_400k fsi3d d16m}; do
   extra=""
   [ "$c" = d16m ] && extra="--no-cpu-baseline"
-  timeout -k 10 600 python bench.py --case $c --steps ${STEPS:-20} --warmup 4 $extra \
+  timeout -k 10 600 python bench.py --full --case $c --steps ${STEPS:-20} --warmup 4 $extra \
       > gpurun_out/configs/bench_$c.json 2> gpurun_out/configs/bench_$c.err || exit 30
 done
