@@ -41,8 +41,9 @@ extern "C" {
 #define MPH_TYPE_COUNT 6            /* main.cpp:68 */
 #define MPH_MAX_NEIGHBOR_COUNT 512  /* main.cpp:100 (semantic limit; overflow is an error here) */
 /* Bumped on every incompatible change of a declaration below (3: mph_slab_bounds/_owner/_window
- * take `cuts`; mph_dist_info slot 0/2 meaning); bindings compare mph_abi_version() with it.     */
-#define MPH_ABI_VERSION 4
+ * take `cuts`; mph_dist_info slot 0/2 meaning; 5: mph_list_layout added); bindings compare
+ * mph_abi_version() with it.                                                                  */
+#define MPH_ABI_VERSION 5
 
 /* Compile-time case modules of the reference (main.cpp:54-59) as a runtime switch.  The module
  * selects the clamp rule of updateElasticPosition (main.cpp:1918-2044).                        */
@@ -396,6 +397,12 @@ int mph_dist_overlap(const MphCtx* ctx, double* out5);
  * count).  ABI 4 (round 6): replaces mph_list_formats, which reported the compact 16-bit list
  * format removed from the product.                                                            */
 int mph_list_stats(MphCtx* ctx, double* mean, int* max);
+/* How the last search laid the stored lists out in rows (the aligned rows of DESIGN.md 3.3), for
+ * verification: out6 = {waves (tiles of 64 particles), waves that made at least one row jump,
+ * row jumps in all, the most jumps of one wave, gap rows in all (the rows the lanes skipped at
+ * their jumps), the most rows of one lane (entries + gaps)}.  Read-only, reduced on the host.
+ * Single contexts only (MPH_ERR_UNSUPPORTED in slab mode).  ABI 5.                             */
+int mph_list_layout(MphCtx* ctx, long long out6[6]);
 /* The neighbour lists of calculateNeighbor themselves (main.cpp:1764-1772: Neighbor[i][k] = j for
  * k < 512), for verification: the sets of the `count` particles [first, first + count) (original
  * order) from the last search, each row as ascending original indices (the reference's rows are in

@@ -353,6 +353,44 @@ _reg(Case("channel3d_st", 3, "dam", 0.001, CASES["channel3d"].lower, CASES["chan
           CASES["channel3d"].cuboids, data_changes=_ST, note="channel3d with surface tension"))
 
 
+# Kernel radii other than the example's 2.5 / 2.5 / 2.5.  The reference reads RadiusRatioA, P and V
+# independently (main.cpp:748-751) and searches to MaxRadius + MARGIN (main.cpp:1744), so every
+# pass may sum over a radius below the lists': <base>_r<A><P><V>[_jit] is the base case (its
+# geometry and data_changes) with the three ratios in tenths of dx.
+def _radii(base: str, a: float, p: float, v: float, jitter: float = 0.0) -> str:
+    b = CASES[base]
+    name = "%s_r%d%d%d%s" % (base, round(10 * a), round(10 * p), round(10 * v), "_jit" if jitter else "")
+    changes = dict(b.data_changes)
+    changes.update({"RadiusRatioA": [a], "RadiusRatioP": [p], "RadiusRatioV": [v]})
+    _reg(Case(name, b.dim, b.module, b.spacing, b.lower, b.upper, b.cuboids, data_changes=changes,
+              wall_motion=b.wall_motion, time0=b.time0, init_calls=b.init_calls, jitter=jitter,
+              note="%s with RadiusRatioA/P/V %.1f/%.1f/%.1f%s" % (base, a, p, v,
+                                                               ", +-%.1f dx offsets" % jitter if jitter else "")))
+    return name
+
+
+# unequal radii (the general branch of pass A, pass B and the virial, lists trimmed to the largest
+# pass radius, grid and stencil from MaxRadius, the elastic weight with RadiusP below or at it);
+# the last is equal radii with long lists (up to 149 neighbours, past the aligned rows' 128)
+RADII_CASES = (
+    _radii("box3d", 3.1, 2.1, 2.6), _radii("box3d", 2.1, 3.1, 2.6), _radii("box3d", 2.6, 2.1, 3.1, 0.3),
+    _radii("box3d_st", 3.1, 2.1, 2.6), _radii("box3d_st", 2.1, 3.1, 2.6, 0.3),
+    _radii("gate3d_sub", 2.1, 3.1, 2.1), _radii("bar3d", 2.1, 3.1, 2.1),
+    _radii("gate2d", 3.1, 2.1, 3.1), _radii("gate2d_sub", 2.6, 2.1, 3.1), _radii("dam2d_st", 2.1, 2.6, 3.1),
+    _radii("seam3d", 3.1, 2.1, 2.6), _radii("channel3d", 2.1, 2.6, 3.1),
+    _radii("box3d", 3.1, 3.1, 3.1, 0.3),
+)
+# on-cutoff lattices: with every ratio at 2.9 (3.9, 4.9) the search's cutoff is 3 (4, 5) dx to
+# within rounding, so the lattice pairs at (3,0,0), (2,2,1), ... lie on it and the reference
+# accepts or rejects each by the last bit of its own expression (main.cpp:1764) -- tens of
+# thousands of pairs per case for the search's exact-expression band, on GPU cells ~1 dx wide
+CUTOFF_CASES = (
+    _radii("box3d", 2.9, 2.9, 2.9), _radii("gate3d_sub", 2.9, 2.9, 2.9), _radii("seam3d", 2.9, 2.9, 2.9),
+    _radii("channel3d", 2.9, 2.9, 2.9), _radii("dam2d", 3.9, 3.9, 3.9), _radii("dam2d", 4.9, 4.9, 4.9),
+    _radii("channel2d", 3.9, 3.9, 3.9),
+)
+
+
 def d1m_weak(nranks: int) -> Case:
     """Weak-scaling workload of bench.py --gpus N: the D1M tank extended N-fold
     along z (slab axis), so each of N slabs holds about one D1M (N = 1 is D1M itself)."""

@@ -1296,6 +1296,32 @@ int mph_list_stats(MphCtx* c, double* mean, int* mx)
     return MPH_OK;
 }
 
+int mph_list_layout(MphCtx* c, long long out[6])
+{
+    if (!c || !out) return MPH_ERR_ARG;
+    CK(ctx_flush(c));
+    if (c->dist) return fail(c, MPH_ERR_UNSUPPORTED, "mph_list_layout: single contexts only");
+    HIP_OK(c, hipSetDevice(c->device));
+    HostRows R;   // the last search's rows and row jumps, reduced on the host
+    CK(host_rows(c, R));
+    const int n = c->n;
+    const long long waves = ((long long)n + kTile - 1) / kTile;
+    long long jumped = 0, jumps = 0, max_jumps = 0, gap_rows = 0, max_rows = 0;
+    for (long long t = 0; t < waves; ++t) {
+        const int J = (int)(R.hdr[t] >> 56);
+        jumped += J > 0;
+        jumps += J;
+        max_jumps = std::max<long long>(max_jumps, J);
+    }
+    for (int s = 0; s < n; ++s) {
+        const int rows = std::min(R.rows[s], kTileRows);
+        gap_rows += rows - R.entries(s);
+        max_rows = std::max<long long>(max_rows, rows);
+    }
+    out[0] = waves; out[1] = jumped; out[2] = jumps; out[3] = max_jumps; out[4] = gap_rows; out[5] = max_rows;
+    return MPH_OK;
+}
+
 int mph_neighbor_rows(MphCtx* c, int first, int count, int* counts, int* ids, long long ids_cap)
 {
     if (!c || first < 0 || count < 0 || !counts || (!ids && ids_cap > 0)) return MPH_ERR_ARG;

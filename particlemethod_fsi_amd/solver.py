@@ -57,10 +57,10 @@ EXPORTED_SYMBOLS = [
     "mph_write_vtu_arrays", "mph_write_vtu", "mph_velocity_profile_arrays",
     "mph_set_initial_velocity_profile", "mph_dist_info", "mph_create_slab", "mph_slab_window",
     "mph_list_stats", "mph_abi_version", "mph_phase_timing", "mph_phase_times",
-    "mph_set_step_batching", "mph_neighbor_rows", "mph_dist_overlap",
+    "mph_set_step_batching", "mph_neighbor_rows", "mph_dist_overlap", "mph_list_layout",
 ]
 
-ABI_VERSION = 4   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
+ABI_VERSION = 5   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
 
 # mph_host_exchange_fn (include/mph_gpu.h): (user, send_l, n, send_r, n, recv_l, n, recv_r, n)
 HOST_EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
@@ -157,10 +157,11 @@ def load_library() -> ctypes.CDLL:
         "mph_set_step_batching": (ip, [vp, ip]),
         "mph_neighbor_rows": (ip, [vp, ip, ip, vp, vp, ctypes.c_longlong]),
         "mph_dist_overlap": (ip, [vp, vp]),
+        "mph_list_layout": (ip, [vp, vp]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
-                "mph_dist_overlap", "mph_profile_graphs", "mph_list_stats"}
+                "mph_dist_overlap", "mph_profile_graphs", "mph_list_stats", "mph_list_layout"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -168,7 +169,8 @@ def load_library() -> ctypes.CDLL:
         f.restype = res
         f.argtypes = args
     # MPH_ABI_ACCEPT=3: an A/B run against a round-5 build (ABI 3 differs only by mph_list_formats,
-    # replaced by mph_list_stats in 4; tools/lib_bitwise.py)
+    # replaced by mph_list_stats in 4; MPH_ABI_ACCEPT=4: a build before mph_list_layout, the only
+    # change of 5; tools/lib_bitwise.py)
     accept = {ABI_VERSION} | {int(v) for v in os.environ.get("MPH_ABI_ACCEPT", "").split(",") if v.strip()}
     if L.mph_abi_version() not in accept:
         raise ImportError("%s has C ABI version %d, these bindings expect %d (rebuild the library)"
@@ -470,6 +472,15 @@ class MphSolver:
         x = ctypes.c_int()
         _check(self._L.mph_list_stats(self._h, ctypes.byref(m), ctypes.byref(x)), self._h)
         return m.value, x.value
+
+    def list_layout(self) -> dict:
+        """How the last search laid the stored lists out in rows (mph_list_layout): waves, the waves
+        that jumped rows, the jumps in all and the most of one wave, the gap rows in all, and the most
+        rows (entries + gaps) of one lane.  Single contexts only."""
+        a = np.zeros(6, np.int64)
+        _check(self._L.mph_list_layout(self._h, a.ctypes.data), self._h)
+        keys = ["waves", "waves_jumped", "jumps", "max_jumps", "gap_rows", "max_rows"]
+        return {k: int(v) for k, v in zip(keys, a)}
 
     def neighbor_rows(self, first: int = 0, count: int | None = None):
         """(counts, offsets, ids): the neighbour sets of the particles [first, first + count) from

@@ -75,6 +75,38 @@ def test_derived_constants_bit_identical_to_reference(case):
     assert np.array_equal(solver.derive_scalars(cfg), Golden(case).z["scalars"])
 
 
+_REF_SCALARS_SCRIPT = r"""
+import sys
+sys.path.insert(0, %(root)r); sys.path.insert(0, %(root)r + '/tests')
+from oracle_bindings import RefSolver, write_case_files
+from particlemethod_fsi_amd import cases
+c = cases.get(%(case)r)
+dp, gp = write_case_files(cases.data_text(c.data()), c.grid_text())
+print("SCALARS", RefSolver(c.dim, c.ref_variant, dp, gp).scalars().tobytes().hex())
+"""
+
+
+@pytest.mark.parametrize("case", ["box3d_r312126", "gate3d_sub_r213121", "gate2d_sub_r262131"])
+def test_derived_constants_unequal_radii(case):
+    """RadiusRatioA, P and V each the largest once (3-D fluid, 3-D gate, 2-D gate): the host's
+    derived constants (N0a, N0p, the Sw*, the four radii, MaxRadius, CellWidth, CellCount, ...)
+    equal the oracle's bit for bit, and the compiled reference's where it is built (in a process
+    of its own: the reference keeps its state in file-scope globals)."""
+    import subprocess
+    from oracle_bindings import OracleSolver, ref_available
+    c = cases.get(case)
+    cfg, parts = c.build()
+    mine = solver.derive_scalars(cfg)
+    assert len({mine[8], mine[10], mine[11]}) > 1 and mine[7] == max(mine[8], mine[10], mine[11])
+    assert np.array_equal(mine, OracleSolver(cfg, parts).scalars())
+    if ref_available(c.dim, c.ref_variant):
+        r = subprocess.run([sys.executable, "-c", _REF_SCALARS_SCRIPT % {"root": ROOT, "case": case}],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "SCALARS" in r.stdout, r.stdout + r.stderr[-2000:]
+        ref = np.frombuffer(bytes.fromhex(r.stdout.split("SCALARS", 1)[1].split()[0]))
+        assert np.array_equal(mine, ref)
+
+
 def test_generator_reproduces_reference_dam_grid():
     # tests/golden/dam_reference.grid.gz: the reference's own results/Dam/dam.grid, byte for byte
     ref = gzip.open(os.path.join(ROOT, "tests", "golden", "dam_reference.grid.gz")).read().decode()
@@ -149,6 +181,38 @@ def test_structure_init_matches_reference(case):
     ref = g.get(0, "Normalizer")
     # neighbour sums in slot order instead of the reference's cell-scan order: reassociation only
     assert np.max(np.abs(N[g.solid] - ref)) <= 1e-12 * np.max(np.abs(ref))
+
+
+@pytest.mark.parametrize("case", ["gate2d_sub_r262131", "gate3d_sub_r213121"])
+def test_structure_init_unequal_radii_matches_oracle(case):
+    """mph_structure_init where the elastic weight's radius differs from the lists': RadiusP below
+    MaxRadius (gate2d_sub 2.6/2.1/3.1; calculateInitialNeighbor keeps every structure pair within
+    MaxRadius + MARGIN, main.cpp:1608, the Normalizer's weight ends at RadiusP) and RadiusP =
+    MaxRadius above RadiusA (gate3d_sub 2.1/3.1/2.1) -- against the oracle (bit-identical to the
+    reference on these configurations, test_oracle_per_kernel_against_live_reference), with the
+    bounds of test_structure_init_matches_reference."""
+    from oracle_bindings import OracleSolver
+    cfg, p = cases.get(case).build()
+    n = p.n
+    o = OracleSolver(cfg, p)
+    o.init()
+    sc = o.scalars()
+    assert sc[10] < sc[7] if case.startswith("gate2d") else sc[8] < sc[10] == sc[7]
+    solid = (p.property >= 2) & (p.property < 4)
+    assert solid.any()
+    isnc = np.zeros(n, np.int32)
+    N = np.zeros((n, 3, 3))
+    ll, lm = np.zeros(n), np.zeros(n)
+    assert solver.load_library().mph_structure_init(ctypes.byref(cfg), n, p.property.ctypes.data,
+                                                    p.initial_position.ctypes.data, isnc.ctypes.data,
+                                                    N.ctypes.data, ll.ctypes.data, lm.ctypes.data) == 0
+    assert np.array_equal(isnc[solid], o.get("InitialStructureNeighborCount")[solid])
+    assert not isnc[~solid].any()
+    assert np.array_equal(ll[solid], o.get("LambdaLames")[solid])
+    assert np.array_equal(lm[solid], o.get("MuLames")[solid])
+    ref = o.get("Normalizer")[solid]
+    # neighbour sums in slot order instead of the reference's cell-scan order: reassociation only
+    assert np.max(np.abs(N[solid] - ref)) <= 1e-12 * np.max(np.abs(ref))
 
 
 def _vtk_reference_format(n, prop, pos, pos0, vel, acc, force, stress, strain, isnc, nc):

@@ -113,7 +113,13 @@ print("OK")
 """
 
 
-@pytest.mark.parametrize("case", ["gate2d", "gate3d", "turek2d", "hydro2d", "movwall3d", "gate3d_jit"])
+# the last four: kernel radii other than 2.5/2.5/2.5 (cases.RADII_CASES, CUTOFF_CASES), which the
+# GPU tests of test_gpu_radii.py take the oracle for -- a fluid case with unequal radii, surface
+# tension with RadiusA the largest, an elastic gate with RadiusP the largest, and the 2.9 lattice
+# whose pairs at 3 dx lie on the search's cutoff
+@pytest.mark.parametrize("case", ["gate2d", "gate3d", "turek2d", "hydro2d", "movwall3d", "gate3d_jit",
+                                  "box3d_r312126", "box3d_st_r312126", "gate3d_sub_r213121",
+                                  "box3d_r292929"])
 def test_oracle_per_kernel_against_live_reference(case):
     c = cases.get(case)
     if not ref_available(c.dim, c.ref_variant):
