@@ -81,7 +81,7 @@ struct MphCtx {
     MphConfig cfg{};
     mph::HostDerived h{};
     mph::DevParams P{};
-    mph::DevTables T{};
+    mph::DevTables tables{};     // host copy of the per-type tables (uploaded to L.T at creation)
     std::string err;
     std::thread out_thread;      // mph_write_vtk_async: the file of the previous output step
     int out_rc = 0;
@@ -112,23 +112,27 @@ struct MphCtx {
     mph::StructureInit S;
     std::vector<int> sl_orig;    // local structure slot -> original particle index
     std::vector<int> sl_s;       // local structure slot -> index into S (the lists built here)
-    // device
-    mph::DevTables* dT = nullptr;
-    mph::DevState* dst = nullptr;
-    mph::Soa A, B;               // sorted current state / integrated state (see mph_kernels.h)
-    int* rank_of = nullptr;
-    int *key = nullptr, *slot = nullptr, *tmp = nullptr, *cnt = nullptr, *start = nullptr, *bsum = nullptr;
+    // device: the arrays every launch sequence uses live in L (mph_kernels.h Launch), allocated at
+    // creation; what only this layer touches is here
+    int* order = nullptr;        // cap ints: the slab sort's dst_of, scratch of the structure init
     double *vir = nullptr, *vpres = nullptr;   // VirialStress [cap][9] / VirialPressure (A order), lazy
-    int *nbr = nullptr, *ncount = nullptr, *nbcount = nullptr;   // list rows / NeighborCount
-    unsigned long long *lhdr = nullptr, *lgap = nullptr;          // the lists' row jumps (RowMask)
-    double *pres = nullptr, *gx = nullptr, *gy = nullptr, *gz = nullptr, *pa = nullptr;
-    double4 *force = nullptr, *acc = nullptr, *fpart = nullptr, *rec = nullptr;
-    double *dens_a = nullptr, *vstrain = nullptr, *divp = nullptr;
     mph::StructDev Sd;
     std::vector<void*> allocs;
     mph::Launch L;
     MphDist* dist = nullptr;     // non-null in slab mode
 };
+
+#define MPH_HIP_OK(ctx, expr)                                                \
+    do {                                                                     \
+        hipError_t _e = (expr);                                              \
+        if (_e != hipSuccess) return mph::ctx_hip_fail(ctx, _e, #expr);      \
+    } while (0)
+
+#define MPH_CK(expr)                   \
+    do {                               \
+        int _r = (expr);               \
+        if (_r != MPH_OK) return _r;   \
+    } while (0)
 
 namespace mph {
 
@@ -144,6 +148,8 @@ int ctx_dalloc(MphCtx* c, T** p, size_t count)
     return st;
 }
 
+// what c->L holds besides the arrays: P (set_uniforms applied), stream, S and the environment's
+// MPH_LIST_FULL / MPH_XCD_BAL_MIN
 void ctx_fill_launch(MphCtx* c);
 // cells between a fast-path interior particle and a grid face along axis d: stencil half-width + 1
 inline int stencil_margin(const DevParams& P, int d)
@@ -158,6 +164,15 @@ void ctx_set_global_error(const std::string& msg);   // mph_last_error(NULL)
 int ctx_create(MphCtx** out, const MphConfig* cfg, int n, const int* property, const double* pos,
                const double* pos0, const double* vel, int device, MphDist* dist, const int* ids = nullptr,
                int n_glob = 0);
+// count elements of a device array into h, on the context's stream (synchronize before reading h)
+template <typename T>
+int fetch(MphCtx* c, const T* d, std::vector<T>& h, size_t count)
+{
+    h.resize(count);
+    if (count) MPH_HIP_OK(c, hipMemcpyAsync(h.data(), d, sizeof(T) * count, hipMemcpyDeviceToHost, c->stream));
+    return MPH_OK;
+}
+
 // original index of host input k (identity unless created slab-local)
 inline int glob_id(const MphCtx* c, int k) { return c->gid.empty() ? k : c->gid[k]; }
 
@@ -180,15 +195,3 @@ int virial_full_lists(MphCtx* c);   // the step's lists again with every neighbo
 void dist_free(MphCtx* c);
 
 }  // namespace mph
-
-#define MPH_HIP_OK(ctx, expr)                                                \
-    do {                                                                     \
-        hipError_t _e = (expr);                                              \
-        if (_e != hipSuccess) return mph::ctx_hip_fail(ctx, _e, #expr);      \
-    } while (0)
-
-#define MPH_CK(expr)                   \
-    do {                               \
-        int _r = (expr);               \
-        if (_r != MPH_OK) return _r;   \
-    } while (0)

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "mph_ctx.h"
+#include "mph_rows.h"
 
 using namespace mph;
 
@@ -66,22 +67,11 @@ void ctx_fill_launch(MphCtx* c)
     // Neighbor[] (mph_neighbor_rows needs them); else only those the passes' sums can take
     if (std::getenv("MPH_LIST_FULL") && std::atoi(std::getenv("MPH_LIST_FULL")) == 1) c->P.rlf = 3.0e38f;
     L.P = &c->P;
-    L.T = c->dT;
-    L.st = c->dst;
     L.stream = c->stream;
-    L.prof = nullptr;
-    // rank_of (original id -> sorted index) has no reader on the single-GPU path (fields are
-    // returned through A.id), so k_rank_scatter skips that scatter; slab mode uses dst_of.
-    L.A = c->A; L.B = c->B; L.rank_of = nullptr; L.dst_of = nullptr;
-    L.key = c->key; L.slot = c->slot; L.tmp = c->tmp; L.cnt = c->cnt; L.start = c->start; L.bsum = c->bsum;
-    L.nbr = c->nbr; L.ncount = c->ncount; L.nbcount = c->nbcount; L.lhdr = c->lhdr; L.lgap = c->lgap;
     // work-balanced XCD map of the passes from this many particles (MPH_XCD_BAL_MIN: tests force it
     // on small cases, the default keeps it off below 2^20 where the split kernel costs more)
     const char* bm = std::getenv("MPH_XCD_BAL_MIN");
     L.xcd_bal_min = bm && *bm ? std::atoi(bm) : (1 << 20);
-    L.pres = c->pres; L.gx = c->gx; L.gy = c->gy; L.gz = c->gz; L.pa = c->pa;
-    L.force = c->force; L.acc = c->acc; L.fpart = c->fpart; L.rec = c->rec;
-    L.dens_a = c->dens_a; L.vstrain = c->vstrain; L.divp = c->divp;
     L.S = &c->Sd;
 }
 
@@ -106,19 +96,6 @@ int virial_full_lists(MphCtx* c)
 }  // namespace mph
 
 namespace {
-
-int fail(MphCtx* c, int code, const std::string& msg) { return ctx_fail(c, code, msg); }
-
-#define HIP_OK(ctx, expr) MPH_HIP_OK(ctx, expr)
-#define CK(expr) MPH_CK(expr)
-
-template <typename T>
-int dalloc(MphCtx* c, T** p, size_t count)
-{
-    return ctx_dalloc(c, p, count);
-}
-
-void fill_launch(MphCtx* c) { ctx_fill_launch(c); }
 
 // Force and Acceleration (main.cpp:2085-2096, 2892-2956) are outputs only: no kernel reads them,
 // and every step overwrites all of them.  So only the last step of a replayed batch stores them
@@ -161,12 +138,12 @@ void enqueue_step(const Launch& L, bool last, hipEvent_t* ev = nullptr)
 int capture(MphCtx* c, int steps, hipGraphExec_t* out, bool store_last = true)
 {
     hipGraph_t g = nullptr;
-    HIP_OK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    MPH_HIP_OK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     for (int k = 0; k < steps; ++k) enqueue_step(c->L, store_last && k == steps - 1);
-    HIP_OK(c, hipStreamEndCapture(c->stream, &g));
-    HIP_OK(c, hipGraphInstantiate(out, g, nullptr, nullptr, 0));
-    HIP_OK(c, hipGraphDestroy(g));
-    HIP_OK(c, hipGraphUpload(*out, c->stream));   // so the first launch costs what later ones do
+    MPH_HIP_OK(c, hipStreamEndCapture(c->stream, &g));
+    MPH_HIP_OK(c, hipGraphInstantiate(out, g, nullptr, nullptr, 0));
+    MPH_HIP_OK(c, hipGraphDestroy(g));
+    MPH_HIP_OK(c, hipGraphUpload(*out, c->stream));   // so the first launch costs what later ones do
     return MPH_OK;
 }
 
@@ -175,17 +152,17 @@ int capture(MphCtx* c, int steps, hipGraphExec_t* out, bool store_last = true)
 // inside its first long run.
 static int capture_graphs(MphCtx* c)
 {
-    if (!c->graph1) CK(capture(c, 1, &c->graph1));
-    if (!c->graph1t) CK(capture(c, 1, &c->graph1t, false));
-    if (!c->graph8) CK(capture(c, 8, &c->graph8));
+    if (!c->graph1) MPH_CK(capture(c, 1, &c->graph1));
+    if (!c->graph1t) MPH_CK(capture(c, 1, &c->graph1t, false));
+    if (!c->graph8) MPH_CK(capture(c, 8, &c->graph8));
     return MPH_OK;
 }
 
 // `left` (< 8) single steps: the output-only stores on the last one only, as in an 8-step batch
 static int launch_singles(MphCtx* c, int left)
 {
-    for (; left > 1; --left) HIP_OK(c, hipGraphLaunch(c->graph1t, c->stream));
-    if (left == 1) HIP_OK(c, hipGraphLaunch(c->graph1, c->stream));
+    for (; left > 1; --left) MPH_HIP_OK(c, hipGraphLaunch(c->graph1t, c->stream));
+    if (left == 1) MPH_HIP_OK(c, hipGraphLaunch(c->graph1, c->stream));
     return MPH_OK;
 }
 
@@ -193,78 +170,31 @@ static int launch_singles(MphCtx* c, int left)
 // explicit sums
 int accumulate_phases(MphCtx* c, const std::vector<hipEvent_t>& ev, int steps)
 {
-    HIP_OK(c, hipEventSynchronize(ev[3 * (size_t)steps - 1]));
+    MPH_HIP_OK(c, hipEventSynchronize(ev[3 * (size_t)steps - 1]));
     for (size_t k = 0; k + 2 < 3 * (size_t)steps; k += 3) {
         float a = 0.0f, b = 0.0f;
-        HIP_OK(c, hipEventElapsedTime(&a, ev[k], ev[k + 1]));
-        HIP_OK(c, hipEventElapsedTime(&b, ev[k + 1], ev[k + 2]));
+        MPH_HIP_OK(c, hipEventElapsedTime(&a, ev[k], ev[k + 1]));
+        MPH_HIP_OK(c, hipEventElapsedTime(&b, ev[k + 1], ev[k + 2]));
         c->phase_ms[0] += a;
         c->phase_ms[1] += b;
     }
     return MPH_OK;
 }
 
-// Device sorted arrays -> host original order via the id arrays.
-int download_vec(MphCtx* c, const double4* d, const int* ids, double* out, int width)
+// Sorted device arrays -> host original order: the first `len` elements of each array of src and
+// the id array of their order (A.id / B.id); put(h, i, id) copies particle i's elements from the
+// host copies to where original index id belongs.  h is an array of N vectors, one per source
+// array: h[k][i] is element i of src[k] (a single array: h[0][i]).  Slab mode: ghosts (id < 0) skipped.
+template <typename T, size_t N, typename Put>
+int download(MphCtx* c, T* const (&src)[N], size_t len, const int* ids, Put put)
 {
-    const int n = c->n;
-    std::vector<double4> h(n);
-    std::vector<int> id(n);
-    HIP_OK(c, hipMemcpyAsync(h.data(), d, sizeof(double4) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipMemcpyAsync(id.data(), ids, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; ++i) {
-        if (id[i] < 0) continue;   // slab mode: ghost
-        double* o = out + (size_t)width * id[i];
-        o[0] = h[i].x;
-        if (width > 1) { o[1] = h[i].y; o[2] = h[i].z; }
-    }
-    return MPH_OK;
-}
-
-template <typename T>
-int download_scalar(MphCtx* c, const T* d, const int* ids, T* out)
-{
-    const int n = c->n;
-    std::vector<T> h(n);
-    std::vector<int> id(n);
-    HIP_OK(c, hipMemcpyAsync(h.data(), d, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipMemcpyAsync(id.data(), ids, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; ++i)
-        if (id[i] >= 0) out[id[i]] = h[i];
-    return MPH_OK;
-}
-
-// three SoA component arrays -> AoS double[n][3] in original order
-int download_soa3(MphCtx* c, const double* dx, const double* dy, const double* dz, const int* ids,
-                  double* out)
-{
-    const int n = c->n;
-    std::vector<double> h(3 * (size_t)n);
-    std::vector<int> id(n);
-    const double* src[3] = {dx, dy, dz};
-    for (int k = 0; k < 3; ++k)
-        HIP_OK(c, hipMemcpyAsync(h.data() + (size_t)k * n, src[k], sizeof(double) * n, hipMemcpyDeviceToHost,
-                                 c->stream));
-    HIP_OK(c, hipMemcpyAsync(id.data(), ids, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; ++i)
-        if (id[i] >= 0)
-            for (int k = 0; k < 3; ++k) out[3 * (size_t)id[i] + k] = h[(size_t)k * n + i];
-    return MPH_OK;
-}
-
-int download_w(MphCtx* c, const double4* d, const int* ids, double* out)
-{
-    const int n = c->n;
-    std::vector<double4> h(n);
-    std::vector<int> id(n);
-    HIP_OK(c, hipMemcpyAsync(h.data(), d, sizeof(double4) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipMemcpyAsync(id.data(), ids, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; ++i)
-        if (id[i] >= 0) out[id[i]] = h[i].w;
+    std::vector<T> h[N];
+    std::vector<int> id;
+    for (size_t k = 0; k < N; ++k) MPH_CK(fetch(c, (const T*)src[k], h[k], len));
+    MPH_CK(fetch(c, ids, id, (size_t)c->n));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < id.size(); ++i)
+        if (id[i] >= 0) put(h, i, (size_t)id[i]);
     return MPH_OK;
 }
 
@@ -275,8 +205,8 @@ int download_struct_m33(MphCtx* c, const double* d, double* out)
     if (ns == 0) return MPH_OK;
     const size_t fes = (size_t)c->Sd.fes;   // nine element planes (StructDev)
     std::vector<double> h(fes * 9);
-    HIP_OK(c, hipMemcpyAsync(h.data(), d, sizeof(double) * 9 * fes, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
+    MPH_HIP_OK(c, hipMemcpyAsync(h.data(), d, sizeof(double) * 9 * fes, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     for (int s = 0; s < ns; ++s) {
         double* o = out + (size_t)9 * c->sl_orig[s];
         for (int e = 0; e < 9; ++e) o[e] = h[e * fes + s];
@@ -324,53 +254,81 @@ struct EventProfiler final : Profiler {
 
 }  // namespace
 
-extern "C" {
-
-}  // extern "C"
-
 namespace mph {
 
 // Shared body of mph_create (dist == nullptr) and the slab-mode constructors of mph_dist.hip
 // (dist != nullptr: only this rank's particles are uploaded, the cell grid covers its window).
 static thread_local std::string g_create_error;   // mph_last_error(NULL) after a failed create
 
-static int ctx_init(MphCtx* c, const MphConfig* cfg, int n, const int* property, const double* pos,
-                    const double* pos0, const double* vel, int device, const int* ids, int n_glob)
+// The arguments of a create, and what one phase of ctx_init hands to the later ones.
+struct CreateArgs {
+    const MphConfig* cfg;
+    int n;
+    const int* property;
+    const double *pos, *pos0, *vel;
+    int device;
+    const int* ids;
+    int n_glob;
+    bool gpu_init = false;     // the fixed elastic lists are built on the device (init_host_state)
+    std::vector<int> owned;    // slab mode: the inputs this rank owns (init_capacity)
+    int cap = 0;               // capacity of every per-particle array (init_capacity)
+};
+
+template <typename T, typename V>
+static hipError_t upload(MphCtx* c, T* d, const V& v)
 {
-    if (cfg->dim != 2 && cfg->dim != 3) return MPH_ERR_ARG;
-    if (cfg->module < 0 || cfg->module > MPH_MODULE_NONE) return MPH_ERR_ARG;
-    if (!(cfg->particle_spacing > 0.0) || !(cfg->dt > 0.0) || !(cfg->elastic_dt > 0.0)) return MPH_ERR_ARG;
-    for (int i = 0; i < n; ++i)
-        if (property[i] < 0 || property[i] >= kTypes) return MPH_ERR_ARG;
-    c->cfg = *cfg;
-    c->n = n;
-    c->n_glob = n;
-    if (ids) {
-        if (!c->dist || n_glob < n) return MPH_ERR_ARG;
-        for (int i = 0; i < n; ++i)
-            if (ids[i] < 0 || ids[i] >= n_glob || (i > 0 && ids[i] <= ids[i - 1]))
-                return fail(c, MPH_ERR_ARG, "slab-local creation: ids must be ascending original indices below n_glob");
-        c->gid.assign(ids, ids + n);
-        c->n_glob = n_glob;
+    return hipMemcpyAsync(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, c->stream);
+}
+
+static int init_check_args(MphCtx* c, const CreateArgs& a)
+{
+    if (a.cfg->dim != 2 && a.cfg->dim != 3) return MPH_ERR_ARG;
+    if (a.cfg->module < 0 || a.cfg->module > MPH_MODULE_NONE) return MPH_ERR_ARG;
+    if (!(a.cfg->particle_spacing > 0.0) || !(a.cfg->dt > 0.0) || !(a.cfg->elastic_dt > 0.0)) return MPH_ERR_ARG;
+    for (int i = 0; i < a.n; ++i)
+        if (a.property[i] < 0 || a.property[i] >= kTypes) return MPH_ERR_ARG;
+    c->cfg = *a.cfg;
+    c->n = a.n;
+    c->n_glob = a.n;
+    if (a.ids) {
+        if (!c->dist || a.n_glob < a.n) return MPH_ERR_ARG;
+        for (int i = 0; i < a.n; ++i)
+            if (a.ids[i] < 0 || a.ids[i] >= a.n_glob || (i > 0 && a.ids[i] <= a.ids[i - 1]))
+                return ctx_fail(c, MPH_ERR_ARG, "slab-local creation: ids must be ascending original indices below n_glob");
+        c->gid.assign(a.ids, a.ids + a.n);
+        c->n_glob = a.n_glob;
     }
-    c->device = device;
-    c->time = cfg->time;
-    HIP_OK(c, hipSetDevice(device));
-    HIP_OK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    c->device = a.device;
+    c->time = a.cfg->time;
+    return MPH_OK;
+}
+
+// device and stream, derived constants, host copies of the static inputs, the elastic lists' host
+// part and the kernels' parameters
+static int init_host_state(MphCtx* c, CreateArgs& a)
+{
+    MPH_HIP_OK(c, hipSetDevice(a.device));
+    MPH_HIP_OK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     derive_constants(c->cfg, c->h);
-    c->prop.assign(property, property + n);
-    c->pos0.assign(pos0, pos0 + 3 * (size_t)n);
+    c->prop.assign(a.property, a.property + a.n);
+    c->pos0.assign(a.pos0, a.pos0 + 3 * (size_t)a.n);
     std::string err;
     // the fixed Lagrangian structure lists: on the device for a single context (calculate-
     // InitialNeighbor + calculateNormalizer as kernels, launch_struct_init); in slab mode on the
     // host over the particles this rank was given, which also routes the static ghost slots
     // (dist_struct_setup).  MPH_STRUCT_INIT=host selects the host build everywhere.
     const char* sie = std::getenv("MPH_STRUCT_INIT");
-    const bool gpu_init = !c->dist && !(sie && std::string(sie) == "host");
-    CK(fail(c, build_structure(c->cfg, c->h, n, property, pos0, c->S, err, !gpu_init), err));
-    const int ns = (int)c->S.orig.size();
-    make_dev_params(c->cfg, c->h, n, ns, c->P);
+    a.gpu_init = !c->dist && !(sie && std::string(sie) == "host");
+    MPH_CK(ctx_fail(c, build_structure(c->cfg, c->h, a.n, a.property, a.pos0, c->S, err, !a.gpu_init), err));
+    make_dev_params(c->cfg, c->h, a.n, (int)c->S.orig.size(), c->P);
+    return MPH_OK;
+}
+
+// the cell grid (order, cell counts, origin) and the interior boxes of the fast minimum image
+static int init_grid(MphCtx* c, const CreateArgs& a)
+{
     const double rc = std::sqrt(c->P.rc2);
+    std::string err;
     {
         // z slabs of a 3-D problem: z in the middle of the cell order, so the ghosts beyond both
         // faces are long runs (whole wavefronts) at the ends of every plane (DevParams.perm;
@@ -378,13 +336,13 @@ static int ctx_init(MphCtx* c, const MphConfig* cfg, int n, const int* property,
         // orders a single 3-D context the z-slab way -- A/B timing and the parity tests)
         const char* pe = std::getenv("MPH_SLAB_PERM");
         const std::string pv = pe ? pe : "";
-        const bool zslab = cfg->dim == 3 && c->dist && c->dist->g.axis == 2;
+        const bool zslab = a.cfg->dim == 3 && c->dist && c->dist->g.axis == 2;
         const bool forced = pv.size() == 1 && pv[0] >= '1' && pv[0] <= '4';
         c->P.perm = 0;
-        if (cfg->dim == 3 && (forced || pv == "force" || (zslab && pv != "0")))
-            c->P.perm = forced ? pv[0] - '0' : choose_cell_order(c->h, n, pos, rc);
-        int r = choose_grid(c->h, cfg->dim, rc, kContigReach, c->P.gc, c->P.ginv, err, c->P.perm);
-        if (r != MPH_OK) return fail(c, r, err);
+        if (a.cfg->dim == 3 && (forced || pv == "force" || (zslab && pv != "0")))
+            c->P.perm = forced ? pv[0] - '0' : choose_cell_order(c->h, a.n, a.pos, rc);
+        int r = choose_grid(c->h, a.cfg->dim, rc, kContigReach, c->P.gc, c->P.ginv, err, c->P.perm);
+        if (r != MPH_OK) return ctx_fail(c, r, err);
         set_uniforms(c->P);
     }
     // interior box for the wave-uniform fast minimum image (k_neighbors / passes): >= 3 cells
@@ -399,7 +357,7 @@ static int ctx_init(MphCtx* c, const MphConfig* cfg, int n, const int* property,
     const char* gsh = std::getenv("MPH_GRID_SHIFT");
     const bool shift = !(gsh && gsh[0] == '0');
     for (int d = 0; d < 3; ++d) {
-        if (d == 2 && cfg->dim == 2) {
+        if (d == 2 && a.cfg->dim == 2) {
             c->P.inner_lo[d] = c->P.sinner_lo[d] = -1e300;
             c->P.inner_hi[d] = c->P.sinner_hi[d] = 1e300;
             continue;
@@ -409,264 +367,310 @@ static int ctx_init(MphCtx* c, const MphConfig* cfg, int n, const int* property,
         const double cw = c->h.dw[d] / c->P.gc[d];
         c->P.inner_lo[d] = c->h.dmin[d] + m * cw * (1.0 + 1e-9);
         c->P.inner_hi[d] = c->h.dmax[d] - m * cw * (1.0 + 1e-9);
-        const int s0 = shift && c->P.fast_ok ? choose_grid_origin(c->h, n, pos, d, c->P.gc[d], m) : 0;
+        const int s0 = shift && c->P.fast_ok ? choose_grid_origin(c->h, a.n, a.pos, d, c->P.gc[d], m) : 0;
         c->P.corg[d] = c->h.dmin[d] + s0 * cw;
         c->P.sinner_lo[d] = m * cw * (1.0 + 1e-9);
         c->P.sinner_hi[d] = c->h.dw[d] - m * cw * (1.0 + 1e-9);
     }
+    return MPH_OK;
+}
+
+static int init_capacity(MphCtx* c, CreateArgs& a)
+{
     // slab mode: owned subset, local window grid along the slab axis, array capacity
-    std::vector<int> owned;
-    int cap = n;
+    a.cap = a.n;
     if (c->dist) {
-        CK(dist_setup(c, pos, owned));
-        cap = c->dist->cap;
-        c->n = (int)owned.size();
+        MPH_CK(dist_setup(c, a.pos, a.owned));
+        a.cap = c->dist->cap;
+        c->n = (int)a.owned.size();
         c->P.n = c->n;
     }
-    if (cap > kIndexMask)
-        return fail(c, MPH_ERR_UNSUPPORTED, "more than 2^28 particles in one context (neighbour-list entries "
+    if (a.cap > kIndexMask)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "more than 2^28 particles in one context (neighbour-list entries "
                                             "carry the type in their top bits)");
-    if ((long long)cap * 48 >= (long long)kGatherOob)
-        return fail(c, MPH_ERR_UNSUPPORTED, "more than 89 million particles in one context (the list passes "
+    if ((long long)a.cap * 48 >= (long long)kGatherOob)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "more than 89 million particles in one context (the list passes "
                                             "gather with 32-bit byte offsets)");
     {
         // the search addresses the cell table with 32-bit byte offsets (buffer descriptors)
         const long long nc = (long long)c->P.gc[0] * c->P.gc[1] * c->P.gc[2];
         if (nc + 1 > (1LL << 30))
-            return fail(c, MPH_ERR_UNSUPPORTED, "cell grid of " + std::to_string(nc) +
+            return ctx_fail(c, MPH_ERR_UNSUPPORTED, "cell grid of " + std::to_string(nc) +
                                                     " cells: more than 2^30 (4 GiB of cell starts)");
         c->P.ncell = (int)nc;
     }
-    // tables
+    return MPH_OK;
+}
+
+// the per-type tables, every array of c->L, and the initial DevState
+static int init_alloc(MphCtx* c, const CreateArgs& a)
+{
+    DevTables& T = c->tables;
     for (int t = 0; t < kTypes; ++t) {
         for (int u = 0; u < kTypes; ++u) {
-            c->T.ratio[t * kTypes + u] = c->P.ratio[t][u];
-            c->T.mu_ij[t * kTypes + u] = c->P.mu_ij[t][u];
+            T.ratio[t * kTypes + u] = c->P.ratio[t][u];
+            T.mu_ij[t * kTypes + u] = c->P.mu_ij[t][u];
         }
-        c->T.cofa[t] = c->P.cofa[t];
-        c->T.mass[t] = c->P.mass[t];
-        c->T.inv_mass[t] = c->P.inv_mass[t];
-        c->T.bulk[t] = c->P.bulk[t];
-        c->T.bulk_visc[t] = c->P.bulk_visc[t];
+        T.cofa[t] = c->P.cofa[t];
+        T.mass[t] = c->P.mass[t];
+        T.inv_mass[t] = c->P.inv_mass[t];
+        T.bulk[t] = c->P.bulk[t];
+        T.bulk_visc[t] = c->P.bulk_visc[t];
     }
     // device allocations (capacity `cap` per particle array)
+    const int cap = a.cap;
     const size_t ntile = ((size_t)cap + kTile - 1) / kTile;
-    CK(dalloc(c, &c->dT, 1));
-    CK(dalloc(c, &c->dst, 1));
-    for (Soa* s : {&c->A, &c->B}) {
+    DevTables* dT = nullptr;
+    MPH_CK(ctx_dalloc(c, &dT, 1));
+    c->L.T = dT;
+    MPH_CK(ctx_dalloc(c, &c->L.st, 1));
+    for (Soa* s : {&c->L.A, &c->L.B}) {
         const size_t m = (size_t)cap + kPad;
-        CK(dalloc(c, &s->x, m)); CK(dalloc(c, &s->y, m)); CK(dalloc(c, &s->z, m));
-        CK(dalloc(c, &s->vx, m)); CK(dalloc(c, &s->vy, m)); CK(dalloc(c, &s->vz, m));
-        CK(dalloc(c, &s->type, m)); CK(dalloc(c, &s->id, m));
+        MPH_CK(ctx_dalloc(c, &s->x, m)); MPH_CK(ctx_dalloc(c, &s->y, m)); MPH_CK(ctx_dalloc(c, &s->z, m));
+        MPH_CK(ctx_dalloc(c, &s->vx, m)); MPH_CK(ctx_dalloc(c, &s->vy, m)); MPH_CK(ctx_dalloc(c, &s->vz, m));
+        MPH_CK(ctx_dalloc(c, &s->type, m)); MPH_CK(ctx_dalloc(c, &s->id, m));
     }
-    CK(dalloc(c, &c->A.p6, 3 * (size_t)cap));
+    MPH_CK(ctx_dalloc(c, &c->L.A.p6, 3 * (size_t)cap));
     // the search's FP32 candidate records (kPad past the last)
-    CK(dalloc(c, &c->A.f4, (size_t)cap + kPad));
-    CK(dalloc(c, &c->rank_of, cap));
-    CK(dalloc(c, &c->key, cap)); CK(dalloc(c, &c->slot, cap)); CK(dalloc(c, &c->tmp, cap));
-    CK(dalloc(c, &c->cnt, c->P.ncell)); CK(dalloc(c, &c->start, (size_t)c->P.ncell + 1));
+    MPH_CK(ctx_dalloc(c, &c->L.A.f4, (size_t)cap + kPad));
+    MPH_CK(ctx_dalloc(c, &c->order, cap));
+    MPH_CK(ctx_dalloc(c, &c->L.key, cap)); MPH_CK(ctx_dalloc(c, &c->L.slot, cap));
+    MPH_CK(ctx_dalloc(c, &c->L.tmp, cap));
+    MPH_CK(ctx_dalloc(c, &c->L.cnt, c->P.ncell)); MPH_CK(ctx_dalloc(c, &c->L.start, (size_t)c->P.ncell + 1));
     // the cell scan's block totals (k_scan_reduce; structure init)
     const size_t bs = (size_t)c->P.ncell / 4096 + 2;   // bsum_stride (mph_kernels.hip)
-    CK(dalloc(c, &c->bsum, bs));
-    CK(dalloc(c, &c->nbr, ntile * kTileStride)); CK(dalloc(c, &c->ncount, cap));
-    CK(dalloc(c, &c->nbcount, cap));
+    MPH_CK(ctx_dalloc(c, &c->L.bsum, bs));
+    MPH_CK(ctx_dalloc(c, &c->L.nbr, ntile * kTileStride)); MPH_CK(ctx_dalloc(c, &c->L.ncount, cap));
+    MPH_CK(ctx_dalloc(c, &c->L.nbcount, cap));
     // the lists' row jumps: a header word per wave, a word of gap starts per lane (whole tiles)
-    CK(dalloc(c, &c->lhdr, ntile)); CK(dalloc(c, &c->lgap, ntile * kTile));
-    CK(dalloc(c, &c->pres, cap)); CK(dalloc(c, &c->gx, cap)); CK(dalloc(c, &c->gy, cap)); CK(dalloc(c, &c->gz, cap));
-    CK(dalloc(c, &c->pa, cap)); CK(dalloc(c, &c->force, cap)); CK(dalloc(c, &c->acc, cap));
-    CK(dalloc(c, &c->fpart, cap)); CK(dalloc(c, &c->rec, cap));
-    CK(dalloc(c, &c->dens_a, cap)); CK(dalloc(c, &c->vstrain, cap)); CK(dalloc(c, &c->divp, cap));
-    HIP_OK(c, hipMemsetAsync(c->cnt, 0, sizeof(int) * c->P.ncell, c->stream));
-    HIP_OK(c, hipMemsetAsync(c->bsum, 0, sizeof(int) * bs, c->stream));
-    HIP_OK(c, hipMemsetAsync(c->force, 0, sizeof(double4) * std::max(cap, 1), c->stream));
-    HIP_OK(c, hipMemsetAsync(c->acc, 0, sizeof(double4) * std::max(cap, 1), c->stream));
-    HIP_OK(c, hipMemcpyAsync(c->dT, &c->T, sizeof(DevTables), hipMemcpyHostToDevice, c->stream));
+    MPH_CK(ctx_dalloc(c, &c->L.lhdr, ntile)); MPH_CK(ctx_dalloc(c, &c->L.lgap, ntile * kTile));
+    for (double** p : {&c->L.pres, &c->L.gx, &c->L.gy, &c->L.gz, &c->L.pa}) MPH_CK(ctx_dalloc(c, p, cap));
+    for (double4** p : {&c->L.force, &c->L.acc, &c->L.fpart, &c->L.rec}) MPH_CK(ctx_dalloc(c, p, cap));
+    for (double** p : {&c->L.dens_a, &c->L.vstrain, &c->L.divp}) MPH_CK(ctx_dalloc(c, p, cap));
+    MPH_HIP_OK(c, hipMemsetAsync(c->L.cnt, 0, sizeof(int) * c->P.ncell, c->stream));
+    MPH_HIP_OK(c, hipMemsetAsync(c->L.bsum, 0, sizeof(int) * bs, c->stream));
+    MPH_HIP_OK(c, hipMemsetAsync(c->L.force, 0, sizeof(double4) * std::max(cap, 1), c->stream));
+    MPH_HIP_OK(c, hipMemsetAsync(c->L.acc, 0, sizeof(double4) * std::max(cap, 1), c->stream));
+    MPH_HIP_OK(c, hipMemcpyAsync(dT, &T, sizeof(DevTables), hipMemcpyHostToDevice, c->stream));
     DevState st{};
-    st.time = cfg->time;
+    st.time = a.cfg->time;
     for (int t = 0; t < kTypes; ++t)
         for (int d = 0; d < 3; ++d) {
-            st.wall_c[t][d] = cfg->wall_center[t][d];
-            st.wall_vel[t][d] = cfg->wall_velocity[t][d];
-            st.wall_omega[t][d] = cfg->wall_omega[t][d];
+            st.wall_c[t][d] = a.cfg->wall_center[t][d];
+            st.wall_vel[t][d] = a.cfg->wall_velocity[t][d];
+            st.wall_omega[t][d] = a.cfg->wall_omega[t][d];
             for (int e = 0; e < 3; ++e) st.wall_rot[t][d][e] = c->h.wall_rot[t][d][e];
         }
-    HIP_OK(c, hipMemcpyAsync(c->dst, &st, sizeof(DevState), hipMemcpyHostToDevice, c->stream));
-    {
-        // upload into the B set (original order, id = file index); the init sort reorders it
-        const int m = c->n;
-        std::vector<int> sel(m);
-        for (int i = 0; i < m; ++i) sel[i] = c->dist ? owned[i] : i;
-        std::vector<double> comp(m);
-        std::vector<int> gids(m), types(m);
-        double* dstc[6] = {c->B.x, c->B.y, c->B.z, c->B.vx, c->B.vy, c->B.vz};
-        for (int k = 0; k < 6; ++k) {
-            const double* src = k < 3 ? pos : vel;
-            for (int i = 0; i < m; ++i) comp[i] = src[3 * (size_t)sel[i] + (k % 3)];
-            HIP_OK(c, hipMemcpy(dstc[k], comp.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-        }
-        for (int i = 0; i < m; ++i) { gids[i] = glob_id(c, sel[i]); types[i] = property[sel[i]]; }
-        HIP_OK(c, hipMemcpy(c->B.type, types.data(), sizeof(int) * m, hipMemcpyHostToDevice));
-        HIP_OK(c, hipMemcpy(c->B.id, gids.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+    MPH_HIP_OK(c, hipMemcpyAsync(c->L.st, &st, sizeof(DevState), hipMemcpyHostToDevice, c->stream));
+    return MPH_OK;
+}
+
+static int init_upload_particles(MphCtx* c, const CreateArgs& a)
+{
+    // upload into the B set (original order, id = file index); the init sort reorders it
+    const int m = c->n;
+    std::vector<int> sel(m);
+    for (int i = 0; i < m; ++i) sel[i] = c->dist ? a.owned[i] : i;
+    std::vector<double> comp(m);
+    std::vector<int> gids(m), types(m);
+    double* dstc[6] = {c->L.B.x, c->L.B.y, c->L.B.z, c->L.B.vx, c->L.B.vy, c->L.B.vz};
+    for (int k = 0; k < 6; ++k) {
+        const double* src = k < 3 ? a.pos : a.vel;
+        for (int i = 0; i < m; ++i) comp[i] = src[3 * (size_t)sel[i] + (k % 3)];
+        MPH_HIP_OK(c, hipMemcpy(dstc[k], comp.data(), sizeof(double) * m, hipMemcpyHostToDevice));
     }
-    // elastic solid: local slots = [computed here | ghosts] (single GPU: every slot, no ghosts)
-    if (ns > 0) {
-        StructDev& D = c->Sd;
-        StructureInit& S = c->S;
-        std::vector<int> lsl;   // local slot -> global slot
-        int no = ns, ni = ns;
-        if (c->dist) {
-            CK(dist_struct_setup(c, lsl, no, ni));
-        } else {
-            lsl.resize(ns);
-            for (int s = 0; s < ns; ++s) lsl[s] = s;
-        }
-        const int nl = (int)lsl.size();
-        std::vector<int> loc(ns, -1);
-        for (int k = 0; k < nl; ++k) loc[lsl[k]] = k;
-        D.n_own = no;
-        D.n_inner = ni;
-        c->sl_orig.resize(nl);
-        for (int k = 0; k < nl; ++k) c->sl_orig[k] = glob_id(c, S.orig[lsl[k]]);
-        c->sl_s.assign(lsl.begin(), lsl.begin() + no);
-        const int sd = c->P.dim;
-        CK(dalloc(c, &D.orig, nl)); CK(dalloc(c, &D.ocnt, std::max(no, 1))); CK(dalloc(c, &D.icnt, std::max(no, 1)));
-        CK(dalloc(c, &D.bidx, nl));
-        CK(dalloc(c, &D.wx0, nl));
-        CK(dalloc(c, &D.L, (size_t)nl * 9)); CK(dalloc(c, &D.lame, nl)); CK(dalloc(c, &D.inv_rho, nl));
-        CK(dalloc(c, &D.clamp, nl)); CK(dalloc(c, &D.x0, nl)); CK(dalloc(c, &D.x, nl)); CK(dalloc(c, &D.v, nl));
-        CK(dalloc(c, &D.u, nl)); CK(dalloc(c, &D.P, (size_t)nl * (sd == 2 ? 1 : 3))); CK(dalloc(c, &D.F, (size_t)nl * 9));
-        CK(dalloc(c, &D.E, (size_t)nl * 9)); CK(dalloc(c, &D.S, (size_t)nl * 9));
-        D.fes = nl;
-        std::vector<double2> lame(nl);
-        std::vector<double> irho(nl);
-        std::vector<int> clamp(nl);
-        std::vector<double4> x0(nl);
-        for (int s = 0; s < nl; ++s) {
-            const int g = lsl[s];
-            const int i = S.orig[g];
-            const int t = property[i];
-            lame[s] = make_double2(S.lame_l[g], S.lame_m[g]);
-            irho[s] = 1.0 / cfg->density[t];
-            const double* p0 = pos0 + 3 * (size_t)i;
-            int cl = 0;   // updateElasticPosition module clamps (main.cpp:1918-2044)
-            switch (cfg->module) {
-            case MPH_MODULE_BAR: cl = p0[0] < 0.001 ? 1 : 0; break;
-            case MPH_MODULE_DAM: cl = p0[1] < 0.002 ? 1 : 0; break;
-            case MPH_MODULE_TUREK_HRON: cl = p0[0] < 0.205 ? 2 : 0; break;
-            case MPH_MODULE_ROLLING1: cl = p0[1] < 0.003 ? 1 : 0; break;
-            case MPH_MODULE_HYDROELASTIC: cl = (p0[0] < 0.01 || p0[0] > 1.99) ? 1 : 0; break;
-            default: cl = 0;
-            }
-            clamp[s] = cl;
-            x0[s] = make_double4(p0[0], p0[1], p0[2], (double)t);
-        }
-        auto up = [&](auto* d, const auto& v) {
-            return hipMemcpyAsync(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, c->stream);
-        };
-        HIP_OK(c, up(D.x0, x0));
-        if (gpu_init) {
-            // calculateInitialNeighbor + calculateNormalizer on the device (single context: the
-            // local slots are all slots, in file order); the host keeps counts and normalizers
-            // for mph_get
-            fill_launch(c);
-            auto alloc = [](void* ctx, size_t bytes) -> void* {
-                int st = MPH_OK;
-                return ctx_alloc((MphCtx*)ctx, bytes, &st);
-            };
-            const int r = launch_struct_init(c->L, ns, D.x0, c->key, c->slot, c->tmp, c->rank_of, D.ocnt, D.icnt,
-                                             &D.eo_nb, &D.wo, &D.ei_nb, &D.wi, D.L, D.wx0, alloc, c);
-            if (r == -2) return fail(c, MPH_ERR_NEIGHBOR_OVERFLOW, "a structure particle has >= 512 initial neighbours");
-            if (r == -3) return fail(c, MPH_ERR_DEVICE_OOM, "structure list allocation failed");
-            if (r != 0) return fail(c, MPH_ERR_HIP, "structure initialisation kernels failed");
-            S.count.resize(ns);
-            S.normalizer.resize((size_t)ns * 9);
-            HIP_OK(c, hipMemcpyAsync(S.count.data(), D.ocnt, sizeof(int) * ns, hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(c, hipMemcpyAsync(S.normalizer.data(), D.L, sizeof(double) * 9 * ns, hipMemcpyDeviceToHost,
-                                     c->stream));
-            HIP_OK(c, hipStreamSynchronize(c->stream));
-        } else {
-            // ELL tiles of the host-built fixed out-list and of its transpose (StructDev), computed slots only
-            const size_t ntile_s = ((size_t)std::max(no, 1) + 63) / 64;
-            std::vector<int> ocnt(std::max(no, 1), 0), icnt(std::max(no, 1), 0);
-            int wo = 0, wi = 0;
-            for (int s = 0; s < no; ++s) {
-                const int g = lsl[s];
-                ocnt[s] = S.offset[g + 1] - S.offset[g];
-                icnt[s] = S.in_offset[g + 1] - S.in_offset[g];
-                wo = std::max(wo, ocnt[s]);
-                wi = std::max(wi, icnt[s]);
-            }
-            wo = std::max(wo, 1);
-            wi = std::max(wi, 1);
-            D.wo = wo;
-            D.wi = wi;
-            std::vector<int> eo_nb(ntile_s * wo * 64, 0), ei_nb(ntile_s * wi * 64, 0);
-            std::vector<double4> wx0(nl, make_double4(0.0, 0.0, 0.0, 0.0));
-            for (int s = 0; s < no; ++s) {
-                const int g = lsl[s];
-                const size_t base_o = (size_t)(s >> 6) * wo * 64 + (s & 63);
-                double c3[3] = {0.0, 0.0, 0.0};
-                for (int k = 0; k < ocnt[s]; ++k) {
-                    const size_t q = S.offset[g] + k;
-                    const double* pr = &S.pair_out[4 * q];
-                    eo_nb[base_o + (size_t)k * 64] = loc[S.nbr[q]];
-                    for (int d = 0; d < 3; ++d) c3[d] += pr[3] * pr[d];
-                }
-                wx0[s] = make_double4(c3[0], c3[1], c3[2], 0.0);
-                const size_t base_i = (size_t)(s >> 6) * wi * 64 + (s & 63);
-                for (int k = 0; k < icnt[s]; ++k) {
-                    const size_t q = S.in_offset[g] + k;
-                    ei_nb[base_i + (size_t)k * 64] = loc[S.in_nbr[q]];
-                }
-            }
-            for (int e : eo_nb) if (e < 0) return fail(c, MPH_ERR_DOMAIN, "structure list leaves the ghost slots");
-            for (int e : ei_nb) if (e < 0) return fail(c, MPH_ERR_DOMAIN, "structure list leaves the ghost slots");
-            std::vector<double> Lm((size_t)nl * 9);
-            for (int s = 0; s < nl; ++s)
-                std::memcpy(&Lm[(size_t)9 * s], &S.normalizer[(size_t)9 * lsl[s]], sizeof(double) * 9);
-            CK(dalloc(c, &D.eo_nb, eo_nb.size()));
-            CK(dalloc(c, &D.ei_nb, ei_nb.size()));
-            HIP_OK(c, up(D.ocnt, ocnt)); HIP_OK(c, up(D.icnt, icnt));
-            HIP_OK(c, up(D.eo_nb, eo_nb));
-            HIP_OK(c, up(D.ei_nb, ei_nb));
-            HIP_OK(c, up(D.wx0, wx0));
-            HIP_OK(c, up(D.L, Lm));
-        }
-        HIP_OK(c, hipMemcpyAsync(D.orig, c->sl_orig.data(), sizeof(int) * nl, hipMemcpyHostToDevice, c->stream));
-        {
-            std::vector<int> slot_of((size_t)c->n_glob, -1);
-            for (int s = 0; s < no; ++s) slot_of[c->sl_orig[s]] = s;
-            CK(dalloc(c, &D.slot_of, slot_of.size()));
-            HIP_OK(c, hipMemcpy(D.slot_of, slot_of.data(), sizeof(int) * slot_of.size(), hipMemcpyHostToDevice));
-        }
-        HIP_OK(c, up(D.lame, lame));
-        HIP_OK(c, up(D.inv_rho, irho));
-        HIP_OK(c, up(D.clamp, clamp));
-        HIP_OK(c, hipMemsetAsync(D.P, 0, sizeof(double4) * (sd == 2 ? 1 : 3) * nl, c->stream));
-        HIP_OK(c, hipMemsetAsync(D.u, 0, sizeof(double4) * nl, c->stream));
-        HIP_OK(c, hipMemsetAsync(D.bidx, 0, sizeof(int) * nl, c->stream));
-        for (double* m : {D.F, D.E, D.S})
-            HIP_OK(c, hipMemsetAsync(m, 0, sizeof(double) * 9 * nl, c->stream));
-        HIP_OK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < m; ++i) { gids[i] = glob_id(c, sel[i]); types[i] = a.property[sel[i]]; }
+    MPH_HIP_OK(c, hipMemcpy(c->L.B.type, types.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+    MPH_HIP_OK(c, hipMemcpy(c->L.B.id, gids.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+    return MPH_OK;
+}
+
+// calculateInitialNeighbor + calculateNormalizer on the device (single context: the local slots
+// are all slots, in file order); the host keeps counts and normalizers for mph_get
+static int elastic_device_build(MphCtx* c, int ns)
+{
+    StructDev& D = c->Sd;
+    StructureInit& S = c->S;
+    ctx_fill_launch(c);
+    auto alloc = [](void* ctx, size_t bytes) -> void* {
+        int st = MPH_OK;
+        return ctx_alloc((MphCtx*)ctx, bytes, &st);
+    };
+    const int r = launch_struct_init(c->L, ns, D.x0, c->L.key, c->L.slot, c->L.tmp, c->order, D.ocnt, D.icnt,
+                                     &D.eo_nb, &D.wo, &D.ei_nb, &D.wi, D.L, D.wx0, alloc, c);
+    if (r == -2) return ctx_fail(c, MPH_ERR_NEIGHBOR_OVERFLOW, "a structure particle has >= 512 initial neighbours");
+    if (r == -3) return ctx_fail(c, MPH_ERR_DEVICE_OOM, "structure list allocation failed");
+    if (r != 0) return ctx_fail(c, MPH_ERR_HIP, "structure initialisation kernels failed");
+    S.count.resize(ns);
+    S.normalizer.resize((size_t)ns * 9);
+    MPH_HIP_OK(c, hipMemcpyAsync(S.count.data(), D.ocnt, sizeof(int) * ns, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipMemcpyAsync(S.normalizer.data(), D.L, sizeof(double) * 9 * ns, hipMemcpyDeviceToHost,
+                             c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    return MPH_OK;
+}
+
+// ELL tiles of the host-built fixed out-list and of its transpose (StructDev), computed slots only
+static int elastic_host_build(MphCtx* c, const std::vector<int>& lsl, int no)
+{
+    StructDev& D = c->Sd;
+    const StructureInit& S = c->S;
+    const int nl = (int)lsl.size();
+    std::vector<int> loc(S.orig.size(), -1);
+    for (int k = 0; k < nl; ++k) loc[lsl[k]] = k;
+    const size_t ntile_s = ((size_t)std::max(no, 1) + 63) / 64;
+    std::vector<int> ocnt(std::max(no, 1), 0), icnt(std::max(no, 1), 0);
+    int wo = 0, wi = 0;
+    for (int s = 0; s < no; ++s) {
+        const int g = lsl[s];
+        ocnt[s] = S.offset[g + 1] - S.offset[g];
+        icnt[s] = S.in_offset[g + 1] - S.in_offset[g];
+        wo = std::max(wo, ocnt[s]);
+        wi = std::max(wi, icnt[s]);
     }
-    fill_launch(c);
+    wo = std::max(wo, 1);
+    wi = std::max(wi, 1);
+    D.wo = wo;
+    D.wi = wi;
+    std::vector<int> eo_nb(ntile_s * wo * 64, 0), ei_nb(ntile_s * wi * 64, 0);
+    std::vector<double4> wx0(nl, make_double4(0.0, 0.0, 0.0, 0.0));
+    for (int s = 0; s < no; ++s) {
+        const int g = lsl[s];
+        const size_t base_o = (size_t)(s >> 6) * wo * 64 + (s & 63);
+        double c3[3] = {0.0, 0.0, 0.0};
+        for (int k = 0; k < ocnt[s]; ++k) {
+            const size_t q = S.offset[g] + k;
+            const double* pr = &S.pair_out[4 * q];
+            eo_nb[base_o + (size_t)k * 64] = loc[S.nbr[q]];
+            for (int d = 0; d < 3; ++d) c3[d] += pr[3] * pr[d];
+        }
+        wx0[s] = make_double4(c3[0], c3[1], c3[2], 0.0);
+        const size_t base_i = (size_t)(s >> 6) * wi * 64 + (s & 63);
+        for (int k = 0; k < icnt[s]; ++k) {
+            const size_t q = S.in_offset[g] + k;
+            ei_nb[base_i + (size_t)k * 64] = loc[S.in_nbr[q]];
+        }
+    }
+    for (int e : eo_nb) if (e < 0) return ctx_fail(c, MPH_ERR_DOMAIN, "structure list leaves the ghost slots");
+    for (int e : ei_nb) if (e < 0) return ctx_fail(c, MPH_ERR_DOMAIN, "structure list leaves the ghost slots");
+    std::vector<double> Lm((size_t)nl * 9);
+    for (int s = 0; s < nl; ++s)
+        std::memcpy(&Lm[(size_t)9 * s], &S.normalizer[(size_t)9 * lsl[s]], sizeof(double) * 9);
+    MPH_CK(ctx_dalloc(c, &D.eo_nb, eo_nb.size()));
+    MPH_CK(ctx_dalloc(c, &D.ei_nb, ei_nb.size()));
+    MPH_HIP_OK(c, upload(c, D.ocnt, ocnt)); MPH_HIP_OK(c, upload(c, D.icnt, icnt));
+    MPH_HIP_OK(c, upload(c, D.eo_nb, eo_nb));
+    MPH_HIP_OK(c, upload(c, D.ei_nb, ei_nb));
+    MPH_HIP_OK(c, upload(c, D.wx0, wx0));
+    MPH_HIP_OK(c, upload(c, D.L, Lm));
+    return MPH_OK;
+}
+
+// elastic solid: local slots = [computed here | ghosts] (single GPU: every slot, no ghosts)
+static int init_elastic(MphCtx* c, const CreateArgs& a)
+{
+    const int ns = (int)c->S.orig.size();
+    if (ns == 0) return MPH_OK;
+    StructDev& D = c->Sd;
+    StructureInit& S = c->S;
+    std::vector<int> lsl;   // local slot -> global slot
+    int no = ns, ni = ns;
     if (c->dist) {
-        // slab mode: allocations of the exchange, then the initial ghost exchange + init sums
-        CK(dist_alloc(c));
-        CK(dist_init(c));
+        MPH_CK(dist_struct_setup(c, lsl, no, ni));
     } else {
-        // initialisation sums, main.cpp:565-568 (calculateNeighbor, DensityA, GravityCenter, DensityP)
+        lsl.resize(ns);
+        for (int s = 0; s < ns; ++s) lsl[s] = s;
+    }
+    const int nl = (int)lsl.size();
+    D.n_own = no;
+    D.n_inner = ni;
+    c->sl_orig.resize(nl);
+    for (int k = 0; k < nl; ++k) c->sl_orig[k] = glob_id(c, S.orig[lsl[k]]);
+    c->sl_s.assign(lsl.begin(), lsl.begin() + no);
+    const int sd = c->P.dim;
+    MPH_CK(ctx_dalloc(c, &D.orig, nl));
+    MPH_CK(ctx_dalloc(c, &D.ocnt, std::max(no, 1))); MPH_CK(ctx_dalloc(c, &D.icnt, std::max(no, 1)));
+    MPH_CK(ctx_dalloc(c, &D.bidx, nl));
+    MPH_CK(ctx_dalloc(c, &D.wx0, nl));
+    MPH_CK(ctx_dalloc(c, &D.L, (size_t)nl * 9)); MPH_CK(ctx_dalloc(c, &D.lame, nl)); MPH_CK(ctx_dalloc(c, &D.inv_rho, nl));
+    MPH_CK(ctx_dalloc(c, &D.clamp, nl));
+    for (double4** p : {&D.x0, &D.x, &D.v, &D.u}) MPH_CK(ctx_dalloc(c, p, nl));
+    MPH_CK(ctx_dalloc(c, &D.P, (size_t)nl * (sd == 2 ? 1 : 3)));
+    for (double** p : {&D.F, &D.E, &D.S}) MPH_CK(ctx_dalloc(c, p, (size_t)nl * 9));
+    D.fes = nl;
+    std::vector<double2> lame(nl);
+    std::vector<double> irho(nl);
+    std::vector<int> clamp(nl);
+    std::vector<double4> x0(nl);
+    for (int s = 0; s < nl; ++s) {
+        const int g = lsl[s];
+        const int i = S.orig[g];
+        const int t = a.property[i];
+        lame[s] = make_double2(S.lame_l[g], S.lame_m[g]);
+        irho[s] = 1.0 / a.cfg->density[t];
+        const double* p0 = a.pos0 + 3 * (size_t)i;
+        int cl = 0;   // updateElasticPosition module clamps (main.cpp:1918-2044)
+        switch (a.cfg->module) {
+        case MPH_MODULE_BAR: cl = p0[0] < 0.001 ? 1 : 0; break;
+        case MPH_MODULE_DAM: cl = p0[1] < 0.002 ? 1 : 0; break;
+        case MPH_MODULE_TUREK_HRON: cl = p0[0] < 0.205 ? 2 : 0; break;
+        case MPH_MODULE_ROLLING1: cl = p0[1] < 0.003 ? 1 : 0; break;
+        case MPH_MODULE_HYDROELASTIC: cl = (p0[0] < 0.01 || p0[0] > 1.99) ? 1 : 0; break;
+        default: cl = 0;
+        }
+        clamp[s] = cl;
+        x0[s] = make_double4(p0[0], p0[1], p0[2], (double)t);
+    }
+    MPH_HIP_OK(c, upload(c, D.x0, x0));
+    MPH_CK(a.gpu_init ? elastic_device_build(c, ns) : elastic_host_build(c, lsl, no));
+    MPH_HIP_OK(c, hipMemcpyAsync(D.orig, c->sl_orig.data(), sizeof(int) * nl, hipMemcpyHostToDevice, c->stream));
+    {
+        std::vector<int> slot_of((size_t)c->n_glob, -1);
+        for (int s = 0; s < no; ++s) slot_of[c->sl_orig[s]] = s;
+        MPH_CK(ctx_dalloc(c, &D.slot_of, slot_of.size()));
+        MPH_HIP_OK(c, hipMemcpy(D.slot_of, slot_of.data(), sizeof(int) * slot_of.size(), hipMemcpyHostToDevice));
+    }
+    MPH_HIP_OK(c, upload(c, D.lame, lame));
+    MPH_HIP_OK(c, upload(c, D.inv_rho, irho));
+    MPH_HIP_OK(c, upload(c, D.clamp, clamp));
+    MPH_HIP_OK(c, hipMemsetAsync(D.P, 0, sizeof(double4) * (sd == 2 ? 1 : 3) * nl, c->stream));
+    MPH_HIP_OK(c, hipMemsetAsync(D.u, 0, sizeof(double4) * nl, c->stream));
+    MPH_HIP_OK(c, hipMemsetAsync(D.bidx, 0, sizeof(int) * nl, c->stream));
+    for (double* m : {D.F, D.E, D.S})
+        MPH_HIP_OK(c, hipMemsetAsync(m, 0, sizeof(double) * 9 * nl, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    return MPH_OK;
+}
+
+// slab mode: the exchange's allocations, the initial ghost exchange and the init sums; else the
+// initialisation sums of main.cpp:565-568 (calculateNeighbor, DensityA, GravityCenter, DensityP)
+static int init_first_sums(MphCtx* c)
+{
+    ctx_fill_launch(c);
+    if (c->dist) {
+        MPH_CK(dist_alloc(c));
+        MPH_CK(dist_init(c));
+    } else {
         launch_sort(c->L, 0);
         launch_search_pass_a(c->L);
     }
-    HIP_OK(c, hipGetLastError());
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    {
-        DevState hs;
-        HIP_OK(c, hipMemcpy(&hs, c->dst, kStateHead, hipMemcpyDeviceToHost));
-        CK(ctx_state_status(c, hs));
-    }
-    return MPH_OK;
+    MPH_HIP_OK(c, hipGetLastError());
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    DevState hs;
+    MPH_HIP_OK(c, hipMemcpy(&hs, c->L.st, kStateHead, hipMemcpyDeviceToHost));
+    return ctx_state_status(c, hs);
+}
+
+static int ctx_init(MphCtx* c, CreateArgs& a)
+{
+    MPH_CK(init_check_args(c, a));
+    MPH_CK(init_host_state(c, a));
+    MPH_CK(init_grid(c, a));
+    MPH_CK(init_capacity(c, a));
+    MPH_CK(init_alloc(c, a));
+    MPH_CK(init_upload_particles(c, a));
+    MPH_CK(init_elastic(c, a));
+    return init_first_sums(c);
 }
 
 void ctx_set_global_error(const std::string& msg) { g_create_error = msg; }
@@ -683,7 +687,8 @@ int ctx_create(MphCtx** out, const MphConfig* cfg, int n, const int* property, c
     *out = nullptr;
     MphCtx* c = new MphCtx();
     c->dist = dist;
-    const int r = ctx_init(c, cfg, n, property, pos, pos0, vel, device, ids, n_glob);
+    CreateArgs a{cfg, n, property, pos, pos0, vel, device, ids, n_glob};
+    const int r = ctx_init(c, a);
     if (r != MPH_OK) {
         g_create_error = c->err.empty() ? "mph_create failed with status " + std::to_string(r) : c->err;
         mph_destroy(c);
@@ -709,14 +714,14 @@ int mph_create(MphCtx** out, const MphConfig* cfg, int n, const int* property, c
 static int ctx_flush(MphCtx* c)
 {
     if (!c->pending && !c->unchecked) return MPH_OK;
-    HIP_OK(c, hipSetDevice(c->device));
-    if (c->pending) CK(capture_graphs(c));
-    if (c->pending) CK(launch_singles(c, c->pending));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    if (c->pending) MPH_CK(capture_graphs(c));
+    if (c->pending) MPH_CK(launch_singles(c, c->pending));
     c->pending = 0;
     c->unchecked = false;
     DevState hs;
-    HIP_OK(c, hipMemcpyAsync(&hs, c->dst, kStateHead, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
+    MPH_HIP_OK(c, hipMemcpyAsync(&hs, c->L.st, kStateHead, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     return ctx_state_status(c, hs);
 }
 
@@ -731,21 +736,21 @@ static int step_batched(MphCtx* c, int nsteps)
     c->stepped = true;
     c->pending += nsteps;
     bool launched = false;
-    CK(capture_graphs(c));
+    MPH_CK(capture_graphs(c));
     while (c->pending >= 8) {
-        HIP_OK(c, hipGraphLaunch(c->graph8, c->stream));
+        MPH_HIP_OK(c, hipGraphLaunch(c->graph8, c->stream));
         c->pending -= 8;
         launched = true;
     }
     if (launched) {
-        HIP_OK(c, hipMemcpyAsync(c->hs_pin, c->dst, kStateHead, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(c, hipEventRecord(c->ev_status, c->stream));
+        MPH_HIP_OK(c, hipMemcpyAsync(c->hs_pin, c->L.st, kStateHead, hipMemcpyDeviceToHost, c->stream));
+        MPH_HIP_OK(c, hipEventRecord(c->ev_status, c->stream));
         c->unchecked = true;
     }
     if (c->unchecked && hipEventQuery(c->ev_status) == hipSuccess) {
         DevState hs;
         std::memcpy(&hs, c->hs_pin, kStateHead);
-        CK(ctx_state_status(c, hs));
+        MPH_CK(ctx_state_status(c, hs));
     }
     return MPH_OK;
 }
@@ -753,14 +758,14 @@ static int step_batched(MphCtx* c, int nsteps)
 int mph_set_step_batching(MphCtx* c, int on)
 {
     if (!c) return MPH_ERR_ARG;
-    if (c->dist) return on ? fail(c, MPH_ERR_ARG, "step batching is not available in slab mode") : MPH_OK;
-    HIP_OK(c, hipSetDevice(c->device));
+    if (c->dist) return on ? ctx_fail(c, MPH_ERR_ARG, "step batching is not available in slab mode") : MPH_OK;
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     if (!on) {
         c->batch_steps = false;
         return ctx_flush(c);
     }
-    if (!c->hs_pin) HIP_OK(c, hipHostMalloc(&c->hs_pin, kStateHead, hipHostMallocDefault));
-    if (!c->ev_status) HIP_OK(c, hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming));
+    if (!c->hs_pin) MPH_HIP_OK(c, hipHostMalloc(&c->hs_pin, kStateHead, hipHostMallocDefault));
+    if (!c->ev_status) MPH_HIP_OK(c, hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming));
     c->batch_steps = true;
     return MPH_OK;
 }
@@ -768,14 +773,14 @@ int mph_set_step_batching(MphCtx* c, int on)
 int mph_step(MphCtx* c, int nsteps)
 {
     if (!c || nsteps < 0) return MPH_ERR_ARG;
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     if (c->dist) return dist_step(c, nsteps);
     if (nsteps == 0 || c->n == 0) {
         for (int k = 0; k < nsteps; ++k) c->time += c->cfg.dt;
         return MPH_OK;
     }
     if (c->batch_steps && !c->phase_timing) return step_batched(c, nsteps);
-    CK(ctx_flush(c));
+    MPH_CK(ctx_flush(c));
     int left = nsteps;
     if (c->phase_timing) {
         // the graphs' batches (8 steps, then single steps; the output-only stores on each batch's
@@ -784,36 +789,36 @@ int mph_step(MphCtx* c, int nsteps)
         while (left > 0) {
             const int b = left >= 8 ? 8 : 1;
             for (int k = 0; k < b; ++k) enqueue_step(c->L, k == b - 1, c->ev8.data() + 3 * k);
-            HIP_OK(c, hipGetLastError());
-            CK(accumulate_phases(c, c->ev8, b));
+            MPH_HIP_OK(c, hipGetLastError());
+            MPH_CK(accumulate_phases(c, c->ev8, b));
             left -= b;
         }
     } else {
-        CK(capture_graphs(c));
-        while (left >= 8) { HIP_OK(c, hipGraphLaunch(c->graph8, c->stream)); left -= 8; }
-        CK(launch_singles(c, left));
+        MPH_CK(capture_graphs(c));
+        while (left >= 8) { MPH_HIP_OK(c, hipGraphLaunch(c->graph8, c->stream)); left -= 8; }
+        MPH_CK(launch_singles(c, left));
     }
     for (int k = 0; k < nsteps; ++k) c->time += c->cfg.dt;
     c->stepped = true;
     // the error flags, copied into pinned memory behind the steps (a pageable copy is staged by the
     // runtime).  Polling the stream instead of the blocking wait measured the same per call
     // (profiles/r05/sync_path/).
-    if (!c->hs_pin) HIP_OK(c, hipHostMalloc(&c->hs_pin, kStateHead, hipHostMallocDefault));
-    HIP_OK(c, hipMemcpyAsync(c->hs_pin, c->dst, kStateHead, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
+    if (!c->hs_pin) MPH_HIP_OK(c, hipHostMalloc(&c->hs_pin, kStateHead, hipHostMallocDefault));
+    MPH_HIP_OK(c, hipMemcpyAsync(c->hs_pin, c->L.st, kStateHead, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     DevState hs;
     std::memcpy(&hs, c->hs_pin, kStateHead);
-    CK(ctx_state_status(c, hs));
+    MPH_CK(ctx_state_status(c, hs));
     return MPH_OK;
 }
 
 int mph_synchronize(MphCtx* c)
 {
     if (!c) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     // slab mode: the second stream too (halo, face pass B, early send, elastic ghost exchanges)
-    if (c->dist && c->dist->stream2) HIP_OK(c, hipStreamSynchronize(c->dist->stream2));
+    if (c->dist && c->dist->stream2) MPH_HIP_OK(c, hipStreamSynchronize(c->dist->stream2));
     return MPH_OK;
 }
 
@@ -831,8 +836,8 @@ int mph_get_scalars(const MphCtx* c, double* out)
 int mph_get(MphCtx* c, int field, void* out)
 {
     if (!c || !out) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     double* o = (double*)out;
     int* oi = (int*)out;
     // structure rows: every list built here (single context), or the slots this rank computes
@@ -841,28 +846,48 @@ int mph_get(MphCtx* c, int field, void* out)
     auto sidx = [c](int k) { return c->dist ? c->sl_s[k] : k; };
     // static inputs: every particle, or (slab-local creation) the ones this rank was created with
     const int nin = (int)c->prop.size();
+    // sorted device arrays -> original order (download; in its callbacks h[k][i] is element i of
+    // the k-th array given): get3 three component arrays into [id][3], get4 the xyz of a double4
+    // array in A order into [id][3], get1 a scalar array in A order into out[id]
+    const size_t n = (size_t)c->n;
+    auto get3 = [&](double* x, double* y, double* z, const int* ids) {
+        double* const src[3] = {x, y, z};
+        return download(c, src, n, ids, [o](auto* h, size_t i, size_t id) {
+            for (int k = 0; k < 3; ++k) o[3 * id + k] = h[k][i];
+        });
+    };
+    auto get4 = [&](double4* d) {
+        double4* const src[1] = {d};
+        return download(c, src, n, c->L.A.id, [o](auto* h, size_t i, size_t id) {
+            o[3 * id] = h[0][i].x; o[3 * id + 1] = h[0][i].y; o[3 * id + 2] = h[0][i].z;
+        });
+    };
+    auto get1 = [&](auto* d, auto* out) {
+        decltype(d) const src[1] = {d};   // (an array of one pointer to d's element type)
+        return download(c, src, n, c->L.A.id, [out](auto* h, size_t i, size_t id) { out[id] = h[0][i]; });
+    };
     switch (field) {
-    case MPH_FIELD_POSITION: return download_soa3(c, c->B.x, c->B.y, c->B.z, c->B.id, o);
-    case MPH_FIELD_VELOCITY: return download_soa3(c, c->B.vx, c->B.vy, c->B.vz, c->B.id, o);
+    case MPH_FIELD_POSITION: return get3(c->L.B.x, c->L.B.y, c->L.B.z, c->L.B.id);
+    case MPH_FIELD_VELOCITY: return get3(c->L.B.vx, c->L.B.vy, c->L.B.vz, c->L.B.id);
     case MPH_FIELD_INITIAL_POSITION:
         for (int k = 0; k < nin; ++k) std::memcpy(o + 3 * (size_t)glob_id(c, k), &c->pos0[3 * (size_t)k], 3 * sizeof(double));
         return MPH_OK;
-    case MPH_FIELD_FORCE: return download_vec(c, c->force, c->A.id, o, 3);
-    case MPH_FIELD_ACCELERATION: return download_vec(c, c->acc, c->A.id, o, 3);
-    case MPH_FIELD_GRAVITY_CENTER: return download_soa3(c, c->gx, c->gy, c->gz, c->A.id, o);
-    case MPH_FIELD_PRESSURE_P: return download_scalar(c, c->pres, c->A.id, o);
-    case MPH_FIELD_PRESSURE_A: return download_scalar(c, c->pa, c->A.id, o);
-    case MPH_FIELD_DENSITY_A: return download_scalar(c, c->dens_a, c->A.id, o);
-    case MPH_FIELD_VOL_STRAIN_P: return download_scalar(c, c->vstrain, c->A.id, o);
-    case MPH_FIELD_DIVERGENCE_P: return download_scalar(c, c->divp, c->A.id, o);
-    case MPH_FIELD_NEIGHBOR_COUNT: return download_scalar(c, c->nbcount, c->A.id, oi);
+    case MPH_FIELD_FORCE: return get4(c->L.force);
+    case MPH_FIELD_ACCELERATION: return get4(c->L.acc);
+    case MPH_FIELD_GRAVITY_CENTER: return get3(c->L.gx, c->L.gy, c->L.gz, c->L.A.id);
+    case MPH_FIELD_PRESSURE_P: return get1(c->L.pres, o);
+    case MPH_FIELD_PRESSURE_A: return get1(c->L.pa, o);
+    case MPH_FIELD_DENSITY_A: return get1(c->L.dens_a, o);
+    case MPH_FIELD_VOL_STRAIN_P: return get1(c->L.vstrain, o);
+    case MPH_FIELD_DIVERGENCE_P: return get1(c->L.divp, o);
+    case MPH_FIELD_NEIGHBOR_COUNT: return get1(c->L.nbcount, oi);
     case MPH_FIELD_MASS:
         for (int k = 0; k < nin; ++k) o[glob_id(c, k)] = c->cfg.density[c->prop[k]] * c->h.vol;
         return MPH_OK;
     case MPH_FIELD_KAPPA: {
         // initializeFluid (1317-1319) before the first step, calculatePhysicalCoefficients after
         std::vector<double> vs(c->stepped ? (size_t)c->n_glob : 0, 0.0);
-        if (c->stepped) CK(download_scalar(c, c->vstrain, c->A.id, vs.data()));
+        if (c->stepped) MPH_CK(get1(c->L.vstrain, vs.data()));
         for (int k = 0; k < nin; ++k) {
             const int i = glob_id(c, k);
             o[i] = (c->stepped && vs[i] < 0.0) ? 0.0 : c->cfg.bulk_modulus[c->prop[k]];
@@ -893,18 +918,13 @@ int mph_get(MphCtx* c, int field, void* out)
         return MPH_OK;
     case MPH_FIELD_VIRIAL_STRESS:
     case MPH_FIELD_VIRIAL_PRESSURE: {
-        const int w = field == MPH_FIELD_VIRIAL_STRESS ? 9 : 1;
+        const size_t w = field == MPH_FIELD_VIRIAL_STRESS ? 9 : 1;
         std::memset(o, 0, sizeof(double) * w * (size_t)c->n_glob);
         if (!c->vir) return MPH_OK;   // never computed (the reference's array is uninitialised)
-        std::vector<double> h((size_t)w * c->n);
-        std::vector<int> id(c->n);
-        HIP_OK(c, hipMemcpyAsync(h.data(), w == 9 ? c->vir : c->vpres, sizeof(double) * w * c->n,
-                                 hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(c, hipMemcpyAsync(id.data(), c->A.id, sizeof(int) * c->n, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < c->n; ++i)
-            if (id[i] >= 0) std::memcpy(o + (size_t)w * id[i], &h[(size_t)w * i], sizeof(double) * w);
-        return MPH_OK;
+        double* const src[1] = {w == 9 ? c->vir : c->vpres};
+        return download(c, src, w * n, c->L.A.id, [o, w](auto* h, size_t i, size_t id) {
+            std::memcpy(o + w * id, &h[0][w * i], sizeof(double) * w);
+        });
     }
     case MPH_FIELD_LAMBDA_LAMES:
     case MPH_FIELD_MU_LAMES:
@@ -913,32 +933,32 @@ int mph_get(MphCtx* c, int field, void* out)
             o[glob_id(c, c->S.orig[sidx(k)])] =
                 field == MPH_FIELD_LAMBDA_LAMES ? c->S.lame_l[sidx(k)] : c->S.lame_m[sidx(k)];
         return MPH_OK;
-    default: return fail(c, MPH_ERR_ARG, "unknown field " + std::to_string(field));
+    default: return ctx_fail(c, MPH_ERR_ARG, "unknown field " + std::to_string(field));
     }
 }
 
 int mph_compute_virial(MphCtx* c)
 {
     if (!c) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     if (!c->vir) {
         // slab mode: the array capacity (c->P.n), the held count changes every step
         const size_t cap = (size_t)std::max(c->dist ? c->P.n : c->n, 1);
-        CK(dalloc(c, &c->vir, 9 * cap));
-        CK(dalloc(c, &c->vpres, cap));
+        MPH_CK(ctx_dalloc(c, &c->vir, 9 * cap));
+        MPH_CK(ctx_dalloc(c, &c->vpres, cap));
     }
     if (c->dist) return dist_virial(c);
     // after a step the integrated state B is in A (list) order; before the first step A is current
-    if (c->phase_timing) HIP_OK(c, hipEventRecord(c->ev_vir[0], c->stream));
-    CK(virial_full_lists(c));
-    launch_virial(c->L, c->stepped ? c->B : c->A, c->vir, c->vpres);
-    HIP_OK(c, hipGetLastError());
-    if (c->phase_timing) HIP_OK(c, hipEventRecord(c->ev_vir[1], c->stream));
-    HIP_OK(c, hipStreamSynchronize(c->stream));
+    if (c->phase_timing) MPH_HIP_OK(c, hipEventRecord(c->ev_vir[0], c->stream));
+    MPH_CK(virial_full_lists(c));
+    launch_virial(c->L, c->stepped ? c->L.B : c->L.A, c->vir, c->vpres);
+    MPH_HIP_OK(c, hipGetLastError());
+    if (c->phase_timing) MPH_HIP_OK(c, hipEventRecord(c->ev_vir[1], c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     if (c->phase_timing) {
         float ms = 0.0f;
-        HIP_OK(c, hipEventElapsedTime(&ms, c->ev_vir[0], c->ev_vir[1]));
+        MPH_HIP_OK(c, hipEventElapsedTime(&ms, c->ev_vir[0], c->ev_vir[1]));
         c->phase_ms[2] += ms;
     }
     return MPH_OK;
@@ -947,21 +967,21 @@ int mph_compute_virial(MphCtx* c)
 int mph_set(MphCtx* c, int field, const void* in)
 {
     if (!c || !in) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
+    MPH_CK(ctx_flush(c));
     if (field != MPH_FIELD_POSITION && field != MPH_FIELD_VELOCITY)
-        return fail(c, MPH_ERR_ARG, "mph_set supports Position and Velocity");
-    HIP_OK(c, hipSetDevice(c->device));
+        return ctx_fail(c, MPH_ERR_ARG, "mph_set supports Position and Velocity");
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     const int n = c->n;
     const double* v = (const double*)in;
     // current state lives in the B set in the order of B.id: rewrite it in that order
     std::vector<double> h(n);
     std::vector<int> id(n);
-    HIP_OK(c, hipMemcpy(id.data(), c->B.id, sizeof(int) * n, hipMemcpyDeviceToHost));
-    double* dst[3] = {c->B.x, c->B.y, c->B.z};
-    if (field == MPH_FIELD_VELOCITY) { dst[0] = c->B.vx; dst[1] = c->B.vy; dst[2] = c->B.vz; }
+    MPH_HIP_OK(c, hipMemcpy(id.data(), c->L.B.id, sizeof(int) * n, hipMemcpyDeviceToHost));
+    double* dst[3] = {c->L.B.x, c->L.B.y, c->L.B.z};
+    if (field == MPH_FIELD_VELOCITY) { dst[0] = c->L.B.vx; dst[1] = c->L.B.vy; dst[2] = c->L.B.vz; }
     for (int k = 0; k < 3; ++k) {
         for (int i = 0; i < n; ++i) h[i] = id[i] >= 0 ? v[3 * (size_t)id[i] + k] : 0.0;
-        HIP_OK(c, hipMemcpy(dst[k], h.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        MPH_HIP_OK(c, hipMemcpy(dst[k], h.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     }
     return MPH_OK;
 }
@@ -969,13 +989,13 @@ int mph_set(MphCtx* c, int field, const void* in)
 int mph_set_initial_velocity_profile(MphCtx* c)
 {
     if (!c) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->n_glob;
     // slab mode: mph_get fills the owned entries and mph_set writes only those back
     std::vector<double> pos(3 * n, 0.0), vel(3 * n, 0.0);
-    CK(mph_get(c, MPH_FIELD_POSITION, pos.data()));
-    CK(mph_get(c, MPH_FIELD_VELOCITY, vel.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_POSITION, pos.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_VELOCITY, vel.data()));
     // the static inputs this context holds, with the current state of the same particles
     const int nin = (int)c->prop.size();
     std::vector<double> p(3 * (size_t)nin), v(3 * (size_t)nin);
@@ -984,7 +1004,7 @@ int mph_set_initial_velocity_profile(MphCtx* c)
             p[3 * (size_t)k + d] = pos[3 * (size_t)glob_id(c, k) + d];
             v[3 * (size_t)k + d] = vel[3 * (size_t)glob_id(c, k) + d];
         }
-    CK(mph_velocity_profile_arrays(&c->cfg, c->time, nin, c->prop.data(), p.data(), c->pos0.data(), v.data()));
+    MPH_CK(mph_velocity_profile_arrays(&c->cfg, c->time, nin, c->prop.data(), p.data(), c->pos0.data(), v.data()));
     for (int k = 0; k < nin; ++k)
         for (int d = 0; d < 3; ++d) vel[3 * (size_t)glob_id(c, k) + d] = v[3 * (size_t)k + d];
     return mph_set(c, MPH_FIELD_VELOCITY, vel.data());
@@ -996,30 +1016,42 @@ int mph_write_prof(MphCtx* c, const char* path)
     if (c->dist) return dist_write_output(c, path, kOutProf);   // collective; rank 0 writes
     const int n = c->n_glob;
     std::vector<double> pos(3 * (size_t)n), vel(3 * (size_t)n);
-    CK(mph_get(c, MPH_FIELD_POSITION, pos.data()));
-    CK(mph_get(c, MPH_FIELD_VELOCITY, vel.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_POSITION, pos.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_VELOCITY, vel.data()));
     return mph_write_prof_arrays(path, &c->cfg, c->time, n, c->prop.data(), pos.data(), c->pos0.data(),
                                  vel.data());
+}
+
+// the per-particle fields of a .vtk / .vtu file, in original order
+struct Snap {
+    std::vector<double> pos, vel, acc, force, stress, strain;
+    std::vector<int> isnc, nc;
+};
+
+static int snapshot(MphCtx* c, Snap& s)
+{
+    const size_t n = (size_t)c->n_glob;
+    for (auto* v : {&s.pos, &s.vel, &s.acc, &s.force}) v->resize(3 * n);
+    s.stress.resize(9 * n); s.strain.resize(9 * n); s.isnc.resize(n); s.nc.resize(n);
+    MPH_CK(mph_get(c, MPH_FIELD_POSITION, s.pos.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_VELOCITY, s.vel.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_ACCELERATION, s.acc.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_FORCE, s.force.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_STRESS, s.stress.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_STRAIN, s.strain.data()));
+    MPH_CK(mph_get(c, MPH_FIELD_INITIAL_STRUCTURE_NEIGHBOR_COUNT, s.isnc.data()));
+    return mph_get(c, MPH_FIELD_NEIGHBOR_COUNT, s.nc.data());
 }
 
 static int write_vtk_any(MphCtx* c, const char* path, bool xml)
 {
     if (!c || !path) return MPH_ERR_ARG;
     if (c->dist) return dist_write_output(c, path, xml ? kOutVtu : kOutVtk);   // collective; rank 0 writes
-    const size_t n = (size_t)c->n_glob;
-    std::vector<double> pos(3 * n), vel(3 * n), acc(3 * n), force(3 * n), stress(9 * n), strain(9 * n);
-    std::vector<int> isnc(n), nc(n);
-    CK(mph_get(c, MPH_FIELD_POSITION, pos.data()));
-    CK(mph_get(c, MPH_FIELD_VELOCITY, vel.data()));
-    CK(mph_get(c, MPH_FIELD_ACCELERATION, acc.data()));
-    CK(mph_get(c, MPH_FIELD_FORCE, force.data()));
-    CK(mph_get(c, MPH_FIELD_STRESS, stress.data()));
-    CK(mph_get(c, MPH_FIELD_STRAIN, strain.data()));
-    CK(mph_get(c, MPH_FIELD_INITIAL_STRUCTURE_NEIGHBOR_COUNT, isnc.data()));
-    CK(mph_get(c, MPH_FIELD_NEIGHBOR_COUNT, nc.data()));
+    Snap s;
+    MPH_CK(snapshot(c, s));
     auto writer = xml ? mph_write_vtu_arrays : mph_write_vtk_arrays;
-    return writer(path, c->n_glob, c->prop.data(), pos.data(), c->pos0.data(), vel.data(), acc.data(), force.data(),
-                  stress.data(), strain.data(), isnc.data(), nc.data());
+    return writer(path, c->n_glob, c->prop.data(), s.pos.data(), c->pos0.data(), s.vel.data(), s.acc.data(),
+                  s.force.data(), s.stress.data(), s.strain.data(), s.isnc.data(), s.nc.data());
 }
 
 int mph_write_vtk(MphCtx* c, const char* path) { return write_vtk_any(c, path, false); }
@@ -1032,40 +1064,22 @@ int mph_output_wait(MphCtx* c)
     if (c->out_thread.joinable()) c->out_thread.join();
     const int rc = c->out_rc;
     c->out_rc = MPH_OK;
-    if (rc) return fail(c, rc, "asynchronous .vtk write failed");
+    if (rc) return ctx_fail(c, rc, "asynchronous .vtk write failed");
     return MPH_OK;
 }
 
 int mph_write_vtk_async(MphCtx* c, const char* path)
 {
     if (!c || !path) return MPH_ERR_ARG;
-    CK(mph_output_wait(c));   // at most one file in flight
+    MPH_CK(mph_output_wait(c));   // at most one file in flight
     if (c->dist) return dist_write_output(c, path, kOutVtkAsync);   // collective; rank 0 formats and writes
-    struct Snap {
-        std::string path;
-        std::vector<double> pos, pos0, vel, acc, force, stress, strain;
-        std::vector<int> prop, isnc, nc;
-    };
-    const size_t n = (size_t)c->n_glob;
     auto s = std::make_shared<Snap>();
-    s->path = path;
-    s->pos.resize(3 * n); s->vel.resize(3 * n); s->acc.resize(3 * n); s->force.resize(3 * n);
-    s->stress.resize(9 * n); s->strain.resize(9 * n); s->isnc.resize(n); s->nc.resize(n);
-    s->pos0 = c->pos0;
-    s->prop = c->prop;
-    CK(mph_get(c, MPH_FIELD_POSITION, s->pos.data()));
-    CK(mph_get(c, MPH_FIELD_VELOCITY, s->vel.data()));
-    CK(mph_get(c, MPH_FIELD_ACCELERATION, s->acc.data()));
-    CK(mph_get(c, MPH_FIELD_FORCE, s->force.data()));
-    CK(mph_get(c, MPH_FIELD_STRESS, s->stress.data()));
-    CK(mph_get(c, MPH_FIELD_STRAIN, s->strain.data()));
-    CK(mph_get(c, MPH_FIELD_INITIAL_STRUCTURE_NEIGHBOR_COUNT, s->isnc.data()));
-    CK(mph_get(c, MPH_FIELD_NEIGHBOR_COUNT, s->nc.data()));
-    const int nn = c->n_glob;
-    c->out_thread = std::thread([c, s, nn] {
-        c->out_rc = mph_write_vtk_arrays(s->path.c_str(), nn, s->prop.data(), s->pos.data(), s->pos0.data(),
-                                         s->vel.data(), s->acc.data(), s->force.data(), s->stress.data(),
-                                         s->strain.data(), s->isnc.data(), s->nc.data());
+    MPH_CK(snapshot(c, *s));
+    // the thread owns copies of everything it reads
+    c->out_thread = std::thread([c, s, nn = c->n_glob, file = std::string(path), prop = c->prop, pos0 = c->pos0] {
+        c->out_rc = mph_write_vtk_arrays(file.c_str(), nn, prop.data(), s->pos.data(), pos0.data(), s->vel.data(),
+                                         s->acc.data(), s->force.data(), s->stress.data(), s->strain.data(),
+                                         s->isnc.data(), s->nc.data());
     });
     return MPH_OK;
 }
@@ -1073,18 +1087,18 @@ int mph_write_vtk_async(MphCtx* c, const char* path)
 int mph_phase_timing(MphCtx* c, int on)
 {
     if (!c) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    if (c->dist) return on ? fail(c, MPH_ERR_ARG, "phase timing is not available in slab mode") : MPH_OK;
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_CK(ctx_flush(c));
+    if (c->dist) return on ? ctx_fail(c, MPH_ERR_ARG, "phase timing is not available in slab mode") : MPH_OK;
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     const bool want = on != 0;
     if (want == c->phase_timing) return MPH_OK;
-    HIP_OK(c, hipStreamSynchronize(c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     c->phase_timing = want;   // (mph_step then launches directly; the graphs stay for later)
     if (want && c->ev_vir.empty()) {
         c->ev_vir.assign(2, nullptr);
-        for (auto& e : c->ev_vir) HIP_OK(c, hipEventCreate(&e));
+        for (auto& e : c->ev_vir) MPH_HIP_OK(c, hipEventCreate(&e));
         c->ev8.assign(3 * 8, nullptr);
-        for (auto& e : c->ev8) HIP_OK(c, hipEventCreate(&e));
+        for (auto& e : c->ev8) MPH_HIP_OK(c, hipEventCreate(&e));
     }
     return MPH_OK;
 }
@@ -1099,17 +1113,17 @@ int mph_phase_times(const MphCtx* c, double* out3)
 int mph_profile_steps(MphCtx* c, int nsteps, double* avg_ms, int* launches, char* names32)
 {
     if (!c || nsteps <= 0 || !avg_ms || !launches || !names32) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     EventProfiler prof;
     if (c->dist) {
-        CK(dist_step(c, nsteps, &prof));
+        MPH_CK(dist_step(c, nsteps, &prof));
     } else {
         Launch L = c->L;
         L.prof = &prof;
         for (int k = 0; k < nsteps; ++k) enqueue_step(L, k == nsteps - 1);
-        HIP_OK(c, hipGetLastError());
-        HIP_OK(c, hipStreamSynchronize(c->stream));
+        MPH_HIP_OK(c, hipGetLastError());
+        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
         for (int k = 0; k < nsteps; ++k) c->time += c->cfg.dt;
         c->stepped = true;
     }
@@ -1120,11 +1134,11 @@ int mph_profile_steps(MphCtx* c, int nsteps, double* avg_ms, int* launches, char
     std::vector<std::pair<float, float>> span;
     for (auto& r : prof.recs) {
         float ms = 0.0f, t0 = 0.0f;
-        HIP_OK(c, hipEventElapsedTime(&ms, r.a, r.b));
-        HIP_OK(c, hipEventElapsedTime(&t0, prof.recs[0].a, r.a));
+        MPH_HIP_OK(c, hipEventElapsedTime(&ms, r.a, r.b));
+        MPH_HIP_OK(c, hipEventElapsedTime(&t0, prof.recs[0].a, r.a));
         if (r.floor >= 0) {
             float tf = 0.0f;
-            HIP_OK(c, hipEventElapsedTime(&tf, prof.recs[0].a, prof.floors[r.floor]));
+            MPH_HIP_OK(c, hipEventElapsedTime(&tf, prof.recs[0].a, prof.floors[r.floor]));
             if (tf > t0) {
                 ms = std::max(0.0f, ms - (tf - t0));
                 t0 = tf;
@@ -1155,8 +1169,8 @@ int mph_profile_steps(MphCtx* c, int nsteps, double* avg_ms, int* launches, char
     std::snprintf(names32 + 32 * k, 32, "%s", "gpu_busy");
     ++k;
     DevState hs;
-    HIP_OK(c, hipMemcpy(&hs, c->dst, kStateHead, hipMemcpyDeviceToHost));
-    CK(ctx_state_status(c, hs));
+    MPH_HIP_OK(c, hipMemcpy(&hs, c->L.st, kStateHead, hipMemcpyDeviceToHost));
+    MPH_CK(ctx_state_status(c, hs));
     return k;
 }
 
@@ -1170,12 +1184,12 @@ int mph_profile_steps(MphCtx* c, int nsteps, double* avg_ms, int* launches, char
 int mph_profile_graphs(MphCtx* c, int reps, double* avg_ms3)
 {
     if (!c || reps <= 0 || reps > 64 || !avg_ms3) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
+    MPH_CK(ctx_flush(c));
     if (!c->stepped) return ctx_fail(c, MPH_ERR_ARG, "mph_profile_graphs: run a step first");
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_OK(c, hipEventCreate(&e0));
-    HIP_OK(c, hipEventCreate(&e1));
+    MPH_HIP_OK(c, hipEventCreate(&e0));
+    MPH_HIP_OK(c, hipEventCreate(&e1));
     int rc = MPH_OK;
     for (int k = 0; k < 3; ++k) avg_ms3[k] = -1.0;
     // pass B before pass A: in slab mode pass A zeroes the pressure of the ghosts' pass-B records,
@@ -1215,56 +1229,34 @@ int mph_profile_graphs(MphCtx* c, int reps, double* avg_ms3)
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    CK(rc);
-    HIP_OK(c, hipStreamSynchronize(c->stream));
+    MPH_CK(rc);
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     DevState hs;
-    HIP_OK(c, hipMemcpy(&hs, c->dst, kStateHead, hipMemcpyDeviceToHost));
+    MPH_HIP_OK(c, hipMemcpy(&hs, c->L.st, kStateHead, hipMemcpyDeviceToHost));
     return ctx_state_status(c, hs);
+}
+
+static void mean_max(const std::vector<int>& h, double* mean, int* mx)
+{
+    long long sum = 0;
+    *mx = 0;
+    for (int v : h) { sum += v; *mx = v > *mx ? v : *mx; }
+    *mean = h.empty() ? 0.0 : (double)sum / h.size();
 }
 
 int mph_neighbor_stats(MphCtx* c, double* mean, int* mx)
 {
     if (!c || !mean || !mx) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     // NeighborCount of the particles held here (slab mode: owned + ghosts), reduced on the host
     std::vector<int> h(c->n);
-    if (c->n) HIP_OK(c, hipMemcpy(h.data(), c->nbcount, sizeof(int) * c->n, hipMemcpyDeviceToHost));
-    long long sum = 0;
-    int m = 0;
-    for (int v : h) { sum += v; m = v > m ? v : m; }
-    *mean = c->n ? (double)sum / c->n : 0.0;
-    *mx = m;
+    if (c->n) MPH_HIP_OK(c, hipMemcpy(h.data(), c->L.nbcount, sizeof(int) * c->n, hipMemcpyDeviceToHost));
+    mean_max(h, mean, mx);
     return MPH_OK;
 }
 
-// The lists' rows as the last search left them (mph_kernels.hip RowMask): per particle (sorted
-// order) its rows [0, ncount) and, per wave, the row jumps -- gap k of lane s is the rows
-// [byte k of lgap[s], byte k of lhdr[s >> 6]) for k below the jump count in byte 7 of the header.
-struct HostRows {
-    std::vector<int> rows;
-    std::vector<unsigned long long> hdr, gap;
-    // whether row r of particle s holds one of its entries
-    bool ok(int s, int r) const
-    {
-        const unsigned long long h = hdr[s >> 6];
-        const int J = (int)(h >> 56);
-        for (int k = 0; k < J; ++k) {
-            const int a = (int)((gap[s] >> (8 * k)) & 0xff), b = (int)((h >> (8 * k)) & 0xff);
-            if (r >= a && r < b) return false;
-        }
-        return r < rows[s];
-    }
-    int entries(int s) const
-    {
-        const unsigned long long h = hdr[s >> 6];
-        const int J = (int)(h >> 56);
-        int e = std::min(rows[s], kTileRows);
-        for (int k = 0; k < J; ++k) e -= (int)((h >> (8 * k)) & 0xff) - (int)((gap[s] >> (8 * k)) & 0xff);
-        return e;
-    }
-};
-
+// the last search's rows and row jumps (mph_rows.h), copied from the device
 static int host_rows(MphCtx* c, HostRows& R)
 {
     const int n = c->n;
@@ -1273,42 +1265,38 @@ static int host_rows(MphCtx* c, HostRows& R)
     R.hdr.resize(ntile);
     R.gap.resize(ntile * kTile);
     if (!n) return MPH_OK;
-    HIP_OK(c, hipMemcpy(R.rows.data(), c->ncount, sizeof(int) * n, hipMemcpyDeviceToHost));
-    HIP_OK(c, hipMemcpy(R.hdr.data(), c->lhdr, sizeof(unsigned long long) * ntile, hipMemcpyDeviceToHost));
-    HIP_OK(c, hipMemcpy(R.gap.data(), c->lgap, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+    MPH_HIP_OK(c, hipMemcpy(R.rows.data(), c->L.ncount, sizeof(int) * n, hipMemcpyDeviceToHost));
+    MPH_HIP_OK(c, hipMemcpy(R.hdr.data(), c->L.lhdr, sizeof(R.hdr[0]) * ntile, hipMemcpyDeviceToHost));
+    MPH_HIP_OK(c, hipMemcpy(R.gap.data(), c->L.lgap, sizeof(R.gap[0]) * n, hipMemcpyDeviceToHost));
     return MPH_OK;
 }
 
 int mph_list_stats(MphCtx* c, double* mean, int* mx)
 {
     if (!c || !mean || !mx) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     HostRows R;   // stored list lengths (the rows outside the gaps), reduced on the host
-    CK(host_rows(c, R));
+    MPH_CK(host_rows(c, R));
     std::vector<int> h(c->n);
     for (int s = 0; s < c->n; ++s) h[s] = R.entries(s);
-    long long sum = 0;
-    int m = 0;
-    for (int v : h) { sum += v; m = v > m ? v : m; }
-    *mean = c->n ? (double)sum / c->n : 0.0;
-    *mx = m;
+    mean_max(h, mean, mx);
     return MPH_OK;
 }
 
 int mph_list_layout(MphCtx* c, long long out[6])
 {
     if (!c || !out) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    if (c->dist) return fail(c, MPH_ERR_UNSUPPORTED, "mph_list_layout: single contexts only");
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_CK(ctx_flush(c));
+    if (c->dist) return ctx_fail(c, MPH_ERR_UNSUPPORTED, "mph_list_layout: single contexts only");
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     HostRows R;   // the last search's rows and row jumps, reduced on the host
-    CK(host_rows(c, R));
+    MPH_CK(host_rows(c, R));
     const int n = c->n;
     const long long waves = ((long long)n + kTile - 1) / kTile;
     long long jumped = 0, jumps = 0, max_jumps = 0, gap_rows = 0, max_rows = 0;
     for (long long t = 0; t < waves; ++t) {
-        const int J = (int)(R.hdr[t] >> 56);
+        const int J = jump_count(R.hdr[t]);
         jumped += J > 0;
         jumps += J;
         max_jumps = std::max<long long>(max_jumps, J);
@@ -1325,33 +1313,33 @@ int mph_list_layout(MphCtx* c, long long out[6])
 int mph_neighbor_rows(MphCtx* c, int first, int count, int* counts, int* ids, long long ids_cap)
 {
     if (!c || first < 0 || count < 0 || !counts || (!ids && ids_cap > 0)) return MPH_ERR_ARG;
-    CK(ctx_flush(c));
-    if (c->dist) return fail(c, MPH_ERR_UNSUPPORTED, "mph_neighbor_rows: single contexts only");
-    if ((long long)first + count > c->n) return fail(c, MPH_ERR_ARG, "mph_neighbor_rows: range past the particle count");
+    MPH_CK(ctx_flush(c));
+    if (c->dist) return ctx_fail(c, MPH_ERR_UNSUPPORTED, "mph_neighbor_rows: single contexts only");
+    if ((long long)first + count > c->n) return ctx_fail(c, MPH_ERR_ARG, "mph_neighbor_rows: range past the particle count");
     if (!count) return 0;
-    HIP_OK(c, hipSetDevice(c->device));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
     const int n = c->n;
     if (c->P.rlf < 3.0e38f)
-        return fail(c, MPH_ERR_UNSUPPORTED, "mph_neighbor_rows: the lists keep only the pairs within the passes' "
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "mph_neighbor_rows: the lists keep only the pairs within the passes' "
                                             "radius (create the context with MPH_LIST_FULL=1 for the reference's lists)");
     // the last search's rows are in its sorted order A: A.id maps a row (and an entry) back to the
     // original index, ncount holds the list's length and nbcount NeighborCount in the same order
     std::vector<int> id(n), nv(n);
-    HIP_OK(c, hipMemcpy(id.data(), c->A.id, sizeof(int) * n, hipMemcpyDeviceToHost));
-    HIP_OK(c, hipMemcpy(nv.data(), c->nbcount, sizeof(int) * n, hipMemcpyDeviceToHost));
+    MPH_HIP_OK(c, hipMemcpy(id.data(), c->L.A.id, sizeof(int) * n, hipMemcpyDeviceToHost));
+    MPH_HIP_OK(c, hipMemcpy(nv.data(), c->L.nbcount, sizeof(int) * n, hipMemcpyDeviceToHost));
     HostRows R;
-    CK(host_rows(c, R));
+    MPH_CK(host_rows(c, R));
     const std::vector<int>& nc = R.rows;
     std::vector<int> row_of(count, -1);
     for (int s = 0; s < n; ++s)
         if (id[s] >= first && id[s] < first + count) row_of[id[s] - first] = s;
     long long total = 0;
     for (int k = 0; k < count; ++k) {
-        if (row_of[k] < 0) return fail(c, MPH_ERR_HIP, "mph_neighbor_rows: particle missing from the sorted set");
+        if (row_of[k] < 0) return ctx_fail(c, MPH_ERR_HIP, "mph_neighbor_rows: particle missing from the sorted set");
         counts[k] = nv[row_of[k]];
         total += std::min(counts[k], kMaxNeighbor);
     }
-    if (total > ids_cap) return fail(c, MPH_ERR_ARG, "mph_neighbor_rows: ids_cap too small (" + std::to_string(total) + " needed)");
+    if (total > ids_cap) return ctx_fail(c, MPH_ERR_ARG, "mph_neighbor_rows: ids_cap too small (" + std::to_string(total) + " needed)");
     // every ELL tile holding a requested row, down to the longest row of its lanes (entry k of lane l
     // at [k][l], 64 ints per entry: one contiguous copy per tile)
     std::map<int, std::vector<int>> tiles;
@@ -1362,7 +1350,7 @@ int mph_neighbor_rows(MphCtx* c, int first, int count, int* counts, int* ids, lo
         for (int s = t * kTile; s < std::min(n, (t + 1) * kTile); ++s) m = std::max(m, std::min(nc[s], kTileRows));
         std::vector<int>& buf = tiles[t];
         buf.resize((size_t)m * kTile);
-        if (m) HIP_OK(c, hipMemcpy(buf.data(), c->nbr + (size_t)t * kTileStride, sizeof(int) * buf.size(),
+        if (m) MPH_HIP_OK(c, hipMemcpy(buf.data(), c->L.nbr + (size_t)t * kTileStride, sizeof(int) * buf.size(),
                                    hipMemcpyDeviceToHost));
     }
     long long w = 0;
@@ -1374,10 +1362,10 @@ int mph_neighbor_rows(MphCtx* c, int first, int count, int* counts, int* ids, lo
             if (!R.ok(s, e)) continue;   // a gap of the row jumps
             const int v = buf[(size_t)ell_slot(e, s & 63)];
             const int j = v & kIndexMask;
-            if (j >= n || q >= m) return fail(c, MPH_ERR_HIP, "mph_neighbor_rows: list entry past the particle count");
+            if (j >= n || q >= m) return ctx_fail(c, MPH_ERR_HIP, "mph_neighbor_rows: list entry past the particle count");
             ids[w + q++] = id[j];
         }
-        if (q != m) return fail(c, MPH_ERR_HIP, "mph_neighbor_rows: list rows disagree with NeighborCount");
+        if (q != m) return ctx_fail(c, MPH_ERR_HIP, "mph_neighbor_rows: list rows disagree with NeighborCount");
         std::sort(ids + w, ids + w + m);
         w += m;
     }

@@ -314,7 +314,7 @@ int redistribute(MphCtx* c, bool move, bool init, Profiler* prof, bool early_in 
     // see early_send (no profiler floor: the second stream has moved on to the exchange since)
     if (early_in) MPH_HIP_OK(c, hipStreamWaitEvent(c->stream, D.ev_s, 0));
     launch_dist_classify(L, D.g, D.cap, D.lay, move ? 1 : 0, D.cls, D.bcnt, early_in ? D.wface : nullptr);
-    launch_scan(D.bcnt, kSlabClasses * nb, D.bsum, D.boff, 0, c->stream, prof);
+    launch_scan(D.bcnt, kSlabClasses * nb, D.bsum, D.boff, 0, nullptr, c->stream, prof);
     launch_dist_scatter(L, D.cap, D.lay, D.cls, D.boff, D.C, lay_field<int>(D.lay, offsetof(DistLayout, seg)),
                         D.virt ? D.vidx : nullptr);
     if (early_in) {
@@ -358,7 +358,7 @@ int early_send(MphCtx* c, Profiler* prof, hipStream_t stream)
     L.stream = stream;
     const int nb = dist_blocks(D.cap);
     launch_dist_early_classify(L, D.g, D.cap, D.lay, D.wface, D.cls, D.bcnt);
-    launch_scan(D.bcnt, kSlabClasses * nb, D.bsum, D.boff, 0, stream, prof);
+    launch_scan(D.bcnt, kSlabClasses * nb, D.bsum, D.boff, 0, nullptr, stream, prof);
     launch_dist_early_pack(L, D.cap, D.lay, D.cls, D.boff, D.cap_sl, D.cap_sr, D.send_l, D.send_r);
     // ev_s: the face waves' pass B and these kernels are done (the next step's partition, on the
     // main stream, waits for it before it reads B and wface); ev_x: the messages have landed
@@ -378,19 +378,19 @@ void sort_local(MphCtx* c, int mode, Profiler* prof)
     L.prof = prof;
     L.B = c->dist->C;
     L.vsrc = dist_vsrc(c);
-    L.dst_of = c->rank_of;
+    L.dst_of = c->order;
     launch_sort(L, mode);
 }
 
 HaloFields halo_fields(MphCtx* c)
 {
     HaloFields F{};
-    F.f[0] = c->pres;
+    F.f[0] = c->L.pres;
     F.nf = 1;
-    F.rec = c->rec;
+    F.rec = c->L.rec;
     F.rec_stride = c->P.n;   // the plane stride of the pass-B records (capacity)
     if (c->P.surface) {
-        F.f[1] = c->gx; F.f[2] = c->gy; F.f[3] = c->gz; F.f[4] = c->pa;
+        F.f[1] = c->L.gx; F.f[2] = c->L.gy; F.f[3] = c->L.gz; F.f[4] = c->L.pa;
         F.nf = 5;
     }
     return F;
@@ -410,10 +410,10 @@ int halo_exchange(MphCtx* c, Profiler* prof, hipStream_t stream, const HaloField
     double* sr = (double*)D.send_r;
     double* rl = (double*)D.recv_l;
     double* rr = (double*)D.recv_r;
-    launch_halo_pack(L, c->rank_of, D.lay, capl, capr, F, sl, sr);
+    launch_halo_pack(L, c->order, D.lay, capl, capr, F, sl, sr);
     const size_t b = sizeof(double) * F.nf;
     MPH_CK(exchange(c, stream, sl, b * capl, sr, b * capr, rl, b * capl, rr, b * capr));
-    launch_halo_unpack(L, rl, rr, c->rank_of, D.lay, capl, capr, F);
+    launch_halo_unpack(L, rl, rr, c->order, D.lay, capl, capr, F);
     return MPH_OK;
 }
 
@@ -771,7 +771,7 @@ int dist_sync(MphCtx* c, bool grow_ok)
 {
     MphDist& D = *c->dist;
     DevState hs;
-    MPH_HIP_OK(c, hipMemcpyAsync(&hs, c->dst, kStateHead, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipMemcpyAsync(&hs, c->L.st, kStateHead, hipMemcpyDeviceToHost, c->stream));
     MPH_HIP_OK(c, hipMemcpyAsync(D.hlay, D.lay, sizeof(DistLayout), hipMemcpyDeviceToHost, c->stream));
     MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     if (hs.overflow & 8)
@@ -815,7 +815,7 @@ int dist_init(MphCtx* c)
     // MPH_SLAB_MSG_CAP0_FRAC, is meant to grow at the first check after real steps)
     MPH_CK(dist_sync(c, false));
     // the integrated-state set B starts as the sorted local set (owned + ghosts, ids signed)
-    MPH_CK(copy_soa(c, c->B, c->A, c->n));
+    MPH_CK(copy_soa(c, c->L.B, c->L.A, c->n));
     MPH_HIP_OK(c, hipGetLastError());
     MPH_CK(dist_sync(c, false));
     MPH_CK(overlap_probe(c));   // MPH_SLAB_OVERLAP auto: the pass-B mode, the same on every rank
@@ -1031,14 +1031,6 @@ struct OutSlot {
     double S[9], E[9];
 };
 
-template <typename T>
-int fetch(MphCtx* c, const T* d, std::vector<T>& h, size_t count)
-{
-    h.resize(count);
-    if (count) MPH_HIP_OK(c, hipMemcpyAsync(h.data(), d, sizeof(T) * count, hipMemcpyDeviceToHost, c->stream));
-    return MPH_OK;
-}
-
 // the records of the particles (and elastic slots) this rank owns, behind two counts
 int pack_owned(MphCtx* c, std::vector<char>& buf)
 {
@@ -1046,16 +1038,16 @@ int pack_owned(MphCtx* c, std::vector<char>& buf)
     std::vector<int> id, nc;
     std::vector<double> x, y, z, vx, vy, vz;
     std::vector<double4> f, a;
-    MPH_CK(fetch(c, (const int*)c->A.id, id, n));
-    MPH_CK(fetch(c, (const int*)c->nbcount, nc, n));
-    MPH_CK(fetch(c, (const double*)c->B.x, x, n));
-    MPH_CK(fetch(c, (const double*)c->B.y, y, n));
-    MPH_CK(fetch(c, (const double*)c->B.z, z, n));
-    MPH_CK(fetch(c, (const double*)c->B.vx, vx, n));
-    MPH_CK(fetch(c, (const double*)c->B.vy, vy, n));
-    MPH_CK(fetch(c, (const double*)c->B.vz, vz, n));
-    MPH_CK(fetch(c, (const double4*)c->force, f, n));
-    MPH_CK(fetch(c, (const double4*)c->acc, a, n));
+    MPH_CK(fetch(c, (const int*)c->L.A.id, id, n));
+    MPH_CK(fetch(c, (const int*)c->L.nbcount, nc, n));
+    MPH_CK(fetch(c, (const double*)c->L.B.x, x, n));
+    MPH_CK(fetch(c, (const double*)c->L.B.y, y, n));
+    MPH_CK(fetch(c, (const double*)c->L.B.z, z, n));
+    MPH_CK(fetch(c, (const double*)c->L.B.vx, vx, n));
+    MPH_CK(fetch(c, (const double*)c->L.B.vy, vy, n));
+    MPH_CK(fetch(c, (const double*)c->L.B.vz, vz, n));
+    MPH_CK(fetch(c, (const double4*)c->L.force, f, n));
+    MPH_CK(fetch(c, (const double4*)c->L.acc, a, n));
     const int ns = c->Sd.n_own;
     std::vector<double> S, E;
     const size_t fes = (size_t)c->Sd.fes;   // nine element planes (StructDev)
@@ -1203,12 +1195,12 @@ int dist_virial(MphCtx* c)
 {
     HaloFields F{};
     F.nf = 3;
-    F.f[0] = c->B.x; F.f[1] = c->B.y; F.f[2] = c->B.z;
+    F.f[0] = c->L.B.x; F.f[1] = c->L.B.y; F.f[2] = c->L.B.z;
     MPH_CK(halo_exchange(c, nullptr, c->stream, &F));
-    F.f[0] = c->B.vx; F.f[1] = c->B.vy; F.f[2] = c->B.vz;
+    F.f[0] = c->L.B.vx; F.f[1] = c->L.B.vy; F.f[2] = c->L.B.vz;
     MPH_CK(halo_exchange(c, nullptr, c->stream, &F));
     MPH_CK(virial_full_lists(c));
-    launch_virial(c->L, c->B, c->vir, c->vpres);
+    launch_virial(c->L, c->L.B, c->vir, c->vpres);
     MPH_HIP_OK(c, hipGetLastError());
     MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     return MPH_OK;
@@ -1456,7 +1448,7 @@ int mph_owned_ids(MphCtx* c, int* out)
     }
     MPH_HIP_OK(c, hipSetDevice(c->device));
     std::vector<int> id(c->n);
-    MPH_HIP_OK(c, hipMemcpyAsync(id.data(), c->B.id, sizeof(int) * c->n, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipMemcpyAsync(id.data(), c->L.B.id, sizeof(int) * c->n, hipMemcpyDeviceToHost, c->stream));
     MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     int k = 0;
     for (int i = 0; i < c->n; ++i)

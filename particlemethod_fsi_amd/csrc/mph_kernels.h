@@ -96,8 +96,7 @@ struct Launch {
     Profiler* prof = nullptr;
     // B set: integrated state in the previous order; A set: cell-sorted current order
     Soa A, B;
-    int* rank_of = nullptr;
-    int* dst_of = nullptr;        // slab mode: pre-sort index -> sorted index (else rank_of[id])
+    int* dst_of = nullptr;        // slab mode: pre-sort index -> sorted index
     int *key = nullptr, *slot = nullptr, *tmp = nullptr, *cnt = nullptr, *start = nullptr, *bsum = nullptr;
     // ncount: each list's rows (what the passes walk); nbcount: NeighborCount (every neighbour within
     // the search radius; the lists keep only r^2 <= DevParams.rlf)
@@ -150,7 +149,9 @@ struct HaloFields {
     double4* rec;   // f[0] (PressureP) is also the P of the pass-B record (its plane stride rec_stride)
     int rec_stride;
 };
-void launch_scan(int* cnt, int ncell, int* bsum, int* start, int total, hipStream_t stream, Profiler* prof);
+// exclusive scan of cnt[ncell] into start (start[ncell] = total, or *n_dev when non-null); re-zeroes cnt
+void launch_scan(int* cnt, int ncell, int* bsum, int* start, int total, const int* n_dev, hipStream_t stream,
+                 Profiler* prof);
 int dist_blocks(int n);
 // slab redistribution; every size is read from the device layout (graph-capturable).  cap = local
 // array capacity, cap_msg = capacity (particles) of the message of that side.

@@ -423,11 +423,11 @@ __device__ __forceinline__ RowMask row_mask(unsigned long long hdr, const unsign
     RowMask m;
     m.lo = ~bits_from(end);
     m.hi = ~bits_from(end - 64);
-    const int J = (int)(hdr >> 56);
+    const int J = jump_count(hdr);
     if (J) {   // wave-uniform
         const unsigned long long g = lgap[i];
         for (int k = 0; k < J; ++k) {
-            const int a = (int)((g >> (8 * k)) & 0xff), b = (int)((hdr >> (8 * k)) & 0xff);
+            const int a = gap_begin(g, k), b = gap_end(hdr, k);
             m.lo &= ~(bits_from(a) & ~bits_from(b));
             m.hi &= ~(bits_from(a - 64) & ~bits_from(b - 64));
         }
@@ -1122,7 +1122,7 @@ __device__ __forceinline__ bool accept_band(const DevParams& P, double dx, doubl
     return r2_exact(q0, q1, q2) <= P.rc2;
 }
 
-template <int DIM, bool FAST, int PERM, int SB = MPH_SB>
+template <int DIM, int PERM, int SB = MPH_SB>
 __device__ __forceinline__ int scan_candidates(const DevParams& P, const Soa& A, const int* start,
                                                int i, double xi, double yi, double zi, int cx,
                                                int cy, int cz, int* out)
@@ -1141,7 +1141,6 @@ __device__ __forceinline__ int scan_candidates(const DevParams& P, const Soa& A,
     const double uu[3] = {grid_offset(xi, P.corg[0], P.dw[0]), grid_offset(yi, P.corg[1], P.dw[1]),
                           DIM == 3 ? grid_offset(zi, P.corg[2], P.dw[2]) : 0.0};
     const double ua = uu[X::A2];                      // offset along the contiguous axis
-    const double lo2 = P.rc2_lo, hi2 = P.rc2_hi;
     const double ginva = P.ginv[X::A2];
     for (int col = 0; col < NCOL; ++col) {
         int base;
@@ -1152,22 +1151,21 @@ __device__ __forceinline__ int scan_candidates(const DevParams& P, const Soa& A,
             const double gx = cell_gap(uu[X::A0], c0, dxc, cw0), gy = cell_gap(uu[X::A1], c1, dyc, cw1);
             d2 = gx * gx + gy * gy;
             if (d2 > rcm2) continue;
-            const int jx = FAST ? c0 + dxc : wrap_cell(c0 + dxc, P.gc[X::A0]);
-            const int jy = FAST ? c1 + dyc : wrap_cell(c1 + dyc, P.gc[X::A1]);
+            const int jx = wrap_cell(c0 + dxc, P.gc[X::A0]);
+            const int jy = wrap_cell(c1 + dyc, P.gc[X::A1]);
             base = (jx * P.gc[X::A1] + jy) * P.gc[X::A2];
         } else {
             const int dxc = col - kReach;
             const double gx = cell_gap(uu[0], cx, dxc, cw0);
             d2 = gx * gx;
             if (d2 > rcm2) continue;
-            base = (FAST ? cx + dxc : wrap_cell(cx + dxc, P.gc[0])) * P.gc[1];
+            base = wrap_cell(cx + dxc, P.gc[0]) * P.gc[1];
         }
         const double ra = sqrt(rcm2 - d2);
         const int lo = (int)fmax(floor((ua - ra) * ginva), (double)(cca - P.sa));
         const int hi = (int)fmin(floor((ua + ra) * ginva), (double)(cca + P.sa));
         int seg_a[2], seg_b[2], nseg;
-        if (FAST) { seg_a[0] = lo; seg_b[0] = hi; seg_a[1] = 0; seg_b[1] = -1; nseg = 1; }
-        else if (lo < 0) { seg_a[0] = lo + gca; seg_b[0] = gca - 1; seg_a[1] = 0; seg_b[1] = hi; nseg = 2; }
+        if (lo < 0) { seg_a[0] = lo + gca; seg_b[0] = gca - 1; seg_a[1] = 0; seg_b[1] = hi; nseg = 2; }
         else if (hi >= gca) { seg_a[0] = lo; seg_b[0] = gca - 1; seg_a[1] = 0; seg_b[1] = hi - gca; nseg = 2; }
         else { seg_a[0] = lo; seg_b[0] = hi; seg_a[1] = 0; seg_b[1] = -1; nseg = 1; }
         for (int sg = 0; sg < nseg; ++sg) {
@@ -1189,15 +1187,10 @@ __device__ __forceinline__ int scan_candidates(const DevParams& P, const Soa& A,
 #pragma unroll
                 for (int u = 0; u < SB; ++u) {
                     const int j = j0 + u;
-                    bool a;
-                    if (FAST) {
-                        a = accept_interior(P, xs[u] - xi, ys[u] - yi, zs[u] - zi, lo2, hi2);
-                    } else {
-                        const double q0 = image_exact<false>(xs[u] - xi, P.dw[0], P.hw[0], P.w075[0]);
-                        const double q1 = image_exact<false>(ys[u] - yi, P.dw[1], P.hw[1], P.w075[1]);
-                        const double q2 = image_exact<DIM == 2>(zs[u] - zi, P.dw[2], P.hw[2], P.w075[2]);
-                        a = r2_exact(q0, q1, q2) <= P.rc2;
-                    }
+                    const double q0 = image_exact<false>(xs[u] - xi, P.dw[0], P.hw[0], P.w075[0]);
+                    const double q1 = image_exact<false>(ys[u] - yi, P.dw[1], P.hw[1], P.w075[1]);
+                    const double q2 = image_exact<DIM == 2>(zs[u] - zi, P.dw[2], P.hw[2], P.w075[2]);
+                    const bool a = r2_exact(q0, q1, q2) <= P.rc2;
                     if (a && j < je && j != i) {
                         if (cnt < kMaxNeighbor) out[ell_slot(cnt, 0)] = nbr_entry(j, A.type[j]);
                         ++cnt;
@@ -1600,7 +1593,7 @@ __device__ __forceinline__ int neighbors_body(const DevParams& P, const Soa& A, 
                                              lgap, lhdr);
     } else {
         if (own)
-            cnt = scan_candidates<DIM, false, PERM>(P, A, start, i, xi, yi, zi, cx, cy, cz, out);
+            cnt = scan_candidates<DIM, PERM>(P, A, start, i, xi, yi, zi, cx, cy, cz, out);
         stored = cnt;
         if ((threadIdx.x & 63) == 0) lhdr[tile] = 0;   // plain rows
     }
@@ -2930,47 +2923,66 @@ static inline int list_grid(int n)
     return (nb + nb / 4 + 15) / 8 * 8;
 }
 
-// A profiled launch (mph_profile_steps): its start/stop events come from the kernel's dispatch
-// packet (hipExtLaunchKernelGGL), or are recorded around it (Profiler::events).  Direct launches
-// run ~9 us apart and start with a written-back L2, so they take 3-8 % longer than the same
-// kernels replayed from a graph (profiles/r05/final/prof: rocprofv3 trace); mph_profile_graphs
-// times the list kernels as graph replays.
-#define MPH_LAUNCH(name, stream, kernel, grid, block, shm, strm, ...)                          \
-    do {                                                                                       \
-        if (prof) {                                                                            \
-            hipEvent_t _a, _b;                                                                 \
-            if (prof->events(name, stream, &_a, &_b)) {                                        \
-                hipExtLaunchKernelGGL(kernel, grid, block, shm, strm, _a, _b, 0u, __VA_ARGS__); \
-            } else {                                                                           \
-                (void)hipEventRecord(_a, strm);                                                \
-                hipLaunchKernelGGL(kernel, grid, block, shm, strm, __VA_ARGS__);               \
-                (void)hipEventRecord(_b, strm);                                                \
-            }                                                                                  \
-        } else {                                                                               \
-            hipLaunchKernelGGL(kernel, grid, block, shm, strm, __VA_ARGS__);                   \
-        }                                                                                      \
-    } while (0)
+// (non-deduced: launch's arguments convert to the kernel's own parameter types, as in a call)
+template <typename T> struct Same { using type = T; };
+
+// One launch, profiled when prof is set (mph_profile_steps): its start/stop events come from the
+// kernel's dispatch packet (hipExtLaunchKernelGGL), or are recorded around it (Profiler::events).
+// Direct launches run ~9 us apart and start with a written-back L2, so they take 3-8 % longer than
+// the same kernels replayed from a graph (profiles/r05/final/prof: rocprofv3 trace);
+// mph_profile_graphs times the list kernels as graph replays.
+template <typename... A>
+static void launch(Profiler* prof, const char* name, hipStream_t stream, void (*kernel)(A...), dim3 grid, dim3 block,
+                   typename Same<A>::type... args)
+{
+    if (!prof) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
+        return;
+    }
+    hipEvent_t a, b;
+    if (prof->events(name, stream, &a, &b)) {
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, a, b, 0u, args...);
+    } else {
+        (void)hipEventRecord(a, stream);
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
+        (void)hipEventRecord(b, stream);
+    }
+}
+
+// f(Int<2>{}) or f(Int<3>{}): the kernels are instantiated per dimension
+template <int N> using Int = std::integral_constant<int, N>;
+
+template <typename F>
+static void by_dim(int dim, F&& f)
+{
+    if (dim == 3) f(Int<3>{});
+    else f(Int<2>{});
+}
+
+void launch_scan(int* cnt, int ncell, int* bsum, int* start, int total, const int* n_dev, hipStream_t stream,
+                 Profiler* prof)
+{
+    const int nb = blocks(ncell, kScanBlock);
+    const int top = nb <= kScanFusedTop;
+    launch(prof, "scan_reduce", stream, k_scan_reduce, dim3(nb), dim3(kScanThreads), cnt, ncell, bsum);
+    if (!top) launch(prof, "scan_top", stream, k_scan_top, dim3(1), dim3(1024), bsum, nb);
+    launch(prof, "scan_down", stream, k_scan_down, dim3(nb), dim3(kScanThreads), cnt, ncell, bsum, start, total,
+           n_dev, top);
+}
 
 void launch_sort(const Launch& L, int mode)
 {
-    Profiler* prof = L.prof;
     const DevParams& P = *L.P;
     const int n = P.n;
     if (n == 0) return;
-    const int nb = blocks(P.ncell, kScanBlock);
-    const int top = nb <= kScanFusedTop;
     const int split = n >= L.xcd_bal_min;   // the passes' XCD split (list_grid, k_rank_scatter)
-    MPH_LAUNCH("prep", L.stream, k_prep, dim3(blocks(n, 256)), dim3(256), 0, L.stream, P, L.st, L.B, L.key,
-               L.slot, L.cnt, mode, L.vsrc);
-    MPH_LAUNCH("scan_reduce", L.stream, k_scan_reduce, dim3(nb), dim3(kScanThreads), 0, L.stream, L.cnt, P.ncell,
-               L.bsum);
-    if (!top) MPH_LAUNCH("scan_top", L.stream, k_scan_top, dim3(1), dim3(1024), 0, L.stream, L.bsum, nb);
-    MPH_LAUNCH("scan_down", L.stream, k_scan_down, dim3(nb), dim3(kScanThreads), 0, L.stream, L.cnt, P.ncell,
-               L.bsum, L.start, n, P.n_dev, top);
-    MPH_LAUNCH("place", L.stream, k_place, dim3(blocks(n, 256)), dim3(256), 0, L.stream, P, L.st, L.key,
-               L.slot, L.start, L.tmp, mode);
-    MPH_LAUNCH("rank_scatter", L.stream, k_rank_scatter, dim3(blocks(n, 256)), dim3(256), 0, L.stream, P,
-               L.key, L.start, L.tmp, L.B, L.A, L.rank_of, L.dst_of, mode, L.vsrc, L.st, split);
+    const dim3 g(blocks(n, 256)), b(256);
+    launch(L.prof, "prep", L.stream, k_prep, g, b, P, L.st, L.B, L.key, L.slot, L.cnt, mode, L.vsrc);
+    launch_scan(L.cnt, P.ncell, L.bsum, L.start, n, P.n_dev, L.stream, L.prof);
+    launch(L.prof, "place", L.stream, k_place, g, b, P, L.st, L.key, L.slot, L.start, L.tmp, mode);
+    launch(L.prof, "rank_scatter", L.stream, k_rank_scatter, g, b, P, L.key, L.start, L.tmp, L.B, L.A,
+           nullptr /* rank_of: no reader (fields return through A.id, slab mode uses dst_of) */, L.dst_of, mode,
+           L.vsrc, L.st, split);
 }
 
 static PassAOut pass_a_out(const Launch& L)
@@ -2980,39 +2992,37 @@ static PassAOut pass_a_out(const Launch& L)
 
 void launch_neighbors(const Launch& L)
 {
-    Profiler* prof = L.prof;
     const DevParams& P = *L.P;
     if (P.n == 0) return;
     const int bal = P.n >= L.xcd_bal_min;
-#define MPH_NEIGHBORS(D, PERM)                                                                             \
-    MPH_LAUNCH("neighbors", L.stream, (k_neighbors<D, PERM>), dim3(blocks(P.n, MPH_LB)), dim3(MPH_LB), 0, \
-               L.stream, P, L.A, L.start, L.nbr, L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, bal)
-    if (P.dim == 3) {
-        switch (P.perm) {
-        case 1: MPH_NEIGHBORS(3, 1); break;
-        case 2: MPH_NEIGHBORS(3, 2); break;
-        case 3: MPH_NEIGHBORS(3, 3); break;
-        case 4: MPH_NEIGHBORS(3, 4); break;
-        default: MPH_NEIGHBORS(3, 0); break;
+    by_dim(P.dim, [&](auto D) {
+        constexpr int DIM = decltype(D)::value;
+        auto go = [&](auto PERM) {
+            launch(L.prof, "neighbors", L.stream, k_neighbors<DIM, decltype(PERM)::value>, dim3(blocks(P.n, MPH_LB)),
+                   dim3(MPH_LB), P, L.A, L.start, L.nbr, L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, bal);
+        };
+        if constexpr (DIM == 3) {   // (the 2-D grid has the one cell order)
+            switch (P.perm) {
+            case 1: go(Int<1>{}); break;
+            case 2: go(Int<2>{}); break;
+            case 3: go(Int<3>{}); break;
+            case 4: go(Int<4>{}); break;
+            default: go(Int<0>{}); break;
+            }
+        } else {
+            go(Int<0>{});
         }
-    } else {
-        MPH_NEIGHBORS(2, 0);
-    }
-#undef MPH_NEIGHBORS
+    });
 }
 
 void launch_pass_a(const Launch& L)
 {
-    Profiler* prof = L.prof;
     const DevParams& P = *L.P;
     if (P.n == 0) return;
-    const PassAOut po = pass_a_out(L);
-    if (P.dim == 3)
-        MPH_LAUNCH("pass_a", L.stream, k_pass_a<3>, dim3(list_grid(P.n)), dim3(MPH_LB), 0, L.stream, P, L.T, L.A,
-                   L.nbr, L.ncount, L.lhdr, L.lgap, po, L.st);
-    else
-        MPH_LAUNCH("pass_a", L.stream, k_pass_a<2>, dim3(list_grid(P.n)), dim3(MPH_LB), 0, L.stream, P, L.T, L.A,
-                   L.nbr, L.ncount, L.lhdr, L.lgap, po, L.st);
+    by_dim(P.dim, [&](auto D) {
+        launch(L.prof, "pass_a", L.stream, k_pass_a<decltype(D)::value>, dim3(list_grid(P.n)), dim3(MPH_LB), P, L.T,
+               L.A, L.nbr, L.ncount, L.lhdr, L.lgap, pass_a_out(L), L.st);
+    });
 }
 
 // calculateNeighbor + the pass-A sums
@@ -3038,7 +3048,6 @@ static StructHook struct_hook(const Launch& L)
 
 void launch_pass_b(const Launch& L, int phase)
 {
-    Profiler* prof = L.prof;
     const DevParams& P = *L.P;
     if (P.n == 0) return;
     // pass B reads GravityCenter and PressureA of every neighbour with surface tension; enqueue_step
@@ -3047,30 +3056,26 @@ void launch_pass_b(const Launch& L, int phase)
         std::fprintf(stderr, "mph: launch_pass_b with surface tension needs GravityCenter/PressureA\n");
         std::abort();
     }
-#define MPH_PASS_B(S, D)                                                                            \
-    MPH_LAUNCH(phase == 2 ? "pass_b_face" : "pass_b", L.stream, (k_pass_b<S, D>), dim3(list_grid(P.n)), dim3(MPH_LB), 0, L.stream, P, \
-               L.T, L.A, L.rec, L.fpart, L.gx, L.gy, L.gz, L.pa, L.nbr, L.ncount, L.lhdr, L.lgap, L.force, L.acc, L.B, \
-               phase, L.wface, \
-               struct_hook(L), L.st)
-    if (P.surface) {
-        if (P.dim == 3) MPH_PASS_B(true, 3); else MPH_PASS_B(true, 2);
-    } else {
-        if (P.dim == 3) MPH_PASS_B(false, 3); else MPH_PASS_B(false, 2);
-    }
-#undef MPH_PASS_B
+    auto go = [&](auto SURF) {
+        by_dim(P.dim, [&](auto D) {
+            launch(L.prof, phase == 2 ? "pass_b_face" : "pass_b", L.stream,
+                   k_pass_b<decltype(SURF)::value, decltype(D)::value>, dim3(list_grid(P.n)), dim3(MPH_LB), P, L.T, L.A,
+                   L.rec, L.fpart, L.gx, L.gy, L.gz, L.pa, L.nbr, L.ncount, L.lhdr, L.lgap, L.force, L.acc, L.B, phase,
+                   L.wface, struct_hook(L), L.st);
+        });
+    };
+    if (P.surface) go(std::true_type{});
+    else go(std::false_type{});
 }
 
 void launch_virial(const Launch& L, const Soa& X, double* vir, double* vpres)
 {
-    Profiler* prof = L.prof;
     const DevParams& P = *L.P;
     if (P.n == 0) return;
-    if (P.dim == 3)
-        MPH_LAUNCH("virial", L.stream, k_virial<3>, dim3(blocks(P.n, 256)), dim3(256), 0, L.stream, P, L.T, L.A, X,
-                   L.pres, L.pa, L.gx, L.gy, L.gz, L.nbr, L.ncount, L.lhdr, L.lgap, vir, vpres);
-    else
-        MPH_LAUNCH("virial", L.stream, k_virial<2>, dim3(blocks(P.n, 256)), dim3(256), 0, L.stream, P, L.T, L.A, X,
-                   L.pres, L.pa, L.gx, L.gy, L.gz, L.nbr, L.ncount, L.lhdr, L.lgap, vir, vpres);
+    by_dim(P.dim, [&](auto D) {
+        launch(L.prof, "virial", L.stream, k_virial<decltype(D)::value>, dim3(blocks(P.n, 256)), dim3(256), P, L.T,
+               L.A, X, L.pres, L.pa, L.gx, L.gy, L.gz, L.nbr, L.ncount, L.lhdr, L.lgap, vir, vpres);
+    });
 }
 
 // lanes per structure slot: one lane per slot while the launch has >= kStructLanesTarget lanes
@@ -3091,52 +3096,46 @@ int struct_lanes(int nslots)
     return g;
 }
 
-#define MPH_STRUCT_G(G, D, KERNEL, NAME, ...)                                                     \
-    MPH_LAUNCH(NAME, L.stream, (KERNEL<D, G>), dim3(blocks((s1 - s0) * G, 256)), dim3(256), 0,   \
-               L.stream, __VA_ARGS__)
-#define MPH_STRUCT_DISPATCH(KERNEL, NAME, ...)                                                    \
-    do {                                                                                          \
-        const int lanes = struct_lanes(S.n_own);   /* not the range: the halves sum alike */     \
-        if (P.dim == 3) {                                                                         \
-            switch (lanes) {                                                                      \
-            case 8: MPH_STRUCT_G(8, 3, KERNEL, NAME, __VA_ARGS__); break;                         \
-            case 4: MPH_STRUCT_G(4, 3, KERNEL, NAME, __VA_ARGS__); break;                         \
-            case 2: MPH_STRUCT_G(2, 3, KERNEL, NAME, __VA_ARGS__); break;                         \
-            default: MPH_STRUCT_G(1, 3, KERNEL, NAME, __VA_ARGS__); break;                        \
-            }                                                                                     \
-        } else {                                                                                  \
-            switch (lanes) {                                                                      \
-            case 8: MPH_STRUCT_G(8, 2, KERNEL, NAME, __VA_ARGS__); break;                         \
-            case 4: MPH_STRUCT_G(4, 2, KERNEL, NAME, __VA_ARGS__); break;                         \
-            case 2: MPH_STRUCT_G(2, 2, KERNEL, NAME, __VA_ARGS__); break;                         \
-            default: MPH_STRUCT_G(1, 2, KERNEL, NAME, __VA_ARGS__); break;                        \
-            }                                                                                     \
-        }                                                                                         \
-    } while (0)
+// f(Int<dim>{}, Int<lanes per slot>{}) of a structure kernel over the slots [s0, s1): its grid
+template <typename F>
+static void by_dim_lanes(const Launch& L, F&& f)
+{
+    const int lanes = struct_lanes(L.S->n_own);   // not the range: the halves sum alike
+    by_dim(L.P->dim, [&](auto D) {
+        switch (lanes) {
+        case 8: f(D, Int<8>{}); break;
+        case 4: f(D, Int<4>{}); break;
+        case 2: f(D, Int<2>{}); break;
+        default: f(D, Int<1>{}); break;
+        }
+    });
+}
 
 void launch_struct_stress(const Launch& L, bool store, int s0, int s1)
 {
-    Profiler* prof = L.prof;
     const DevParams& P = *L.P;
     const StructDev& S = *L.S;
     if (s1 < 0) s1 = S.n_own;
     if (s1 <= s0) return;
-    MPH_STRUCT_DISPATCH(k_struct_stress, "struct_stress", P, s0, s1, S.wo, S.ocnt, S.eo_nb, S.x0, S.u, S.L,
-                        S.lame, S.P, S.F, S.E, S.S, S.fes, store ? 1 : 0);
+    by_dim_lanes(L, [&](auto D, auto G) {
+        launch(L.prof, "struct_stress", L.stream, k_struct_stress<decltype(D)::value, decltype(G)::value>,
+               dim3(blocks((s1 - s0) * G(), 256)), dim3(256), P, s0, s1, S.wo, S.ocnt, S.eo_nb, S.x0, S.u, S.L, S.lame,
+               S.P, S.F, S.E, S.S, S.fes, store ? 1 : 0);
+    });
 }
 
 void launch_struct_velocity(const Launch& L, bool last, int s0, int s1)
 {
-    Profiler* prof = L.prof;
     const DevParams& P = *L.P;
     const StructDev& S = *L.S;
     if (s1 < 0) s1 = S.n_own;
     if (s1 <= s0) return;
-    MPH_STRUCT_DISPATCH(k_struct_velocity, "struct_velocity", P, s0, s1, S.wi, S.icnt, S.ei_nb, S.wx0, S.P,
-                        S.inv_rho, S.clamp, S.x0, S.x, S.v, S.u, last ? 1 : 0, S.bidx, L.B, L.force);
+    by_dim_lanes(L, [&](auto D, auto G) {
+        launch(L.prof, "struct_velocity", L.stream, k_struct_velocity<decltype(D)::value, decltype(G)::value>,
+               dim3(blocks((s1 - s0) * G(), 256)), dim3(256), P, s0, s1, S.wi, S.icnt, S.ei_nb, S.wx0, S.P, S.inv_rho,
+               S.clamp, S.x0, S.x, S.v, S.u, last ? 1 : 0, S.bidx, L.B, L.force);
+    });
 }
-#undef MPH_STRUCT_DISPATCH
-#undef MPH_STRUCT_G
 
 void launch_structure(const Launch& L, bool last)
 {
@@ -3156,17 +3155,19 @@ int launch_struct_init(const Launch& L, int ns, const double4* x0, int* key, int
     const DevParams& P = *L.P;
     if (ns <= 0) return 0;
     const dim3 g(blocks(ns, 256)), b(256);
+    // the rows of every slot: counted (ell null), then stored
+    auto search = [&](int* ell, int w, int store) {
+        by_dim(P.dim, [&](auto D) {
+            launch(prof, "sinit_search", L.stream, k_sinit_search<decltype(D)::value>, g, b, P, ns, x0, L.start,
+                   sorted, ocnt, ell, w, store, L.st);
+        });
+    };
     // bin the slots on the grid (L.cnt is zero between steps and the scan re-zeroes it)
-    MPH_LAUNCH("sinit_bin", L.stream, k_sinit_bin, g, b, 0, L.stream, P, ns, x0, key, L.cnt, slot);
-    launch_scan(L.cnt, P.ncell, L.bsum, L.start, ns, L.stream, prof);
-    MPH_LAUNCH("sinit_place", L.stream, k_sinit_place, g, b, 0, L.stream, ns, key, slot, L.start, tmp, sorted, 0);
-    MPH_LAUNCH("sinit_place", L.stream, k_sinit_place, g, b, 0, L.stream, ns, key, slot, L.start, tmp, sorted, 1);
-    if (P.dim == 3)
-        MPH_LAUNCH("sinit_search", L.stream, k_sinit_search<3>, g, b, 0, L.stream, P, ns, x0, L.start, sorted, ocnt,
-                   (int*)nullptr, 0, 0, L.st);
-    else
-        MPH_LAUNCH("sinit_search", L.stream, k_sinit_search<2>, g, b, 0, L.stream, P, ns, x0, L.start, sorted, ocnt,
-                   (int*)nullptr, 0, 0, L.st);
+    launch(prof, "sinit_bin", L.stream, k_sinit_bin, g, b, P, ns, x0, key, L.cnt, slot);
+    launch_scan(L.cnt, P.ncell, L.bsum, L.start, ns, nullptr, L.stream, prof);
+    launch(prof, "sinit_place", L.stream, k_sinit_place, g, b, ns, key, slot, L.start, tmp, sorted, 0);
+    launch(prof, "sinit_place", L.stream, k_sinit_place, g, b, ns, key, slot, L.start, tmp, sorted, 1);
+    search(nullptr, 0, 0);
     // ELL width = the longest row (one host read at initialisation)
     std::vector<int> h(ns);
     if (hipMemcpyAsync(h.data(), ocnt, sizeof(int) * ns, hipMemcpyDeviceToHost, L.stream) != hipSuccess ||
@@ -3179,18 +3180,12 @@ int launch_struct_init(const Launch& L, int ns, const double4* x0, int* key, int
     *eo = (int*)alloc(actx, ntile * w * 64 * sizeof(int));
     if (!*eo) return -3;
     if (hipMemsetAsync(*eo, 0, ntile * w * 64 * sizeof(int), L.stream) != hipSuccess) return -1;
-    if (P.dim == 3)
-        MPH_LAUNCH("sinit_search", L.stream, k_sinit_search<3>, g, b, 0, L.stream, P, ns, x0, L.start, sorted, ocnt,
-                   *eo, w, 1, L.st);
-    else
-        MPH_LAUNCH("sinit_search", L.stream, k_sinit_search<2>, g, b, 0, L.stream, P, ns, x0, L.start, sorted, ocnt,
-                   *eo, w, 1, L.st);
-    MPH_LAUNCH("sinit_sort_rows", L.stream, k_sinit_sort_rows, g, b, 0, L.stream, ns, ocnt, *eo, w);
+    search(*eo, w, 1);
+    launch(prof, "sinit_sort_rows", L.stream, k_sinit_sort_rows, g, b, ns, ocnt, *eo, w);
     *wo = w;
     // transpose: in-degrees, width, then the rows (atomic order) sorted ascending
     if (hipMemsetAsync(icnt, 0, sizeof(int) * ns, L.stream) != hipSuccess) return -1;
-    MPH_LAUNCH("sinit_transpose", L.stream, k_sinit_transpose, g, b, 0, L.stream, ns, ocnt, *eo, w, icnt,
-               (int*)nullptr, 0, 0);
+    launch(prof, "sinit_transpose", L.stream, k_sinit_transpose, g, b, ns, ocnt, *eo, w, icnt, nullptr, 0, 0);
     if (hipMemcpyAsync(h.data(), icnt, sizeof(int) * ns, hipMemcpyDeviceToHost, L.stream) != hipSuccess ||
         hipStreamSynchronize(L.stream) != hipSuccess)
         return -1;
@@ -3200,44 +3195,28 @@ int launch_struct_init(const Launch& L, int ns, const double4* x0, int* key, int
     if (!*ei) return -3;
     if (hipMemsetAsync(*ei, 0, ntile * wi2 * 64 * sizeof(int), L.stream) != hipSuccess) return -1;
     if (hipMemsetAsync(icnt, 0, sizeof(int) * ns, L.stream) != hipSuccess) return -1;
-    MPH_LAUNCH("sinit_transpose", L.stream, k_sinit_transpose, g, b, 0, L.stream, ns, ocnt, *eo, w, icnt, *ei,
-               wi2, 1);
-    MPH_LAUNCH("sinit_sort_rows", L.stream, k_sinit_sort_rows, g, b, 0, L.stream, ns, icnt, *ei, wi2);
+    launch(prof, "sinit_transpose", L.stream, k_sinit_transpose, g, b, ns, ocnt, *eo, w, icnt, *ei, wi2, 1);
+    launch(prof, "sinit_sort_rows", L.stream, k_sinit_sort_rows, g, b, ns, icnt, *ei, wi2);
     *wi = wi2;
-    if (P.dim == 3)
-        MPH_LAUNCH("sinit_normalizer", L.stream, k_sinit_normalizer<3>, g, b, 0, L.stream, P, ns, x0, ocnt, *eo, w,
-                   Lm, wx0);
-    else
-        MPH_LAUNCH("sinit_normalizer", L.stream, k_sinit_normalizer<2>, g, b, 0, L.stream, P, ns, x0, ocnt, *eo, w,
-                   Lm, wx0);
+    by_dim(P.dim, [&](auto D) {
+        launch(prof, "sinit_normalizer", L.stream, k_sinit_normalizer<decltype(D)::value>, g, b, P, ns, x0, ocnt, *eo,
+               w, Lm, wx0);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 void launch_struct_pack(const Launch& L, const double4* src, int w, const int* idx, int m, double4* buf)
 {
-    Profiler* prof = L.prof;
     if (m <= 0) return;
-    MPH_LAUNCH("struct_pack", L.stream, k_struct_pack, dim3(blocks(m * w, 256)), dim3(256), 0, L.stream, src, w,
-               idx, m, buf);
+    launch(L.prof, "struct_pack", L.stream, k_struct_pack, dim3(blocks(m * w, 256)), dim3(256), src, w, idx, m,
+           buf);
 }
 
 void launch_struct_unpack(const Launch& L, const double4* buf, int w, const int* idx, int m, double4* dst)
 {
-    Profiler* prof = L.prof;
     if (m <= 0) return;
-    MPH_LAUNCH("struct_unpack", L.stream, k_struct_unpack, dim3(blocks(m * w, 256)), dim3(256), 0, L.stream, buf,
-               w, idx, m, dst);
-}
-
-void launch_scan(int* cnt, int ncell, int* bsum, int* start, int total, hipStream_t stream, Profiler* prof)
-{
-    const int nb = blocks(ncell, kScanBlock);
-    const int top = nb <= kScanFusedTop;
-    MPH_LAUNCH("scan_reduce", stream, k_scan_reduce, dim3(nb), dim3(kScanThreads), 0, stream, cnt, ncell, bsum);
-    if (!top)
-        MPH_LAUNCH("scan_top", stream, k_scan_top, dim3(1), dim3(1024), 0, stream, bsum, nb);
-    MPH_LAUNCH("scan_down", stream, k_scan_down, dim3(nb), dim3(kScanThreads), 0, stream, cnt, ncell, bsum,
-               start, total, (const int*)nullptr, top);
+    launch(L.prof, "struct_unpack", L.stream, k_struct_unpack, dim3(blocks(m * w, 256)), dim3(256), buf, w, idx,
+           m, dst);
 }
 
 int dist_blocks(int n) { return blocks(n > 0 ? n : 1, 256); }
@@ -3245,69 +3224,61 @@ int dist_blocks(int n) { return blocks(n > 0 ? n : 1, 256); }
 void launch_dist_classify(const Launch& L, const SlabGeom& g, int cap, const DistLayout* lay, int move, int* cls,
                           int* bcnt, const int* wface)
 {
-    Profiler* prof = L.prof;
     const int nb = dist_blocks(cap);
-    MPH_LAUNCH("dist_classify", L.stream, k_dist_classify, dim3(nb), dim3(256), 0, L.stream, *L.P, L.st, g,
-               L.B, lay, move, cls, bcnt, nb, wface);
+    launch(L.prof, "dist_classify", L.stream, k_dist_classify, dim3(nb), dim3(256), *L.P, L.st, g, L.B, lay, move,
+           cls, bcnt, nb, wface);
 }
 
 void launch_dist_early_classify(const Launch& L, const SlabGeom& g, int cap, const DistLayout* lay,
                                 const int* wface, int* cls, int* bcnt)
 {
-    Profiler* prof = L.prof;
     const int nb = dist_blocks(cap);
-    MPH_LAUNCH("dist_early_classify", L.stream, k_dist_early_classify, dim3(nb), dim3(256), 0, L.stream, *L.P,
-               L.st, g, L.B, lay, wface, cls, bcnt, nb);
+    launch(L.prof, "dist_early_classify", L.stream, k_dist_early_classify, dim3(nb), dim3(256), *L.P, L.st, g, L.B,
+           lay, wface, cls, bcnt, nb);
 }
 
 void launch_dist_early_pack(const Launch& L, int cap, DistLayout* lay, const int* cls, const int* boff, int cap_l,
                             int cap_r, char* buf_l, char* buf_r)
 {
-    Profiler* prof = L.prof;
     const int nb = dist_blocks(cap);
-    MPH_LAUNCH("dist_early_pack", L.stream, k_dist_early_pack, dim3(nb), dim3(256), 0, L.stream, L.B, lay, cls,
-               boff, nb, cap_l, cap_r, L.st, buf_l, buf_r);
+    launch(L.prof, "dist_early_pack", L.stream, k_dist_early_pack, dim3(nb), dim3(256), L.B, lay, cls, boff, nb,
+           cap_l, cap_r, L.st, buf_l, buf_r);
 }
 
 void launch_dist_scatter(const Launch& L, int cap, DistLayout* lay, const int* cls, const int* boff,
                          const Soa& C, int* dseg, int* vidx)
 {
-    Profiler* prof = L.prof;
     const int nb = dist_blocks(cap);
-    MPH_LAUNCH("dist_scatter", L.stream, k_dist_scatter, dim3(nb), dim3(256), 0, L.stream, L.B, lay, cls, boff,
-               nb, C, dseg, vidx);
+    launch(L.prof, "dist_scatter", L.stream, k_dist_scatter, dim3(nb), dim3(256), L.B, lay, cls, boff, nb, C, dseg,
+           vidx);
 }
 
 void launch_dist_pack(const Launch& L, const Soa& C, DistLayout* lay, int cap_l, int cap_r, char* buf_l,
                       char* buf_r, const VSrc& vs)
 {
-    Profiler* prof = L.prof;
-    MPH_LAUNCH("dist_pack", L.stream, k_dist_pack, dim3(dist_blocks(std::max(cap_l, cap_r)), 2), dim3(256), 0,
-               L.stream, C, lay, cap_l, cap_r, L.st, buf_l, buf_r, vs);
+    launch(L.prof, "dist_pack", L.stream, k_dist_pack, dim3(dist_blocks(std::max(cap_l, cap_r)), 2), dim3(256), C, lay,
+           cap_l, cap_r, L.st, buf_l, buf_r, vs);
 }
 
 void launch_dist_unpack(const Launch& L, const char* buf_l, const char* buf_r, DistLayout* lay, int cap_l,
                         int cap_r, int cap, const Soa& C)
 {
-    Profiler* prof = L.prof;
-    MPH_LAUNCH("dist_unpack", L.stream, k_dist_unpack, dim3(dist_blocks(std::max(cap_l, cap_r)), 2), dim3(256), 0,
-               L.stream, buf_l, buf_r, lay, cap_l, cap_r, cap, L.st, C);
+    launch(L.prof, "dist_unpack", L.stream, k_dist_unpack, dim3(dist_blocks(std::max(cap_l, cap_r)), 2), dim3(256),
+           buf_l, buf_r, lay, cap_l, cap_r, cap, L.st, C);
 }
 
 void launch_halo_pack(const Launch& L, const int* dst_of, const DistLayout* lay, int cap_l, int cap_r,
                       const HaloFields& F, double* buf_l, double* buf_r)
 {
-    Profiler* prof = L.prof;
-    MPH_LAUNCH("halo_pack", L.stream, k_halo_pack, dim3(dist_blocks(std::max(cap_l, cap_r)), 2), dim3(256), 0,
-               L.stream, dst_of, lay, cap_l, cap_r, F, buf_l, buf_r);
+    launch(L.prof, "halo_pack", L.stream, k_halo_pack, dim3(dist_blocks(std::max(cap_l, cap_r)), 2), dim3(256), dst_of,
+           lay, cap_l, cap_r, F, buf_l, buf_r);
 }
 
 void launch_halo_unpack(const Launch& L, const double* buf_l, const double* buf_r, const int* dst_of,
                         const DistLayout* lay, int cap_l, int cap_r, const HaloFields& F)
 {
-    Profiler* prof = L.prof;
-    MPH_LAUNCH("halo_unpack", L.stream, k_halo_unpack, dim3(dist_blocks(std::max(cap_l, cap_r)), 2), dim3(256), 0,
-               L.stream, buf_l, buf_r, dst_of, lay, cap_l, cap_r, F);
+    launch(L.prof, "halo_unpack", L.stream, k_halo_unpack, dim3(dist_blocks(std::max(cap_l, cap_r)), 2), dim3(256),
+           buf_l, buf_r, dst_of, lay, cap_l, cap_r, F);
 }
 
 }  // namespace mph

@@ -226,6 +226,13 @@ constexpr size_t kStateHead = offsetof(DevState, seg_work);
 #define MPH_HD
 #endif
 
+// The lists' row jumps (kAlignRows above; mph_kernels.hip RowMask), decoded alike by the kernels and
+// the host readers: byte 7 of a wave's header word is its jump count J; gap k < J of a lane is the
+// rows [byte k of the lane's gap word, byte k of the header).
+MPH_HD inline int jump_count(unsigned long long hdr) { return (int)(hdr >> 56); }
+MPH_HD inline int gap_begin(unsigned long long gap, int k) { return (int)((gap >> (8 * k)) & 0xff); }
+MPH_HD inline int gap_end(unsigned long long hdr, int k) { return (int)((hdr >> (8 * k)) & 0xff); }
+
 // Pass A's single-cutoff form (pass_a_term<.., true>) when RadiusA = RadiusP = RadiusV (RadiusG =
 // RadiusA, main.cpp:1195-1198), as in every BASELINE config.
 #ifndef MPH_PA_EQR

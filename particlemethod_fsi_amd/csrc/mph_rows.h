@@ -1,0 +1,38 @@
+// mph_rows.h -- host view of the neighbour lists' rows (no HIP types: builds with plain g++).
+#pragma once
+
+#include <algorithm>
+#include <vector>
+
+#include "mph_params.h"
+
+namespace mph {
+
+// The lists' rows as the last search left them (mph_kernels.hip RowMask): per particle (sorted
+// order) its rows [0, rows[s]) and, per wave, the row jumps (jump_count / gap_begin / gap_end).
+struct HostRows {
+    std::vector<int> rows;
+    std::vector<unsigned long long> hdr, gap;
+    // whether row r of particle s holds one of its entries
+    bool ok(int s, int r) const
+    {
+        const unsigned long long h = hdr[s >> 6];
+        for (int k = 0; k < jump_count(h); ++k)
+            if (r >= gap_begin(gap[s], k) && r < gap_end(h, k)) return false;
+        return r < rows[s];
+    }
+    int entries(int s) const
+    {
+        const unsigned long long h = hdr[s >> 6];
+        const int end = std::min(rows[s], kTileRows);
+        // At a jump every lane's row counter moves on to the gap's end (scan_candidates_lds
+        // group_end: soff += (m - row) << 8, in all lanes) and only grows after it, so the search
+        // leaves rows[s] >= every gap end, and those are below kAlignRows < kTileRows: on its lists
+        // the clamps change nothing.  Like the kernels' row_mask, a gap past the end takes nothing.
+        int e = end;
+        for (int k = 0; k < jump_count(h); ++k) e -= std::min(gap_end(h, k), end) - std::min(gap_begin(gap[s], k), end);
+        return e;
+    }
+};
+
+}  // namespace mph

@@ -29,6 +29,29 @@ def asan_binary(tmp_path_factory):
     return out
 
 
+def test_host_rows_against_model(tmp_path):
+    """HostRows::ok / entries (csrc/mph_rows.h, the decoder the kernels share) against a brute-force
+    model on hand-made waves (tests/native/rows_check.cpp), under ASan + UBSan."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    flags = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+             "-fno-sanitize-recover=all", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
+    # whether the sanitizers are there is decided on an empty program, so that a header or a
+    # rows_check.cpp that does not compile fails the test instead of skipping it
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    r = subprocess.run(flags + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
+    if r.returncode != 0:
+        pytest.skip("sanitizer build unavailable: " + r.stderr[-500:])
+    out = str(tmp_path / "rows_check")
+    r = subprocess.run(flags + [os.path.join(ROOT, "tests", "native", "rows_check.cpp"), "-o", out],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([out], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert "runtime error" not in r.stderr
+
+
 @pytest.mark.parametrize("case", ["dam2d", "bar2d", "gate2d", "box3d", "gate3d"])
 def test_host_layer_under_asan_ubsan(asan_binary, case, tmp_path):
     c = cases.get(case)
