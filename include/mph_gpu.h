@@ -41,9 +41,9 @@ extern "C" {
 #define MPH_TYPE_COUNT 6            /* main.cpp:68 */
 #define MPH_MAX_NEIGHBOR_COUNT 512  /* main.cpp:100 (semantic limit; overflow is an error here) */
 /* Bumped on every incompatible change of a declaration below (3: mph_slab_bounds/_owner/_window
- * take `cuts`; mph_dist_info slot 0/2 meaning; 5: mph_list_layout added); bindings compare
- * mph_abi_version() with it.                                                                  */
-#define MPH_ABI_VERSION 5
+ * take `cuts`; mph_dist_info slot 0/2 meaning; 5: mph_list_layout added; 6: the monitors); bindings
+ * compare mph_abi_version() with it.                                                          */
+#define MPH_ABI_VERSION 6
 
 /* Compile-time case modules of the reference (main.cpp:54-59) as a runtime switch.  The module
  * selects the clamp rule of updateElasticPosition (main.cpp:1918-2044).                        */
@@ -230,7 +230,8 @@ int mph_step(MphCtx* ctx, int nsteps);
  * mph_step(ctx, 8) instead of eight synchronised single steps.  Time (mph_time) advances per call.
  * Steps still pending run, and the error flags of everything launched are read, at the next
  * flush point: mph_synchronize, mph_get, mph_set, every writer, mph_compute_virial,
- * mph_neighbor_stats, mph_profile_steps, mph_phase_timing, turning batching off, mph_destroy; so
+ * mph_neighbor_stats, mph_profile_steps, mph_phase_timing, mph_monitor_configure, mph_monitor_read,
+ * turning batching off, mph_destroy; so
  * every field read after a step is that step's, bit for bit as without batching.  A launched
  * batch's error is also reported by a later mph_step once its flags have landed (no wait).
  * Errors therefore surface up to two batches late, or at the next flush point.  Off by default. */
@@ -277,6 +278,85 @@ void mph_destroy(MphCtx* ctx);
  * the first call.  Slab mode: collective; every rank computes its owned particles, after one halo
  * exchange of the ghosts' post-step positions and velocities.                               */
 int mph_compute_virial(MphCtx* ctx);
+
+/* ---- per-step monitors ------------------------------------------------------------------------ */
+
+/* A time history without mph_get: while monitors are on, every step (whichever way mph_step runs
+ * it: the captured graphs, step batching, phase timing, mph_profile_steps) ends with kernels that
+ * reduce the state the step leaves into one record, the sample, and every `stride`-th step's
+ * sample is kept in a ring buffer on the device.  Reading the ring is a flush point like mph_get,
+ * stepping is not.  With monitors off a step is what it was.  Single contexts only.
+ *
+ * A sample is MPH_MONITOR_HEAD doubles (MphMonitorSlot), then {x, y, z, vx, vy, vz} per tracked
+ * particle, then {value, count} per probe.  Every slot but the probes is the named function of
+ * what mph_get would return for Position, Velocity, PressureP and Property right after that step;
+ * the mass of a particle is Density[type] * V (MPH_FIELD_MASS).  Sums are taken in an order fixed
+ * by the particle count, so the same state gives the same bits in any batch shape.  Extrema over
+ * no particle: +inf for a minimum, -inf for a maximum, 0 for VMAX2.
+ * Probe q: the Shepard average of the step's PressureP over the fluid particles within
+ * probe_radius h of the probe, value = sum w P / sum w with w = (1 - r/h)^2 for r < h, r the
+ * minimum-image distance to the position PressureP was computed at (the step's sorted set: the
+ * wrapped position before the step's motion); count = the contributing particles; no particle in
+ * range: value = count = 0.  2-D: a probe's z is ignored.                                        */
+#define MPH_MONITOR_MAX_TRACK  64
+#define MPH_MONITOR_MAX_PROBES 64
+#define MPH_MONITOR_HEAD       32
+typedef enum MphMonitorSlot {
+    MPH_MON_STEP = 0,            /* steps since mph_monitor_configure at which the sample was taken */
+    MPH_MON_TIME = 1,            /* == mph_time after that step, bit for bit                        */
+    /* per class, six slots: COUNT, KE = sum 1/2 m v.v, PX PY PZ = sum m v, VMAX2 = max v.v
+     * (vx vx + vy vy + vz vz left to right, no contraction)                                       */
+    MPH_MON_FLUID_COUNT = 2,     /* fluid: types 0, 1 */
+    MPH_MON_FLUID_KE = 3,
+    MPH_MON_FLUID_PX = 4,
+    MPH_MON_FLUID_PY = 5,
+    MPH_MON_FLUID_PZ = 6,
+    MPH_MON_FLUID_VMAX2 = 7,
+    MPH_MON_STRUCT_COUNT = 8,    /* structure: types 2, 3 */
+    MPH_MON_STRUCT_KE = 9,
+    MPH_MON_STRUCT_PX = 10,
+    MPH_MON_STRUCT_PY = 11,
+    MPH_MON_STRUCT_PZ = 12,
+    MPH_MON_STRUCT_VMAX2 = 13,
+    MPH_MON_WALL_COUNT = 14,     /* walls: types 4, 5 */
+    MPH_MON_WALL_KE = 15,
+    MPH_MON_WALL_PX = 16,
+    MPH_MON_WALL_PY = 17,
+    MPH_MON_WALL_PZ = 18,
+    MPH_MON_WALL_VMAX2 = 19,
+    MPH_MON_XMIN = 20,           /* bounding box of the fluid */
+    MPH_MON_XMAX = 21,
+    MPH_MON_YMIN = 22,
+    MPH_MON_YMAX = 23,
+    MPH_MON_ZMIN = 24,
+    MPH_MON_ZMAX = 25,
+    MPH_MON_FLUID_PMIN = 26,     /* PressureP over the fluid */
+    MPH_MON_FLUID_PMAX = 27,
+    MPH_MON_WALL_PMAX = 28,      /* PressureP over the walls */
+    MPH_MON_EPOT = 29,           /* - sum m (g . x) over fluid and structure particles */
+    MPH_MON_RESERVED0 = 30,      /* zero */
+    MPH_MON_RESERVED1 = 31
+} MphMonitorSlot;
+typedef struct MphMonitorConfig {
+    int stride;            /* sample the steps k = stride, 2 stride, ... counted from this call (>= 1) */
+    int capacity;          /* samples the device ring holds (>= 1) */
+    int ntrack;            /* tracked particles (original indices), 0..MAX_TRACK */
+    const int* track;
+    int nprobe;            /* pressure probes, 0..MAX_PROBES */
+    const double* probes;  /* [nprobe][3], wrapped into the periodic domain like a particle */
+    double probe_radius;   /* 0: RadiusRatioP * dx; must be <= MaxRadius + MARGIN (the cell stencil's reach) */
+} MphMonitorConfig;
+/* Turn monitors on with *cfg (replacing an earlier configuration: the ring is emptied, STEP counts
+ * from this call) or, cfg == NULL, off.  A flush point; the step graphs are captured again at the
+ * next step.  MPH_ERR_ARG: stride or capacity < 1, a count over its maximum, a track index outside
+ * [0, n), a probe radius below 0 or over the stencil's reach.  MPH_ERR_UNSUPPORTED: slab mode.   */
+int mph_monitor_configure(MphCtx* ctx, const MphMonitorConfig* cfg);
+/* Doubles per sample: MPH_MONITOR_HEAD + 6 ntrack + 2 nprobe; 0 with monitors off.              */
+int mph_monitor_sample_doubles(const MphCtx* ctx);
+/* Copy the unread samples, oldest first and at most max_samples, to out ([k][sample doubles]) and
+ * return how many.  The ring keeps the newest `capacity` samples: *lost (may be NULL) receives how
+ * many unread samples were overwritten since the last read.  A flush point, like mph_get.        */
+long long mph_monitor_read(MphCtx* ctx, double* out, long long max_samples, long long* lost);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

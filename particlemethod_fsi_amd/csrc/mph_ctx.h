@@ -119,6 +119,15 @@ struct MphCtx {
     mph::StructDev Sd;
     std::vector<void*> allocs;
     mph::Launch L;
+    // monitors (mph_monitor_configure): the kernels' arguments (L.mon points here while they are
+    // on), the device buffers behind them (allocated once, the ring regrown when too small) and
+    // how many samples the host has read
+    bool mon_on = false;
+    mph::MonitorDev mon;
+    size_t mon_ring_cap = 0;     // doubles the ring allocation holds
+    int *mon_sorted = nullptr, *mon_map = nullptr;
+    double* mon_probes = nullptr;
+    long long mon_read = 0;
     MphDist* dist = nullptr;     // non-null in slab mode
 };
 
@@ -139,6 +148,7 @@ namespace mph {
 int ctx_fail(MphCtx* c, int code, const std::string& msg);
 int ctx_hip_fail(MphCtx* c, hipError_t e, const char* what);
 void* ctx_alloc(MphCtx* c, size_t bytes, int* status);
+void ctx_dfree(MphCtx* c, void* p);   // free one ctx_alloc allocation now
 
 template <typename T>
 int ctx_dalloc(MphCtx* c, T** p, size_t count)

@@ -46,6 +46,13 @@ void* ctx_alloc(MphCtx* c, size_t bytes, int* status)
     return q;
 }
 
+void ctx_dfree(MphCtx* c, void* p)
+{
+    if (!p) return;
+    c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), p), c->allocs.end());
+    (void)hipFree(p);
+}
+
 // Error flags raised by the kernels (DevState.overflow bits).
 int ctx_state_status(MphCtx* c, const DevState& hs)
 {
@@ -131,6 +138,7 @@ void enqueue_step(const Launch& L, bool last, hipEvent_t* ev = nullptr)
     }
     launch_structure(L, last);
     if (ev) (void)hipEventRecord(ev[2], L.stream);
+    if (L.mon) launch_monitor(L, *L.mon);   // monitors on: this step's sample (mph_monitor.hip)
 }
 
 // store_last = false: no step of the graph stores the output-only fields (graph1t, the steps of a
@@ -1370,6 +1378,124 @@ int mph_neighbor_rows(MphCtx* c, int first, int count, int* counts, int* ids, lo
         w += m;
     }
     return (int)std::min<long long>(w, 0x7fffffff);
+}
+
+// ---- per-step monitors (kernels: mph_monitor.hip) ----------------------------------------------
+
+// the step graphs hold the monitor kernels and their arguments: captured again at the next step
+static int drop_graphs(MphCtx* c)
+{
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    for (hipGraphExec_t* g : {&c->graph1, &c->graph1t, &c->graph8})
+        if (*g) {
+            MPH_HIP_OK(c, hipGraphExecDestroy(*g));
+            *g = nullptr;
+        }
+    return MPH_OK;
+}
+
+int mph_monitor_configure(MphCtx* c, const MphMonitorConfig* m)
+{
+    if (!c) return MPH_ERR_ARG;
+    MPH_CK(ctx_flush(c));
+    if (c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "monitors are not available in slab mode (no cross-rank reduction yet)");
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    if (!m) {
+        if (c->mon_on) MPH_CK(drop_graphs(c));
+        c->mon_on = false;
+        c->L.mon = nullptr;
+        return MPH_OK;
+    }
+    if (m->stride < 1 || m->capacity < 1) return ctx_fail(c, MPH_ERR_ARG, "monitors: stride and capacity must be >= 1");
+    if (m->ntrack < 0 || m->ntrack > MPH_MONITOR_MAX_TRACK || (m->ntrack > 0 && !m->track))
+        return ctx_fail(c, MPH_ERR_ARG, "monitors: 0.." + std::to_string(MPH_MONITOR_MAX_TRACK) + " tracked particles");
+    if (m->nprobe < 0 || m->nprobe > MPH_MONITOR_MAX_PROBES || (m->nprobe > 0 && !m->probes))
+        return ctx_fail(c, MPH_ERR_ARG, "monitors: 0.." + std::to_string(MPH_MONITOR_MAX_PROBES) + " probes");
+    for (int k = 0; k < m->ntrack; ++k)
+        if (m->track[k] < 0 || m->track[k] >= c->n_glob)
+            return ctx_fail(c, MPH_ERR_ARG, "monitors: tracked index " + std::to_string(m->track[k]) + " outside [0, n)");
+    const double reach = c->h.max_radius + 0.1 * c->h.dx;   // MaxRadius + MARGIN (make_dev_params)
+    if (!(m->probe_radius >= 0.0) || m->probe_radius > reach)
+        return ctx_fail(c, MPH_ERR_ARG, "monitors: probe radius outside [0, MaxRadius + MARGIN = " + std::to_string(reach) + "]");
+    MPH_CK(drop_graphs(c));
+    MonitorDev& D = c->mon;
+    if (!D.counters) {   // once, for the maxima
+        MPH_CK(ctx_dalloc(c, &D.counters, 2));
+        MPH_CK(ctx_dalloc(c, &D.partial, (size_t)kMonPartial * monitor_blocks(c->n)));
+        MPH_CK(ctx_dalloc(c, &D.trk, 6 * (size_t)MPH_MONITOR_MAX_TRACK));
+        MPH_CK(ctx_dalloc(c, &D.prb, 2 * (size_t)MPH_MONITOR_MAX_PROBES));
+        MPH_CK(ctx_dalloc(c, &c->mon_sorted, MPH_MONITOR_MAX_TRACK));
+        MPH_CK(ctx_dalloc(c, &c->mon_map, MPH_MONITOR_MAX_TRACK));
+        MPH_CK(ctx_dalloc(c, &c->mon_probes, 3 * (size_t)MPH_MONITOR_MAX_PROBES));
+        D.track_sorted = c->mon_sorted;
+        D.track_map = c->mon_map;
+        D.probes = c->mon_probes;
+    }
+    const int width = MPH_MONITOR_HEAD + 6 * m->ntrack + 2 * m->nprobe;
+    const size_t need = (size_t)m->capacity * width;
+    if (need > c->mon_ring_cap) {
+        ctx_dfree(c, D.ring);
+        D.ring = nullptr;
+        c->mon_ring_cap = 0;
+        MPH_CK(ctx_dalloc(c, &D.ring, need));
+        c->mon_ring_cap = need;
+    }
+    // the distinct tracked ids ascending (the kernel's search), and each entry's row among them
+    std::vector<int> sorted(m->track, m->track + m->ntrack);
+    std::sort(sorted.begin(), sorted.end());
+    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+    std::vector<int> map(MPH_MONITOR_MAX_TRACK, 0);
+    for (int k = 0; k < m->ntrack; ++k)
+        map[k] = (int)(std::lower_bound(sorted.begin(), sorted.end(), m->track[k]) - sorted.begin());
+    sorted.resize(MPH_MONITOR_MAX_TRACK, 0x7fffffff);
+    std::vector<double> probes(3 * (size_t)MPH_MONITOR_MAX_PROBES, 0.0);
+    std::copy(m->probes, m->probes + 3 * (size_t)m->nprobe, probes.begin());
+    MPH_HIP_OK(c, hipMemcpy(c->mon_sorted, sorted.data(), sizeof(int) * sorted.size(), hipMemcpyHostToDevice));
+    MPH_HIP_OK(c, hipMemcpy(c->mon_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
+    MPH_HIP_OK(c, hipMemcpy(c->mon_probes, probes.data(), sizeof(double) * probes.size(), hipMemcpyHostToDevice));
+    MPH_HIP_OK(c, hipMemset(D.counters, 0, 2 * sizeof(long long)));
+    MPH_HIP_OK(c, hipMemset(D.trk, 0, sizeof(double) * 6 * MPH_MONITOR_MAX_TRACK));
+    MPH_HIP_OK(c, hipMemset(D.prb, 0, sizeof(double) * 2 * MPH_MONITOR_MAX_PROBES));
+    D.stride = m->stride;
+    D.capacity = m->capacity;
+    D.ntrack = m->ntrack;
+    D.nprobe = m->nprobe;
+    D.width = width;
+    D.probe_h = m->probe_radius > 0.0 ? m->probe_radius : c->h.rp;
+    c->mon_read = 0;
+    c->mon_on = true;
+    c->L.mon = &c->mon;
+    return MPH_OK;
+}
+
+int mph_monitor_sample_doubles(const MphCtx* c) { return c && c->mon_on ? c->mon.width : 0; }
+
+long long mph_monitor_read(MphCtx* c, double* out, long long max_samples, long long* lost)
+{
+    if (!c || max_samples < 0 || (max_samples > 0 && !out)) return MPH_ERR_ARG;
+    if (lost) *lost = 0;
+    MPH_CK(ctx_flush(c));
+    if (!c->mon_on) return 0;
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    const MonitorDev& D = c->mon;
+    long long cnt[2] = {0, 0};
+    MPH_HIP_OK(c, hipMemcpy(cnt, D.counters, sizeof(cnt), hipMemcpyDeviceToHost));
+    const long long unread = cnt[1] - c->mon_read;
+    const long long avail = std::min<long long>(unread, D.capacity);
+    if (lost) *lost = unread - avail;
+    const long long first = cnt[1] - avail, k = std::min(avail, max_samples);
+    // samples first .. first + k - 1, sample i in ring slot i mod capacity: at most two runs
+    for (long long i = first; i < first + k;) {
+        const long long slot = i % D.capacity;
+        const long long run = std::min<long long>(first + k - i, D.capacity - slot);
+        MPH_HIP_OK(c, hipMemcpy(out + (size_t)(i - first) * D.width, D.ring + (size_t)slot * D.width,
+                                sizeof(double) * (size_t)run * D.width, hipMemcpyDeviceToHost));
+        i += run;
+    }
+    c->mon_read = first + k;
+    return k;
 }
 
 void mph_destroy(MphCtx* c)

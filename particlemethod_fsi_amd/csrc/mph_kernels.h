@@ -87,6 +87,24 @@ struct StructHook {
     int* bidx;
 };
 
+// Per-step monitors (mph_monitor.hip): the configuration and device buffers of
+// mph_monitor_configure, passed to the monitor kernels by value.
+constexpr int kMonFirst = 2;      // head slots [kMonFirst, kMonFirst + kMonPartial) are reduced over particles
+constexpr int kMonPartial = 28;   // entries of a block's partial record
+struct MonitorDev {
+    int stride = 1, capacity = 1, ntrack = 0, nprobe = 0;
+    int width = 0;                     // doubles per sample
+    double probe_h = 0.0;
+    long long* counters = nullptr;     // {steps since the configuration, samples written}
+    double* ring = nullptr;            // [capacity][width]
+    double* partial = nullptr;         // [monitor_blocks(n)][kMonPartial]
+    double* trk = nullptr;             // rows {x, y, z, vx, vy, vz} of the distinct tracked ids
+    double* prb = nullptr;             // {value, count} per probe
+    const int* track_sorted = nullptr; // the distinct tracked ids ascending, padded with INT_MAX to 64
+    const int* track_map = nullptr;    // tracked entry k -> its row of trk
+    const double* probes = nullptr;    // [nprobe][3]
+};
+
 // Everything one launch sequence needs.
 struct Launch {
     const DevParams* P = nullptr;
@@ -116,8 +134,11 @@ struct Launch {
     double4 *rec = nullptr;     // pass A: {x, y, z, PressureP}, the pass-B gather record
     double4 *force = nullptr, *acc = nullptr;   // outputs (A order)
     const StructDev* S = nullptr;
+    const MonitorDev* mon = nullptr;   // monitors on: sampled at the end of every step
 };
 
+int monitor_blocks(int n);   // blocks (partial records) of k_monitor_partial
+void launch_monitor(const Launch& L, const MonitorDev& M);
 void launch_sort(const Launch& L, int mode);   // mode 0 init, 1 step, 2 step (motion done)
 void launch_neighbors(const Launch& L);
 void launch_pass_a(const Launch& L);

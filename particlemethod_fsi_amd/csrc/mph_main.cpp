@@ -25,6 +25,7 @@
 #include <unistd.h>
 
 #include <cerrno>
+#include <cmath>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
@@ -99,6 +100,50 @@ static void die(MphCtx* c, int rc, const char* what)
     logf("error: %s failed (%d): %s\n", what, rc, c ? mph_last_error(c) : "");
     kill_children();   // rank 0: the other ranks would wait for it forever (children: none)
     std::exit(1);
+}
+
+// ---- monitors: MPH_MONITOR=<csv path> -----------------------------------------------------------
+// Opt-in time history (include/mph_gpu.h mph_monitor_*): every MPH_MONITOR_STRIDE-th step's sample
+// -- sums, extrema, the particles MPH_MONITOR_TRACK=i,j,... and the pressure probes
+// MPH_MONITOR_PROBES="x,y,z;x,y,z" -- is computed on the device inside the step graphs; the loop
+// reads the ring after each batch of steps, where it synchronises anyway, and appends one CSV row
+// per sample, a header line of column names first, the values as %.17g (the doubles round-trip).
+struct MonitorCsv {
+    FILE* f = nullptr;
+    int stride = 1, width = 0;
+    std::vector<int> track;
+    std::vector<double> probes;
+    std::vector<double> buf;
+};
+
+static std::vector<double> parse_numbers(const char* s)
+{
+    std::vector<double> v;
+    while (s && *s) {
+        char* e = nullptr;
+        const double x = std::strtod(s, &e);
+        if (e == s) { ++s; continue; }   // a separator (',' ';' blanks)
+        v.push_back(x);
+        s = e;
+    }
+    return v;
+}
+
+static void monitor_header(const MonitorCsv& m)
+{
+    static const char* cls[3] = {"fluid", "struct", "wall"};
+    static const char* per[6] = {"count", "ke", "px", "py", "pz", "vmax2"};
+    static const char* rest[12] = {"xmin", "xmax", "ymin", "ymax", "zmin", "zmax", "fluid_pmin", "fluid_pmax",
+                                   "wall_pmax", "epot", "reserved0", "reserved1"};
+    static const char* row[6] = {"x", "y", "z", "vx", "vy", "vz"};
+    std::fprintf(m.f, "step,time");
+    for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 6; ++k) std::fprintf(m.f, ",%s_%s", cls[c], per[k]);
+    for (int k = 0; k < 12; ++k) std::fprintf(m.f, ",%s", rest[k]);
+    for (int i : m.track)
+        for (int k = 0; k < 6; ++k) std::fprintf(m.f, ",p%d_%s", i, row[k]);
+    for (size_t q = 0; q < m.probes.size() / 3; ++q) std::fprintf(m.f, ",probe%zu_value,probe%zu_count", q, q);
+    std::fprintf(m.f, "\n");
 }
 
 // ---- slab ranks: fork, socket-pair ring, RCCL id over pipes ----------------------------------
@@ -255,6 +300,9 @@ int main(int argc, char** argv)
     SlabRank R;
     const int nslabs = std::getenv("MPH_SLABS") ? std::atoi(std::getenv("MPH_SLABS")) : 1;
     const bool host_transport = std::getenv("MPH_SLAB_TRANSPORT") && std::strcmp(std::getenv("MPH_SLAB_TRANSPORT"), "host") == 0;
+    if (nslabs > 1 && std::getenv("MPH_MONITOR"))   // (before any rank is started)
+        die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_MONITOR with MPH_SLABS > 1 (monitors need a single context; "
+                                         "the cross-rank reduction is not built yet)");
     if (nslabs > 1 && spawn_ranks(R, nslabs, host_transport) < 0) {
         std::fprintf(stderr, "error: could not start %d slab ranks\n", nslabs);
         return 1;
@@ -346,9 +394,34 @@ int main(int argc, char** argv)
         rc = mph_phase_timing(ctx, 1);
         if (rc) die(ctx, rc, "mph_phase_timing");
     }
+    const double dt = cfg.dt;
+    MonitorCsv mon;
+    if (const char* mp = std::getenv("MPH_MONITOR")) {
+        if (const char* e = std::getenv("MPH_MONITOR_STRIDE")) mon.stride = std::atoi(e);
+        for (double v : parse_numbers(std::getenv("MPH_MONITOR_TRACK"))) mon.track.push_back((int)v);
+        mon.probes = parse_numbers(std::getenv("MPH_MONITOR_PROBES"));
+        if (mon.probes.size() % 3 != 0) die(nullptr, MPH_ERR_ARG, "MPH_MONITOR_PROBES (x,y,z;x,y,z;...)");
+        // the ring holds the samples of the longest batch the loop below issues: a batch ends at the
+        // next .prof or .vtk output step or at EndTime
+        const double span = std::fmin(std::fmin(cfg.output_interval, cfg.vtk_output_interval), cfg.end_time - cfg.time);
+        const double most = std::fmin(std::fmax(span, 0.0) / dt + 4.0, 1.0e8);
+        MphMonitorConfig mc{};
+        mc.stride = mon.stride;
+        mc.capacity = (int)(most / (mon.stride > 0 ? mon.stride : 1)) + 2;
+        mc.ntrack = (int)mon.track.size();
+        mc.track = mon.track.data();
+        mc.nprobe = (int)(mon.probes.size() / 3);
+        mc.probes = mon.probes.data();
+        rc = mph_monitor_configure(ctx, &mc);
+        if (rc) die(ctx, rc, "mph_monitor_configure");
+        mon.width = mph_monitor_sample_doubles(ctx);
+        mon.buf.resize((size_t)mc.capacity * mon.width);
+        mon.f = std::fopen(mp, "w");
+        if (!mon.f) die(nullptr, MPH_ERR_IO, "opening the MPH_MONITOR file");
+        monitor_header(mon);
+    }
     const auto loop_t0 = std::chrono::steady_clock::now();
     double time_now = cfg.time;
-    const double dt = cfg.dt;
     int istep = (int)(time_now / dt);
     double out_next = 0.0, vtk_next = 0.0;
     const bool vtu = vtk.size() > 4 && vtk.compare(vtk.size() - 4, 4, ".vtu") == 0;
@@ -381,6 +454,18 @@ int main(int argc, char** argv)
         if (rc) die(ctx, rc, "mph_step");
         mph_synchronize(ctx);
         roctxRangePop();
+        if (mon.f) {
+            long long lost = 0;
+            const long long got = mph_monitor_read(ctx, mon.buf.data(), (long long)(mon.buf.size() / mon.width), &lost);
+            if (got < 0) die(ctx, (int)got, "mph_monitor_read");
+            if (lost) logf("error: the monitor ring overwrote %lld unread samples (ring sized too small)\n", lost);
+            for (long long r = 0; r < got; ++r) {
+                for (int k = 0; k < mon.width; ++k)
+                    std::fprintf(mon.f, k ? ",%.17g" : "%.17g", mon.buf[(size_t)r * mon.width + k]);
+                std::fprintf(mon.f, "\n");
+            }
+            std::fflush(mon.f);
+        }
         // fault injection for the failure-propagation test (tests/test_gpu_driver.py): this rank
         // fails after its first batch
         if (const char* f = std::getenv("MPH_FAIL_RANK"))
@@ -430,6 +515,7 @@ int main(int argc, char** argv)
     rc = mph_output_wait(ctx);
     if (rc) die(ctx, rc, "writing a .vtk file");
     mph_destroy(ctx);
+    if (mon.f) std::fclose(mon.f);
     if (g_log) std::fclose(g_log);
     // rank 0 waits for the other ranks (the SIGCHLD handler reaps them and ends the run if one failed)
     for (;;) {

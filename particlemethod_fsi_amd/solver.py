@@ -58,9 +58,10 @@ EXPORTED_SYMBOLS = [
     "mph_set_initial_velocity_profile", "mph_dist_info", "mph_create_slab", "mph_slab_window",
     "mph_list_stats", "mph_abi_version", "mph_phase_timing", "mph_phase_times",
     "mph_set_step_batching", "mph_neighbor_rows", "mph_dist_overlap", "mph_list_layout",
+    "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
 ]
 
-ABI_VERSION = 5   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
+ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
 
 # mph_host_exchange_fn (include/mph_gpu.h): (user, send_l, n, send_r, n, recv_l, n, recv_r, n)
 HOST_EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
@@ -74,6 +75,40 @@ class MphSlabOptions(ctypes.Structure):
                 ("unique_id128", ctypes.c_char_p), ("host_fn", HOST_EXCHANGE_FN),
                 ("host_user", ctypes.c_void_p), ("n_glob", ctypes.c_int), ("ids", ctypes.c_void_p),
                 ("cuts", ctypes.c_void_p)]
+
+
+class MphMonitorConfig(ctypes.Structure):
+    """include/mph_gpu.h MphMonitorConfig."""
+    _fields_ = [("stride", ctypes.c_int), ("capacity", ctypes.c_int), ("ntrack", ctypes.c_int),
+                ("track", ctypes.c_void_p), ("nprobe", ctypes.c_int), ("probes", ctypes.c_void_p),
+                ("probe_radius", ctypes.c_double)]
+
+
+# MphMonitorSlot (include/mph_gpu.h): name -> index into a sample's head
+MONITOR_HEAD = 32
+MONITOR_MAX_TRACK = 64
+MONITOR_MAX_PROBES = 64
+MONITOR_CLASSES = ("FLUID", "STRUCT", "WALL")
+MONITOR_SLOTS = {"STEP": 0, "TIME": 1}
+for _c, _cls in enumerate(MONITOR_CLASSES):
+    for _k, _q in enumerate(("COUNT", "KE", "PX", "PY", "PZ", "VMAX2")):
+        MONITOR_SLOTS["%s_%s" % (_cls, _q)] = 2 + 6 * _c + _k
+MONITOR_SLOTS.update({"XMIN": 20, "XMAX": 21, "YMIN": 22, "YMAX": 23, "ZMIN": 24, "ZMAX": 25,
+                      "FLUID_PMIN": 26, "FLUID_PMAX": 27, "WALL_PMAX": 28, "EPOT": 29,
+                      "RESERVED0": 30, "RESERVED1": 31})
+
+
+def monitor_split(row: np.ndarray, ntrack: int, nprobe: int):
+    """One sample (or [k, width] samples) -> (head [.., 32], tracked [.., ntrack, 6] rows
+    {x, y, z, vx, vy, vz}, probes [.., nprobe, 2] rows {value, count})."""
+    row = np.asarray(row)
+    lead = row.shape[:-1]
+    a, b = MONITOR_HEAD, MONITOR_HEAD + 6 * ntrack
+    if row.shape[-1] != b + 2 * nprobe:
+        raise ValueError("a sample of %d tracked particles and %d probes has %d doubles, not %d"
+                         % (ntrack, nprobe, b + 2 * nprobe, row.shape[-1]))
+    return (row[..., :a], row[..., a:b].reshape(lead + (ntrack, 6)),
+            row[..., b:].reshape(lead + (nprobe, 2)))
 
 
 class MphError(RuntimeError):
@@ -158,10 +193,14 @@ def load_library() -> ctypes.CDLL:
         "mph_neighbor_rows": (ip, [vp, ip, ip, vp, vp, ctypes.c_longlong]),
         "mph_dist_overlap": (ip, [vp, vp]),
         "mph_list_layout": (ip, [vp, vp]),
+        "mph_monitor_configure": (ip, [vp, ctypes.POINTER(MphMonitorConfig)]),
+        "mph_monitor_sample_doubles": (ip, [vp]),
+        "mph_monitor_read": (ctypes.c_longlong, [vp, vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
-                "mph_dist_overlap", "mph_profile_graphs", "mph_list_stats", "mph_list_layout"}
+                "mph_dist_overlap", "mph_profile_graphs", "mph_list_stats", "mph_list_layout",
+                "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -170,7 +209,8 @@ def load_library() -> ctypes.CDLL:
         f.argtypes = args
     # MPH_ABI_ACCEPT=3: an A/B run against a round-5 build (ABI 3 differs only by mph_list_formats,
     # replaced by mph_list_stats in 4; MPH_ABI_ACCEPT=4: a build before mph_list_layout, the only
-    # change of 5; tools/lib_bitwise.py)
+    # change of 5; MPH_ABI_ACCEPT=5: a build before the monitors, the only change of 6;
+    # tools/lib_bitwise.py)
     accept = {ABI_VERSION} | {int(v) for v in os.environ.get("MPH_ABI_ACCEPT", "").split(",") if v.strip()}
     if L.mph_abi_version() not in accept:
         raise ImportError("%s has C ABI version %d, these bindings expect %d (rebuild the library)"
@@ -457,6 +497,41 @@ class MphSolver:
         a = np.zeros(3)
         _check(self._L.mph_phase_times(self._h, a.ctypes.data), self._h)
         return {"neighbor_ms": float(a[0]), "explicit_ms": float(a[1]), "virial_ms": float(a[2])}
+
+    # -- monitors ---------------------------------------------------------------------------------
+    def monitor(self, stride=1, capacity: int = 4096, track=(), probes=(), probe_radius: float = 0.0):
+        """mph_monitor_configure: from the next step on, every `stride`-th step leaves a sample
+        (MONITOR_SLOTS, then the tracked particles `track` (original indices), then the pressure
+        probes `probes` ([k][3] points)) in a device ring of `capacity` samples, computed inside the
+        step graphs -- stepping stays batched, monitor_read() fetches.  monitor(None): off."""
+        if stride is None:
+            _check(self._L.mph_monitor_configure(self._h, None), self._h)
+            self._mon_shape = None
+            return
+        tr = np.ascontiguousarray(track, np.int32).reshape(-1)
+        pr = np.ascontiguousarray(probes, np.float64).reshape(-1, 3)
+        m = MphMonitorConfig(int(stride), int(capacity), len(tr), tr.ctypes.data if len(tr) else None,
+                             len(pr), pr.ctypes.data if len(pr) else None, float(probe_radius))
+        _check(self._L.mph_monitor_configure(self._h, ctypes.byref(m)), self._h)
+        self._mon_shape = (len(tr), len(pr))
+        self._mon_cap = int(capacity)
+
+    def monitor_read(self, max_samples: int | None = None):
+        """(samples [k, width], lost): the unread samples, oldest first, and how many unread ones the
+        ring overwrote since the last read.  A flush point like get()."""
+        w = self._L.mph_monitor_sample_doubles(self._h)
+        if w == 0:
+            return np.zeros((0, 0)), 0
+        cap = int(max_samples) if max_samples is not None else self._mon_cap
+        out = np.zeros((max(cap, 1), w))
+        lost = ctypes.c_longlong(0)
+        k = _check(self._L.mph_monitor_read(self._h, out.ctypes.data, cap, ctypes.byref(lost)), self._h)
+        return out[:k].copy(), int(lost.value)
+
+    def monitor_split(self, rows: np.ndarray):
+        """monitor_split(rows, ...) with this solver's tracked-particle and probe counts."""
+        nt, npr = self._mon_shape
+        return monitor_split(rows, nt, npr)
 
     def owned_ids(self) -> np.ndarray:
         """Original indices of the particles this context owns (all of them without a slab)."""
