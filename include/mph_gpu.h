@@ -231,7 +231,7 @@ int mph_step(MphCtx* ctx, int nsteps);
  * Steps still pending run, and the error flags of everything launched are read, at the next
  * flush point: mph_synchronize, mph_get, mph_set, every writer, mph_compute_virial,
  * mph_neighbor_stats, mph_profile_steps, mph_phase_timing, mph_monitor_configure, mph_monitor_read,
- * turning batching off, mph_destroy; so
+ * mph_sample_grid, turning batching off, mph_destroy; so
  * every field read after a step is that step's, bit for bit as without batching.  A launched
  * batch's error is also reported by a later mph_step once its flags have landed (no wait).
  * Errors therefore surface up to two batches late, or at the next flush point.  Off by default. */
@@ -357,6 +357,59 @@ int mph_monitor_sample_doubles(const MphCtx* ctx);
  * return how many.  The ring keeps the newest `capacity` samples: *lost (may be NULL) receives how
  * many unread samples were overwritten since the last read.  A flush point, like mph_get.        */
 long long mph_monitor_read(MphCtx* ctx, double* out, long long max_samples, long long* lost);
+
+/* ---- lattice sampling ------------------------------------------------------------------------- */
+
+/* Fields on a regular lattice without mph_get: the monitors' probe, evaluated on the device at every
+ * point of an axis-aligned lattice, on demand.  Point (i, j, k), i < count[0], j < count[1],
+ * k < count[2], lies at origin + (i spacing[0], j spacing[1], k spacing[2]) (each product and sum
+ * rounded, no contraction), wrapped into the periodic domain like a particle; points outside the
+ * domain are legal and wrap.  2-D: z is ignored and count[2] must be 1.
+ *
+ * Per point, over the particles j of the selected classes within `radius` h of it: r the exact FP64
+ * minimum-image distance to the position PressureP was computed at (the last step's sorted set: the
+ * wrapped position before that step's motion), w = (1 - r/h)^2 for r < h, and MPH_SAMPLE_CHANNELS
+ * doubles (MphSampleChannel): COUNT the contributing particles, WSUM = sum w (the fill level: 0 in
+ * empty space), P = sum w PressureP / sum w with the last step's PressureP, VX VY VZ = sum w v /
+ * sum w with v the velocity that step started from: what mph_get(MPH_FIELD_VELOCITY) returned
+ * before the step, except where the step's own preamble rewrites it first: the Turek_Hron inlet
+ * profile on its fluid particles, and calculateWall on the wall particles (their velocity and
+ * position are set from the wall motion before the sort; a static wall keeps its velocity 0 and its
+ * position to the last bit or two).  No contributor: all six are 0.
+ * out is [count[2]][count[1]][count[0]][MPH_SAMPLE_CHANNELS], i fastest.
+ * A point's six values depend only on the point, the radius, the class mask and the state -- not on
+ * the lattice around it -- and the same call gives the same bits again.                          */
+#define MPH_SAMPLE_CHANNELS   6
+#define MPH_SAMPLE_MAX_POINTS (1 << 24)
+typedef enum MphSampleChannel {
+    MPH_SAMPLE_COUNT = 0,
+    MPH_SAMPLE_WSUM = 1,
+    MPH_SAMPLE_P = 2,
+    MPH_SAMPLE_VX = 3,
+    MPH_SAMPLE_VY = 4,
+    MPH_SAMPLE_VZ = 5
+} MphSampleChannel;
+typedef struct MphSampleGrid {
+    double origin[3];
+    double spacing[3];     /* > 0 */
+    int count[3];          /* >= 1 each, count[0] count[1] count[2] <= MPH_SAMPLE_MAX_POINTS */
+    int classes;           /* bit mask: 1 fluid (types 0, 1), 2 structure (2, 3), 4 walls (4, 5); 0: fluid only */
+    double radius;         /* 0: RadiusRatioP * dx; must be <= MaxRadius + MARGIN (the cell stencil's reach) */
+} MphSampleGrid;           /* 72 bytes: origin 0, spacing 24, count 48, classes 60, radius 64 */
+/* Sample the lattice *g into host memory `out`.  A flush point like mph_get; it changes no state and
+ * touches no step graph.  MPH_ERR_ARG: no step since creation or since the last mph_set (the sorted
+ * set is not that state's), a count or spacing <= 0, more than MPH_SAMPLE_MAX_POINTS points, a radius
+ * below 0 or over the stencil's reach, class bits above 7, count[2] != 1 in 2-D.
+ * MPH_ERR_UNSUPPORTED: slab mode.  A context without particles gives zeros.                        */
+int mph_sample_grid(MphCtx* ctx, const MphSampleGrid* g, double* out);
+/* mph_sample_grid with the kernel timed through the profiler of mph_profile_steps: *kernel_ms (may
+ * be NULL) receives its duration from HIP events, name32 (32 chars, may be NULL) the name it was
+ * recorded under (empty where no kernel ran: a context without particles).                        */
+int mph_sample_grid_timed(MphCtx* ctx, const MphSampleGrid* g, double* out, double* kernel_ms, char* name32);
+/* VTK XML ImageData (.vti) of a sampled lattice, host only: WholeExtent 0 nx-1 0 ny-1 0 nz-1, Origin
+ * and Spacing of *g, Float64 point arrays Count, WSum, PressureP and Velocity (3 components) in raw
+ * appended data (UInt64 headers), the doubles as sampled.                                         */
+int mph_write_vti_arrays(const char* path, const MphSampleGrid* g, const double* out);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

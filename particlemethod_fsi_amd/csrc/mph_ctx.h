@@ -128,6 +128,12 @@ struct MphCtx {
     int *mon_sorted = nullptr, *mon_map = nullptr;
     double* mon_probes = nullptr;
     long long mon_read = 0;
+    // lattice sampling (mph_sample_grid): the device result buffer (allocated at the first call,
+    // regrown when a larger lattice arrives) and whether the sorted set A and pres are the current
+    // state's -- a step has run since creation and no mph_set since
+    double* sample_out = nullptr;
+    size_t sample_cap = 0;       // doubles the allocation holds
+    bool a_current = false;
     MphDist* dist = nullptr;     // non-null in slab mode
 };
 

@@ -742,6 +742,7 @@ static int step_batched(MphCtx* c, int nsteps)
 {
     for (int k = 0; k < nsteps; ++k) c->time += c->cfg.dt;
     c->stepped = true;
+    c->a_current = true;
     c->pending += nsteps;
     bool launched = false;
     MPH_CK(capture_graphs(c));
@@ -808,6 +809,7 @@ int mph_step(MphCtx* c, int nsteps)
     }
     for (int k = 0; k < nsteps; ++k) c->time += c->cfg.dt;
     c->stepped = true;
+    c->a_current = true;
     // the error flags, copied into pinned memory behind the steps (a pageable copy is staged by the
     // runtime).  Polling the stream instead of the blocking wait measured the same per call
     // (profiles/r05/sync_path/).
@@ -979,6 +981,7 @@ int mph_set(MphCtx* c, int field, const void* in)
     if (field != MPH_FIELD_POSITION && field != MPH_FIELD_VELOCITY)
         return ctx_fail(c, MPH_ERR_ARG, "mph_set supports Position and Velocity");
     MPH_HIP_OK(c, hipSetDevice(c->device));
+    c->a_current = false;   // the sorted set A is the last step's, no longer this state's (mph_sample_grid)
     const int n = c->n;
     const double* v = (const double*)in;
     // current state lives in the B set in the order of B.id: rewrite it in that order
@@ -1134,6 +1137,7 @@ int mph_profile_steps(MphCtx* c, int nsteps, double* avg_ms, int* launches, char
         MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
         for (int k = 0; k < nsteps; ++k) c->time += c->cfg.dt;
         c->stepped = true;
+        c->a_current = true;
     }
     std::vector<std::string> order;
     std::map<std::string, std::pair<double, int>> acc;
@@ -1496,6 +1500,79 @@ long long mph_monitor_read(MphCtx* c, double* out, long long max_samples, long l
     }
     c->mon_read = first + k;
     return k;
+}
+
+// ---- lattice sampling (kernel: mph_sample.hip) --------------------------------------------------
+
+// prof set: the kernel's launch is recorded by it (its events are read by the caller)
+static int sample_grid(MphCtx* c, const MphSampleGrid* g, double* out, Profiler* prof)
+{
+    if (!c || !g || !out) return MPH_ERR_ARG;
+    MPH_CK(ctx_flush(c));
+    if (c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "sampling is not available in slab mode (a lattice spans the ranks)");
+    long long points = 1;
+    for (int d = 0; d < 3; ++d) {
+        if (g->count[d] < 1 || !(g->spacing[d] > 0.0) || !std::isfinite(g->spacing[d]) || !std::isfinite(g->origin[d]))
+            return ctx_fail(c, MPH_ERR_ARG, "sample grid: counts must be >= 1, spacings > 0 and the origin finite");
+        points *= g->count[d];   // (at most 2^24 before each factor below 2^31)
+        if (points > MPH_SAMPLE_MAX_POINTS)
+            return ctx_fail(c, MPH_ERR_ARG, "sample grid: more than MPH_SAMPLE_MAX_POINTS = " +
+                                                std::to_string(MPH_SAMPLE_MAX_POINTS) + " points");
+    }
+    if (c->cfg.dim == 2 && g->count[2] != 1) return ctx_fail(c, MPH_ERR_ARG, "sample grid: count[2] must be 1 in 2-D");
+    if (g->classes < 0 || g->classes > 7) return ctx_fail(c, MPH_ERR_ARG, "sample grid: class mask outside 0..7");
+    const double reach = c->h.max_radius + 0.1 * c->h.dx;   // MaxRadius + MARGIN (make_dev_params)
+    if (!(g->radius >= 0.0) || g->radius > reach)
+        return ctx_fail(c, MPH_ERR_ARG, "sample grid: radius outside [0, MaxRadius + MARGIN = " + std::to_string(reach) + "]");
+    const size_t need = (size_t)points * MPH_SAMPLE_CHANNELS;
+    if (c->n == 0) {
+        std::memset(out, 0, sizeof(double) * need);
+        return MPH_OK;
+    }
+    if (!c->a_current)
+        return ctx_fail(c, MPH_ERR_ARG, "sample grid: run a step first (none since creation or since the last mph_set)");
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    if (need > c->sample_cap) {
+        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+        ctx_dfree(c, c->sample_out);
+        c->sample_out = nullptr;
+        c->sample_cap = 0;
+        MPH_CK(ctx_dalloc(c, &c->sample_out, need));
+        c->sample_cap = need;
+    }
+    SampleDev G{};
+    for (int d = 0; d < 3; ++d) {
+        G.origin[d] = g->origin[d];
+        G.spacing[d] = g->spacing[d];
+        G.count[d] = g->count[d];
+    }
+    G.mask = g->classes ? g->classes : 1;
+    G.h = g->radius > 0.0 ? g->radius : c->h.rp;
+    if (sample_tiling(G, contig_axis(c->P.dim, c->P.perm)) > 0x7fffffffLL) return ctx_fail(c, MPH_ERR_ARG, "sample grid: too many tiles");
+    Launch L = c->L;
+    L.prof = prof;
+    launch_sample_grid(L, G, c->sample_out);
+    MPH_HIP_OK(c, hipGetLastError());
+    MPH_HIP_OK(c, hipMemcpyAsync(out, c->sample_out, sizeof(double) * need, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    return MPH_OK;
+}
+
+int mph_sample_grid(MphCtx* c, const MphSampleGrid* g, double* out) { return sample_grid(c, g, out, nullptr); }
+
+int mph_sample_grid_timed(MphCtx* c, const MphSampleGrid* g, double* out, double* kernel_ms, char* name32)
+{
+    EventProfiler prof;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (name32) name32[0] = 0;
+    MPH_CK(sample_grid(c, g, out, &prof));
+    if (prof.recs.empty()) return MPH_OK;
+    float ms = 0.0f;
+    MPH_HIP_OK(c, hipEventElapsedTime(&ms, prof.recs[0].a, prof.recs[0].b));
+    if (kernel_ms) *kernel_ms = ms;
+    if (name32) std::snprintf(name32, 32, "%s", prof.recs[0].name.c_str());
+    return MPH_OK;
 }
 
 void mph_destroy(MphCtx* c)

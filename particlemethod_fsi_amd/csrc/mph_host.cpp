@@ -432,6 +432,50 @@ extern "C" int mph_write_vtu_arrays(const char* path, int n, const int* prop, co
     return ok ? MPH_OK : MPH_ERR_IO;
 }
 
+extern "C" int mph_write_vti_arrays(const char* path, const MphSampleGrid* g, const double* out)
+{
+    if (!path || !g || !out) return MPH_ERR_ARG;
+    for (int d = 0; d < 3; ++d)
+        if (g->count[d] < 1) return MPH_ERR_ARG;
+    const size_t N = (size_t)g->count[0] * g->count[1] * g->count[2];
+    // channel c0 (, c0 + 1, c0 + 2) of every point's record, in point order
+    struct Arr { const char* name; int ncomp, c0; };
+    const Arr pd[4] = {{"Count", 1, MPH_SAMPLE_COUNT}, {"WSum", 1, MPH_SAMPLE_WSUM}, {"PressureP", 1, MPH_SAMPLE_P},
+                       {"Velocity", 3, MPH_SAMPLE_VX}};
+    FILE* fp = std::fopen(path, "wb");
+    if (!fp) return MPH_ERR_IO;
+    std::fprintf(fp, "<?xml version=\"1.0\"?>\n<VTKFile type=\"ImageData\" version=\"1.0\" "
+                     "byte_order=\"LittleEndian\" header_type=\"UInt64\">\n");
+    // %.17g: Origin and Spacing read back as the doubles they were
+    std::fprintf(fp, "  <ImageData WholeExtent=\"0 %d 0 %d 0 %d\" Origin=\"%.17g %.17g %.17g\" Spacing=\"%.17g %.17g %.17g\">\n",
+                 g->count[0] - 1, g->count[1] - 1, g->count[2] - 1, g->origin[0], g->origin[1], g->origin[2],
+                 g->spacing[0], g->spacing[1], g->spacing[2]);
+    std::fprintf(fp, "    <Piece Extent=\"0 %d 0 %d 0 %d\">\n      <PointData Scalars=\"PressureP\" Vectors=\"Velocity\">\n",
+                 g->count[0] - 1, g->count[1] - 1, g->count[2] - 1);
+    uint64_t off = 0;
+    for (const Arr& a : pd) {
+        std::fprintf(fp, "        <DataArray type=\"Float64\" Name=\"%s\"", a.name);
+        if (a.ncomp > 1) std::fprintf(fp, " NumberOfComponents=\"%d\"", a.ncomp);
+        std::fprintf(fp, " format=\"appended\" offset=\"%llu\"/>\n", (unsigned long long)off);
+        off += sizeof(uint64_t) + sizeof(double) * a.ncomp * N;
+    }
+    std::fprintf(fp, "      </PointData>\n    </Piece>\n  </ImageData>\n  <AppendedData encoding=\"raw\">\n   _");
+    std::vector<double> buf;
+    for (const Arr& a : pd) {
+        const uint64_t nb = sizeof(double) * a.ncomp * N;
+        buf.resize(std::max<size_t>((size_t)a.ncomp * N, 1));
+        for (size_t p = 0; p < N; ++p)
+            for (int k = 0; k < a.ncomp; ++k) buf[a.ncomp * p + k] = out[MPH_SAMPLE_CHANNELS * p + a.c0 + k];
+        std::fwrite(&nb, sizeof(nb), 1, fp);
+        std::fwrite(buf.data(), 1, nb, fp);
+    }
+    std::fprintf(fp, "\n  </AppendedData>\n</VTKFile>\n");
+    std::fflush(fp);
+    const bool ok = !std::ferror(fp);
+    std::fclose(fp);
+    return ok ? MPH_OK : MPH_ERR_IO;
+}
+
 extern "C" int mph_derive_scalars(const MphConfig* cfg, double* out36)
 {
     if (!cfg || !out36 || (cfg->dim != 2 && cfg->dim != 3) || !(cfg->particle_spacing > 0.0)) return MPH_ERR_ARG;

@@ -137,8 +137,24 @@ struct Launch {
     const MonitorDev* mon = nullptr;   // monitors on: sampled at the end of every step
 };
 
+// Lattice sampling (mph_sample.hip, mph_sample_grid): the lattice, the wave tiling chosen for it
+// (sample_tiling) and the resolved radius and class mask, passed to the kernel by value.
+struct SampleDev {
+    double origin[3], spacing[3];
+    int count[3];
+    int tile[3];     // lattice points of one wave's tile per axis (powers of two, product <= 64)
+    int tiles[3];    // tiles per axis
+    int mask;        // classes summed: bit 0 fluid, 1 structure, 2 walls
+    double h;        // radius
+};
+
 int monitor_blocks(int n);   // blocks (partial records) of k_monitor_partial
 void launch_monitor(const Launch& L, const MonitorDev& M);
+// fills G.tile / G.tiles from G.count / G.spacing (run_axis: the contiguous cell axis); returns the
+// number of tiles (waves)
+long long sample_tiling(SampleDev& G, int run_axis);
+// the six channels of every lattice point into out ([nz][ny][nx][6], device); L.P->n > 0
+void launch_sample_grid(const Launch& L, const SampleDev& G, double* out);
 void launch_sort(const Launch& L, int mode);   // mode 0 init, 1 step, 2 step (motion done)
 void launch_neighbors(const Launch& L);
 void launch_pass_a(const Launch& L);

@@ -7,7 +7,8 @@
 // after a step (672-683).  Differences: the physics runs on MI355X through libmph_gpu.so;
 // the .prof holds the current state (the OpenACC build writes stale host arrays);
 // the timing report is wall time of the step loop, not clock() CPU time.  A <vtk pattern> ending
-// in ".vtu" writes binary VTK XML files instead (mph_write_vtu).
+// in ".vtu" writes binary VTK XML files instead (mph_write_vtu).  MPH_MONITOR and
+// MPH_SAMPLE add a time history and, per VTK output step, the fields on a lattice (below).
 //
 // Several GPUs: MPH_SLABS=N runs the same case as N slab ranks (include/mph_gpu.h, one process
 // per rank): the process forks N - 1 ranks before any HIP call, rank r takes device
@@ -303,6 +304,8 @@ int main(int argc, char** argv)
     if (nslabs > 1 && std::getenv("MPH_MONITOR"))   // (before any rank is started)
         die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_MONITOR with MPH_SLABS > 1 (monitors need a single context; "
                                          "the cross-rank reduction is not built yet)");
+    if (nslabs > 1 && std::getenv("MPH_SAMPLE"))
+        die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_SAMPLE with MPH_SLABS > 1 (sampling needs a single context)");
     if (nslabs > 1 && spawn_ranks(R, nslabs, host_transport) < 0) {
         std::fprintf(stderr, "error: could not start %d slab ranks\n", nslabs);
         return 1;
@@ -420,6 +423,31 @@ int main(int argc, char** argv)
         if (!mon.f) die(nullptr, MPH_ERR_IO, "opening the MPH_MONITOR file");
         monitor_header(mon);
     }
+    // MPH_SAMPLE="ox,oy,oz;sx,sy,sz;nx,ny,nz": at every VTK output step the fields are sampled on
+    // that lattice (include/mph_gpu.h mph_sample_grid; MPH_SAMPLE_RADIUS, MPH_SAMPLE_CLASSES
+    // optional) and written as VTK ImageData to MPH_SAMPLE_FILE, a printf pattern taking the .vtk
+    // files' index (default sample%03d.vti)
+    MphSampleGrid sgrid{};
+    std::vector<double> sbuf;
+    std::string sfile = "sample%03d.vti";
+    const bool sampling = std::getenv("MPH_SAMPLE") != nullptr;
+    if (sampling) {
+        const std::vector<double> v = parse_numbers(std::getenv("MPH_SAMPLE"));
+        if (v.size() != 9) die(nullptr, MPH_ERR_ARG, "MPH_SAMPLE (ox,oy,oz;sx,sy,sz;nx,ny,nz)");
+        double points = 1.0;
+        for (int d = 0; d < 3; ++d) {
+            sgrid.origin[d] = v[d];
+            sgrid.spacing[d] = v[3 + d];
+            if (!(v[6 + d] >= 1.0 && v[6 + d] <= MPH_SAMPLE_MAX_POINTS)) die(nullptr, MPH_ERR_ARG, "MPH_SAMPLE counts");
+            sgrid.count[d] = (int)v[6 + d];
+            points *= sgrid.count[d];
+        }
+        if (points > MPH_SAMPLE_MAX_POINTS) die(nullptr, MPH_ERR_ARG, "MPH_SAMPLE (too many points)");
+        if (const char* e = std::getenv("MPH_SAMPLE_RADIUS")) sgrid.radius = std::atof(e);
+        if (const char* e = std::getenv("MPH_SAMPLE_CLASSES")) sgrid.classes = std::atoi(e);
+        if (const char* e = std::getenv("MPH_SAMPLE_FILE")) sfile = e;
+        sbuf.resize((size_t)points * MPH_SAMPLE_CHANNELS);
+    }
     const auto loop_t0 = std::chrono::steady_clock::now();
     double time_now = cfg.time;
     int istep = (int)(time_now / dt);
@@ -473,6 +501,13 @@ int main(int argc, char** argv)
         loop_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         steps_run += k;
         for (int s = 0; s < k; ++s) {
+            if (vtk_after && s == k - 1 && sampling) {
+                rc = mph_sample_grid(ctx, &sgrid, sbuf.data());
+                if (rc) die(ctx, rc, "mph_sample_grid");
+                std::snprintf(name, sizeof(name), sfile.c_str(), istep);
+                rc = mph_write_vti_arrays(name, &sgrid, sbuf.data());
+                if (rc) die(ctx, rc, "writing a .vti file");
+            }
             if (vtk_after && s == k - 1) {
                 // main.cpp:672-673: the virial diagnostic runs before every VTK write
                 roctxRangePushA("virial");

@@ -1,0 +1,253 @@
+// mph_sample.hip -- lattice sampling (include/mph_gpu.h mph_sample_grid): the monitors' probe at
+// every point of an axis-aligned lattice, on demand.  k_monitor_probe gives a whole wavefront to one
+// point, right for 64 probes; here a lattice has up to 2^24 points, so every lane takes one point
+// and walks the probe's stencil itself: the stencil columns in the probe's order, each column's one
+// or two index ranges of start[] front to back.  A point's sums are therefore taken in an order
+// fixed by the point and the state alone -- no atomics, no cross-lane reduction -- and its six
+// values do not depend on the lattice around it or on the wave that holds it.
+//
+// Points to waves: a wave takes a tile of tile[0] x tile[1] x tile[2] lattice points (powers of
+// two, product <= 64; sample_tiling): a run along the contiguous cell axis where the lattice has
+// points along it -- its lanes share their stencil columns, which the wave then stages in LDS -- and
+// otherwise (a slice across that axis) a tile as compact in space as the lattice allows, whose lanes
+// walk nearly the same columns and read the same few lines of the 48-byte records, which the vector
+// L1 then serves.  Points many cells apart (every lane in another region) or many to a cell change
+// only which of the two ways a wave takes and what the caches see.  DESIGN.md section 11 has the
+// measurements, with the version that only walks.
+#include <hip/hip_runtime.h>
+
+#include "mph_device.h"
+#include "mph_kernels.h"
+#include "mph_params.h"
+
+namespace mph {
+
+// The tile of one wave, from one point up to 64 by doubling: first along the contiguous cell axis
+// `run_axis` while the lattice has more points along it than the tile (a run along it shares its
+// stencil columns); then the axis whose tile is shortest in space (ties: the lower axis), likewise.
+// A lattice of fewer than 64 points gets a smaller tile (the other lanes idle).
+long long sample_tiling(SampleDev& G, int run_axis)
+{
+    for (int d = 0; d < 3; ++d) G.tile[d] = 1;
+    int lanes = 1;
+    for (; lanes < 64 && G.tile[run_axis] < G.count[run_axis]; lanes *= 2) G.tile[run_axis] *= 2;
+    for (; lanes < 64; lanes *= 2) {
+        int best = -1;
+        for (int d = 0; d < 3; ++d)
+            if (G.tile[d] < G.count[d] &&
+                (best < 0 || G.tile[d] * G.spacing[d] < G.tile[best] * G.spacing[best]))
+                best = d;
+        if (best < 0) break;
+        G.tile[best] *= 2;
+    }
+    long long total = 1;
+    for (int d = 0; d < 3; ++d) {
+        G.tiles[d] = (G.count[d] + G.tile[d] - 1) / G.tile[d];
+        total *= G.tiles[d];
+    }
+    return total;
+}
+
+// A point's running sums, and one candidate's terms added to them; both kernels below add the same
+// terms in the same order, so they give the same bits.
+struct SampleAcc {
+    double cnt = 0.0, sw = 0.0, swp = 0.0, sv0 = 0.0, sv1 = 0.0, sv2 = 0.0;
+};
+
+// the lane's lattice point: its indices and its position wrapped into the periodic domain like a
+// particle (2-D: z is ignored); false for a lane without a point
+__device__ __forceinline__ bool sample_point(const SampleDev& G, const DevParams& P, int dim, long long tile, int lane,
+                                             size_t& pt, double (&p)[3])
+{
+#pragma clang fp contract(off)
+    const int t0 = (int)(tile % G.tiles[0]);
+    const int t1 = (int)((tile / G.tiles[0]) % G.tiles[1]);
+    const int t2 = (int)(tile / ((long long)G.tiles[0] * G.tiles[1]));
+    const int i = t0 * G.tile[0] + lane % G.tile[0];
+    const int j = t1 * G.tile[1] + (lane / G.tile[0]) % G.tile[1];
+    const int l2 = lane / (G.tile[0] * G.tile[1]);
+    const int k = t2 * G.tile[2] + l2;
+    if (l2 >= G.tile[2] || i >= G.count[0] || j >= G.count[1] || k >= G.count[2]) return false;
+    pt = ((size_t)k * G.count[1] + j) * G.count[0] + i;
+    const int ijk[3] = {i, j, k};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const double q = G.origin[d] + (double)ijk[d] * G.spacing[d];
+        p[d] = d < dim ? mod_exact(q - P.dmin[d], P.dw[d]) + P.dmin[d] : 0.0;
+    }
+    return true;
+}
+
+template <int DIM>
+__device__ __forceinline__ void sample_term(SampleAcc& a, const DevParams& P, const double (&p)[3], double h, int mask,
+                                            int t, double2 r0, double2 r1, double2 r2, double pj)
+{
+#pragma clang fp contract(off)
+    if ((unsigned)t >= (unsigned)kTypes || !((mask >> (t >> 1)) & 1)) return;
+    const double q0 = image_exact<false>(r0.x - p[0], P.dw[0], P.hw[0], P.w075[0]);
+    const double q1 = image_exact<false>(r0.y - p[1], P.dw[1], P.hw[1], P.w075[1]);
+    const double q2 = DIM == 3 ? image_exact<false>(r1.x - p[2], P.dw[2], P.hw[2], P.w075[2]) : 0.0;
+    const double r = sqrt(q0 * q0 + q1 * q1 + q2 * q2);
+    if (r < h) {
+        const double u = 1.0 - r / h;
+        const double w = u * u;
+        a.cnt += 1.0;
+        a.sw += w;
+        a.swp += w * pj;
+        a.sv0 += w * r1.y;
+        a.sv1 += w * r2.x;
+        a.sv2 += w * r2.y;
+    }
+}
+
+// the point's 48-byte record {COUNT, WSUM, P, VX, VY, VZ}; no contributor: zeros
+__device__ __forceinline__ void sample_store(double2* __restrict__ out, size_t pt, const SampleAcc& a)
+{
+#pragma clang fp contract(off)
+    const bool any = a.sw > 0.0;
+    out[3 * pt] = make_double2(a.cnt, a.sw);
+    out[3 * pt + 1] = make_double2(any ? a.swp / a.sw : 0.0, any ? a.sv0 / a.sw : 0.0);
+    out[3 * pt + 2] = make_double2(any ? a.sv1 / a.sw : 0.0, any ? a.sv2 / a.sw : 0.0);
+}
+
+// The stencil of k_monitor_probe around the cell (cx, cy, cz): kReach cells across the column axes
+// a0 (, a1), P.sa cells along the contiguous axis ca -- the same cells for every column: one range
+// [lo, hi], a second one [lo1, hi1] where the stencil wraps.
+template <int DIM> struct SampleStencil {
+    int ca, a0, a1, c[3], lo, hi, lo1, hi1;
+    static constexpr int ncol = DIM == 3 ? kGroups * kGroups : kGroups;
+    __device__ __forceinline__ SampleStencil(const DevParams& P, const double (&p)[3])
+    {
+        c[0] = cell_axis(p[0], P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
+        c[1] = cell_axis(p[1], P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
+        c[2] = DIM == 3 ? cell_axis(p[2], P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
+        ca = contig_axis(DIM, P.perm);
+        a0 = DIM == 3 ? (ca == 0 ? 1 : 0) : 0;
+        a1 = DIM == 3 ? (ca == 2 ? 1 : 2) : -1;
+        const int cc = ca == 0 ? c[0] : (ca == 1 ? c[1] : c[2]), g = ca == 0 ? P.gc[0] : (ca == 1 ? P.gc[1] : P.gc[2]);
+        lo = cc - P.sa; hi = cc + P.sa; lo1 = 0; hi1 = -1;
+        if (hi - lo + 1 >= g) { lo = 0; hi = g - 1; }
+        else if (lo < 0) { lo1 = lo + g; hi1 = g - 1; lo = 0; }
+        else if (hi >= g) { lo1 = 0; hi1 = hi - g; hi = g - 1; }
+    }
+    // column col's first cell: cell (.., m along ca, ..) is column(col) + m, the contiguous axis
+    // being the fastest of cell_index
+    __device__ __forceinline__ int column(const DevParams& P, int col) const
+    {
+        const int d0 = (DIM == 3 ? col / kGroups : col) - kReach, d1 = DIM == 3 ? col % kGroups - kReach : 0;
+        int q[3] = {c[0], c[1], c[2]};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            if (d == a0) q[d] = wrap_cell(q[d] + d0, P.gc[d]);
+            else if (d == a1) q[d] = wrap_cell(q[d] + d1, P.gc[d]);
+        }
+        return cell_index(P, ca == 0 ? 0 : q[0], ca == 1 ? 0 : q[1], ca == 2 ? 0 : q[2]);
+    }
+};
+
+// a lane walks its point's whole stencil through global memory
+template <int DIM>
+__device__ __forceinline__ void sample_walk(SampleAcc& acc, const DevParams& P, const SampleStencil<DIM>& S,
+                                            const double (&p)[3], double h, int mask, int n, const Soa& A,
+                                            const int* __restrict__ start, const double* __restrict__ pres)
+{
+    for (int col = 0; col < SampleStencil<DIM>::ncol; ++col) {
+        const int cell0 = S.column(P, col);
+        for (int run = 0; run < 2; ++run) {
+            if (run == 1 && S.hi1 < S.lo1) break;
+            const int b = start[cell0 + (run ? S.lo1 : S.lo)];
+            const int e = start[cell0 + (run ? S.hi1 : S.hi) + 1];
+            for (int q = b < 0 ? 0 : b; q < e && q < n; ++q)
+                sample_term<DIM>(acc, P, p, h, mask, A.type[q], A.p6[3 * (size_t)q], A.p6[3 * (size_t)q + 1],
+                                 A.p6[3 * (size_t)q + 2], pres[q]);
+        }
+    }
+}
+
+// One wave per block.  Where the wave's points share their stencil columns -- the same cells across
+// the column axes, no wrap along the contiguous one: a run of points along that axis, or many points
+// in one cell -- each column's window, the union of the lanes' ranges, is staged in LDS 64 records
+// at a time with coalesced loads, as k_neighbors stages its windows, and every lane tests its own
+// sub-range of what is staged, in index order.  The lanes of any other wave walk their stencils
+// themselves.  Both ways add the same terms in the same order.
+constexpr int kSampleStage = 64;   // records staged at a time: one per lane
+template <int DIM>
+__global__ __launch_bounds__(64) void k_sample_grid(DevParams P, SampleDev G, int n, Soa A,
+                                                    const int* __restrict__ start, const double* __restrict__ pres,
+                                                    double2* __restrict__ out)
+{
+    __shared__ double2 s_r[3][kSampleStage];
+    __shared__ double s_p[kSampleStage];
+    __shared__ int s_t[kSampleStage];
+    const int lane = threadIdx.x;
+    const long long tile = blockIdx.x;
+    size_t pt = 0;
+    double p[3] = {0.0, 0.0, 0.0};
+    const bool active = sample_point(G, P, DIM, tile, lane, pt, p);
+    if (!__any(active)) return;
+    const SampleStencil<DIM> S(P, p);
+    SampleAcc acc;
+    // the first active lane's column cells; do all active lanes share them, none wrapping along ca?
+    const int first = __ffsll((unsigned long long)__ballot(active)) - 1;
+    const int k0 = S.a0 == 0 ? S.c[0] : S.c[1], k1 = S.a1 < 0 ? 0 : (S.a1 == 1 ? S.c[1] : S.c[2]);
+    const bool same = k0 == __shfl(k0, first, 64) && k1 == __shfl(k1, first, 64) && S.hi1 < S.lo1;
+    if (!__all(same || !active)) {
+        if (active) {
+            sample_walk<DIM>(acc, P, S, p, G.h, G.mask, n, A, start, pres);
+            sample_store(out, pt, acc);
+        }
+        return;
+    }
+    // the window of the wave along ca
+    int wlo = active ? S.lo : 0x7fffffff, whi = active ? S.hi : -1;
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        wlo = min(wlo, __shfl_xor(wlo, m, 64));
+        whi = max(whi, __shfl_xor(whi, m, 64));
+    }
+    // (every lane's stencil has the first active lane's column cells: inactive lanes take its whole
+    // stencil so that column() is the same in all of them)
+    SampleStencil<DIM> W = S;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) W.c[d] = __shfl(S.c[d], first, 64);
+    for (int col = 0; col < SampleStencil<DIM>::ncol; ++col) {
+        const int cell0 = W.column(P, col);
+        const int wb = max(start[cell0 + wlo], 0), we = min(start[cell0 + whi + 1], n);
+        int b = 0, e = 0;
+        if (active) {
+            b = max(start[cell0 + S.lo], 0);
+            e = min(start[cell0 + S.hi + 1], n);
+        }
+        for (int base = wb; base < we; base += kSampleStage) {
+            const int m = min(kSampleStage, we - base);
+            __syncthreads();
+            if (lane < m) {
+                const size_t q = (size_t)(base + lane);
+                s_r[0][lane] = A.p6[3 * q];
+                s_r[1][lane] = A.p6[3 * q + 1];
+                s_r[2][lane] = A.p6[3 * q + 2];
+                s_p[lane] = pres[q];
+                s_t[lane] = A.type[q];
+            }
+            __syncthreads();
+            const int qe = min(e, base + m);
+            for (int q = max(b, base); q < qe; ++q) {
+                const int t = q - base;
+                sample_term<DIM>(acc, P, p, G.h, G.mask, s_t[t], s_r[0][t], s_r[1][t], s_r[2][t], s_p[t]);
+            }
+        }
+    }
+    if (active) sample_store(out, pt, acc);
+}
+
+void launch_sample_grid(const Launch& L, const SampleDev& G, double* out)
+{
+    const DevParams& P = *L.P;
+    const long long ntiles = (long long)G.tiles[0] * G.tiles[1] * G.tiles[2];
+    by_dim(P.dim, [&](auto D) {
+        launch(L.prof, "sample_grid", L.stream, k_sample_grid<decltype(D)::value>, dim3((unsigned)ntiles), dim3(64), P,
+               G, P.n, L.A, L.start, L.pres, (double2*)out);
+    });
+}
+
+}  // namespace mph

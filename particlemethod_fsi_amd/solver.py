@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "mph_list_stats", "mph_abi_version", "mph_phase_timing", "mph_phase_times",
     "mph_set_step_batching", "mph_neighbor_rows", "mph_dist_overlap", "mph_list_layout",
     "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
+    "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -82,6 +83,26 @@ class MphMonitorConfig(ctypes.Structure):
     _fields_ = [("stride", ctypes.c_int), ("capacity", ctypes.c_int), ("ntrack", ctypes.c_int),
                 ("track", ctypes.c_void_p), ("nprobe", ctypes.c_int), ("probes", ctypes.c_void_p),
                 ("probe_radius", ctypes.c_double)]
+
+
+class MphSampleGrid(ctypes.Structure):
+    """include/mph_gpu.h MphSampleGrid."""
+    _fields_ = [("origin", ctypes.c_double * 3), ("spacing", ctypes.c_double * 3), ("count", ctypes.c_int * 3),
+                ("classes", ctypes.c_int), ("radius", ctypes.c_double)]
+
+
+# MphSampleChannel (include/mph_gpu.h): name -> index into a lattice point's record
+SAMPLE_CHANNELS = {"COUNT": 0, "WSUM": 1, "P": 2, "VX": 3, "VY": 4, "VZ": 5}
+SAMPLE_MAX_POINTS = 1 << 24
+SAMPLE_CLASSES = {"fluid": 1, "structure": 2, "walls": 4}
+
+
+def _sample_grid(origin, spacing, count, radius=0.0, classes=0) -> MphSampleGrid:
+    g = MphSampleGrid()
+    for d in range(3):
+        g.origin[d], g.spacing[d], g.count[d] = float(origin[d]), float(spacing[d]), int(count[d])
+    g.classes, g.radius = int(classes), float(radius)
+    return g
 
 
 # MphMonitorSlot (include/mph_gpu.h): name -> index into a sample's head
@@ -196,11 +217,15 @@ def load_library() -> ctypes.CDLL:
         "mph_monitor_configure": (ip, [vp, ctypes.POINTER(MphMonitorConfig)]),
         "mph_monitor_sample_doubles": (ip, [vp]),
         "mph_monitor_read": (ctypes.c_longlong, [vp, vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
+        "mph_sample_grid": (ip, [vp, ctypes.POINTER(MphSampleGrid), vp]),
+        "mph_sample_grid_timed": (ip, [vp, ctypes.POINTER(MphSampleGrid), vp, ctypes.POINTER(ctypes.c_double), vp]),
+        "mph_write_vti_arrays": (ip, [ctypes.c_char_p, ctypes.POINTER(MphSampleGrid), vp]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
                 "mph_dist_overlap", "mph_profile_graphs", "mph_list_stats", "mph_list_layout",
-                "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read"}
+                "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
+                "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -262,6 +287,38 @@ def read_vtu(path: str) -> dict:
         a = np.frombuffer(data[off + 8:off + 8 + nb], dt[attrs[b"type"].decode()])
         k = int(attrs.get(b"NumberOfComponents", b"1"))
         out[attrs.get(b"Name", b"Points").decode()] = a.reshape(-1, k) if k > 1 else a
+    return out
+
+
+def write_vti(path: str, out: np.ndarray, origin, spacing, radius: float = 0.0, classes: int = 0):
+    """VTK ImageData (.vti) of a sampled lattice (mph_write_vti_arrays): `out` as MphSolver.sample_grid
+    returns it, shape (nz, ny, nx, 6), with the lattice's origin and spacing."""
+    a = np.ascontiguousarray(out, np.float64)
+    if a.ndim != 4 or a.shape[3] != len(SAMPLE_CHANNELS):
+        raise ValueError("write_vti: an array of shape (nz, ny, nx, %d) expected" % len(SAMPLE_CHANNELS))
+    g = _sample_grid(origin, spacing, a.shape[2::-1], radius, classes)
+    _check(load_library().mph_write_vti_arrays(path.encode(), ctypes.byref(g), a.ctypes.data))
+
+
+def read_vti(path: str) -> dict:
+    """A .vti written by mph_write_vti_arrays: {name: ndarray of shape (nz, ny, nx) or (nz, ny, nx, 3)}
+    plus 'origin', 'spacing' (3 floats each) and 'extent' (6 ints)."""
+    import re
+    raw = open(path, "rb").read()
+    head, _, data = raw.partition(b'<AppendedData encoding="raw">')
+    data = data[data.index(b"_") + 1:]
+    img = dict(re.findall(rb'(\w+)="([^"]*)"', re.search(rb"<ImageData ([^>]*)>", head).group(1)))
+    ext = [int(v) for v in img[b"WholeExtent"].split()]
+    out = {"origin": [float(v) for v in img[b"Origin"].split()], "spacing": [float(v) for v in img[b"Spacing"].split()],
+           "extent": ext}
+    shape = (ext[5] - ext[4] + 1, ext[3] - ext[2] + 1, ext[1] - ext[0] + 1)
+    for m in re.finditer(rb"<DataArray ([^>]*)/>", head):
+        attrs = dict(re.findall(rb'(\w+)="([^"]*)"', m.group(1)))
+        off = int(attrs[b"offset"])
+        nb = int(np.frombuffer(data[off:off + 8], np.uint64)[0])
+        a = np.frombuffer(data[off + 8:off + 8 + nb], {"Float64": np.float64}[attrs[b"type"].decode()])
+        k = int(attrs.get(b"NumberOfComponents", b"1"))
+        out[attrs[b"Name"].decode()] = a.reshape(shape + (k,)) if k > 1 else a.reshape(shape)
     return out
 
 
@@ -532,6 +589,32 @@ class MphSolver:
         """monitor_split(rows, ...) with this solver's tracked-particle and probe counts."""
         nt, npr = self._mon_shape
         return monitor_split(rows, nt, npr)
+
+    # -- lattice sampling -------------------------------------------------------------------------
+    def sample_grid(self, origin, spacing, count, radius: float = 0.0, classes: int = 0, timed: bool = False,
+                    out: np.ndarray | None = None):
+        """mph_sample_grid: the fields at the points origin + (i sx, j sy, k sz) of a lattice of
+        count = (nx, ny, nz) points, evaluated on the device -> array of shape (nz, ny, nx, 6), the
+        channels SAMPLE_CHANNELS (COUNT, WSUM = the fill level, P, VX, VY, VZ): Shepard averages over
+        the particles of `classes` (bit mask SAMPLE_CLASSES, 0: fluid) within `radius` (0:
+        RadiusRatioP dx) of each point.  Needs a step since creation / the last set(); a flush point.
+        timed: (array, kernel milliseconds from HIP events, the kernel's profiler name).
+        out: a C-contiguous float64 array of that shape to fill instead of a new one."""
+        g = _sample_grid(origin, spacing, count, radius, classes)
+        shape = (max(int(count[2]), 0), max(int(count[1]), 0), max(int(count[0]), 0), len(SAMPLE_CHANNELS))
+        n = shape[0] * shape[1] * shape[2]
+        if out is None:
+            out = np.zeros(shape if 0 < n <= SAMPLE_MAX_POINTS else (1, 1, 1, len(SAMPLE_CHANNELS)))
+        elif out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError("sample_grid: out must be a C-contiguous float64 array of shape %r" % (shape,))
+        if not timed:
+            _check(self._L.mph_sample_grid(self._h, ctypes.byref(g), out.ctypes.data), self._h)
+            return out
+        ms = ctypes.c_double(0.0)
+        name = ctypes.create_string_buffer(32)
+        _check(self._L.mph_sample_grid_timed(self._h, ctypes.byref(g), out.ctypes.data, ctypes.byref(ms),
+                                             ctypes.addressof(name)), self._h)
+        return out, ms.value, name.value.decode()
 
     def owned_ids(self) -> np.ndarray:
         """Original indices of the particles this context owns (all of them without a slab)."""
