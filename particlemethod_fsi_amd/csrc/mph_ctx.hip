@@ -446,7 +446,7 @@ static int init_alloc(MphCtx* c, const CreateArgs& a)
     MPH_CK(ctx_dalloc(c, &c->L.tmp, cap));
     MPH_CK(ctx_dalloc(c, &c->L.cnt, c->P.ncell)); MPH_CK(ctx_dalloc(c, &c->L.start, (size_t)c->P.ncell + 1));
     // the cell scan's block totals (k_scan_reduce; structure init)
-    const size_t bs = (size_t)c->P.ncell / 4096 + 2;   // bsum_stride (mph_kernels.hip)
+    const size_t bs = (size_t)c->P.ncell / 4096 + 2;   // bsum_stride (mph_sort.hip)
     MPH_CK(ctx_dalloc(c, &c->L.bsum, bs));
     MPH_CK(ctx_dalloc(c, &c->L.nbr, ntile * kTileStride)); MPH_CK(ctx_dalloc(c, &c->L.ncount, cap));
     MPH_CK(ctx_dalloc(c, &c->L.nbcount, cap));

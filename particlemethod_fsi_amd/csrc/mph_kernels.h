@@ -1,4 +1,7 @@
-// mph_kernels.h -- launch interface of the HIP kernels (mph_kernels.hip) used by mph_ctx.hip.
+// mph_kernels.h -- launch interface of the hand-written HIP/CDNA4 (gfx950) kernels of the MPH explicit
+// hot path, the one host-visible interface of the kernel units (mph_sort.hip, mph_search.hip,
+// mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip, mph_sample.hip), used by mph_ctx.hip
+// and mph_dist.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -119,7 +122,7 @@ struct Launch {
     // ncount: each list's rows (what the passes walk); nbcount: NeighborCount (every neighbour within
     // the search radius; the lists keep only r^2 <= DevParams.rlf)
     int *nbr = nullptr, *ncount = nullptr, *nbcount = nullptr;
-    // the row jumps of the lists (mph_kernels.hip RowMask): one header word per wave, one word of gap
+    // the row jumps of the lists (mph_list.h RowMask): one header word per wave, one word of gap
     // starts per particle; ncount counts rows, gaps included
     unsigned long long *lhdr = nullptr, *lgap = nullptr;
     int* wface = nullptr;         // slab mode: face-wavefront flags written by pass B (early send)
@@ -147,6 +150,41 @@ struct SampleDev {
     int mask;        // classes summed: bit 0 fluid, 1 structure, 2 walls
     double h;        // radius
 };
+
+// One time step of the reference (main.cpp:597-686) is mapped onto these launches:
+//
+//   k_prep           calculateWall (3031-3071) + calculatePeriodicBoundary (3322-3333) + cell key
+//                    + cell histogram (first half of the counting sort that replaces the
+//                    reference's bitonic sort, 1683-1708)
+//   k_scan_*         exclusive scan of the cell histogram -> cell start offsets (1711-1728)
+//   k_place          scatter particle ids into their cells (unordered) + Time/WallCenter advance
+//   k_rank_scatter   deterministic in-cell rank (by previous sorted index) and particle reorder
+//   k_neighbors      linked-cell search (1743-1810): 7x7(x5) stencil (2 kReach + 1 columns of cells
+//                    >= rc/3, 2 kContigReach + 1 cells >= rc/2 along the contiguous axis), the
+//                    reference's exact FP64 acceptance test, ELL neighbour list per wavefront
+//   k_pass_a         the pass-A sums over the list: DensityA (2141), GravityCenter (2174), DensityP
+//                    (2314), DivergenceP (2343), PhysicalCoefficients (2099), pressure values
+//                    PressureP (2384) / PressureA (2218)
+//   k_pass_b         PressureP force (2394), PressureA force (2225), DiffuseInterface (2261),
+//                    ViscosityV (2478), InterfaceForce (2427), Gravity (2917), Acceleration (2938),
+//                    Convection (1892)
+//   k_struct_*       elastic substeps: DeformationVector (2673) + Stress (2756) -> PK1 stress;
+//                    StressForce (2812) in gather form + updateElasticPosition (1910); pass B
+//                    hands the structure particles to them and the last substep writes back
+//
+// One unit per phase: mph_sort.hip (k_prep ... k_rank_scatter), mph_search.hip (k_neighbors),
+// mph_passes.hip (k_pass_a, k_pass_b, k_virial), mph_elastic.hip (k_struct_*, and k_sinit_* at
+// creation), mph_slab.hip (the slab decomposition's k_dist_*, k_halo_*, k_struct_pack / _unpack).  What
+// two or more units share is in mph_device.h and, for the neighbour lists' layout, mph_list.h.
+//
+// All arithmetic is FP64.  Neighbour membership and every per-kernel radius test reproduce the
+// reference's FP64 expressions bit for bit (no contraction, IEEE division), so NeighborCount is
+// exact; the weighted sums are reassociated (own order, FMA) and agree within the tolerances
+// written in tests/.
+//
+// Memory layout: particle state is structure-of-arrays FP64 in cell-sorted order (Soa).  The
+// neighbour loops are bound by the per-CU texture-address path (profiles/r01: TA ~75% busy with
+// 32-byte records); SoA makes consecutive lanes gather consecutive doubles.
 
 int monitor_blocks(int n);   // blocks (partial records) of k_monitor_partial
 void launch_monitor(const Launch& L, const MonitorDev& M);

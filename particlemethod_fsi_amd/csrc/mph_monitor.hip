@@ -206,40 +206,20 @@ __global__ __launch_bounds__(64) void k_monitor_probe(DevParams P, MonitorDev M,
     constexpr int kSeg = 128;   // two runs per lane
     __shared__ int s_off[kSeg], s_beg[kSeg];
     const int q = blockIdx.x, lane = threadIdx.x;
-    // the probe, wrapped into the periodic domain like a particle (2-D: z is ignored)
-    const double px = mod_exact(M.probes[3 * q] - P.dmin[0], P.dw[0]) + P.dmin[0];
-    const double py = mod_exact(M.probes[3 * q + 1] - P.dmin[1], P.dw[1]) + P.dmin[1];
-    const double pz = DIM == 3 ? mod_exact(M.probes[3 * q + 2] - P.dmin[2], P.dw[2]) + P.dmin[2] : 0.0;
-    const int cx = cell_axis(px, P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
-    const int cy = cell_axis(py, P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
-    const int cz = DIM == 3 ? cell_axis(pz, P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
-    // the stencil of k_sinit_search: kReach cells across the column axes a0 (, a1), P.sa along the
-    // contiguous axis ca
-    const int ca = contig_axis(DIM, P.perm);
-    const int a0 = DIM == 3 ? (ca == 0 ? 1 : 0) : 0;
-    const int a1 = DIM == 3 ? (ca == 2 ? 1 : 2) : -1;
-    const int ncol = DIM == 3 ? kGroups * kGroups : kGroups;
-    const int d0 = (DIM == 3 ? lane / kGroups : lane) - kReach, d1 = DIM == 3 ? lane % kGroups - kReach : 0;
+    // the probe, wrapped into the periodic domain like a particle
+    const double pq[3] = {M.probes[3 * q], M.probes[3 * q + 1], DIM == 3 ? M.probes[3 * q + 2] : 0.0};
+    double p[3];
+    wrap_point(P, DIM, pq, p);
+    // lane c's column of the probe's stencil: one run of start[], two where the column wraps
+    const PointStencil<DIM> S(P, p);
     int b0 = 0, len0 = 0, b1 = 0, len1 = 0;
-    if (lane < ncol) {
-        int c[3] = {cx, cy, cz};
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if (d == a0) c[d] = wrap_cell(c[d] + d0, P.gc[d]);
-            else if (d == a1) c[d] = wrap_cell(c[d] + d1, P.gc[d]);
-        }
-        const int cc = ca == 0 ? cx : (ca == 1 ? cy : cz), g = ca == 0 ? P.gc[0] : (ca == 1 ? P.gc[1] : P.gc[2]);
-        // cell (.., k along ca, ..) is cell0 + k: the contiguous axis is the fastest of cell_index
-        const int cell0 = cell_index(P, ca == 0 ? 0 : c[0], ca == 1 ? 0 : c[1], ca == 2 ? 0 : c[2]);
-        int lo = cc - P.sa, hi = cc + P.sa, lo1 = 0, hi1 = -1;
-        if (hi - lo + 1 >= g) { lo = 0; hi = g - 1; }
-        else if (lo < 0) { lo1 = lo + g; hi1 = g - 1; lo = 0; }
-        else if (hi >= g) { lo1 = 0; hi1 = hi - g; hi = g - 1; }
-        b0 = start[cell0 + lo];
-        len0 = start[cell0 + hi + 1] - b0;
-        if (hi1 >= lo1) {
-            b1 = start[cell0 + lo1];
-            len1 = start[cell0 + hi1 + 1] - b1;
+    if (lane < PointStencil<DIM>::ncol) {
+        const int cell0 = S.column(P, lane);
+        b0 = start[cell0 + S.lo];
+        len0 = start[cell0 + S.hi + 1] - b0;
+        if (S.hi1 >= S.lo1) {
+            b1 = start[cell0 + S.lo1];
+            len1 = start[cell0 + S.hi1 + 1] - b1;
         }
     }
     // exclusive offsets of the runs
@@ -267,13 +247,8 @@ __global__ __launch_bounds__(64) void k_monitor_probe(DevParams P, MonitorDev M,
         const int j = s_beg[s] + (t - s_off[s]);
         if (j < 0 || j >= n) continue;
         if (A.type[j] >= 2) continue;
-        const double q0 = image_exact<false>(A.x[j] - px, P.dw[0], P.hw[0], P.w075[0]);
-        const double q1 = image_exact<false>(A.y[j] - py, P.dw[1], P.hw[1], P.w075[1]);
-        const double q2 = DIM == 3 ? image_exact<false>(A.z[j] - pz, P.dw[2], P.hw[2], P.w075[2]) : 0.0;
-        const double r = sqrt(q0 * q0 + q1 * q1 + q2 * q2);
-        if (r < h) {
-            const double u = 1.0 - r / h;
-            const double w = u * u;
+        double w;
+        if (shepard_weight<DIM>(P, p, h, A.x[j], A.y[j], DIM == 3 ? A.z[j] : 0.0, w)) {
             swp += w * pres[j];
             sw += w;
             cnt += 1.0;

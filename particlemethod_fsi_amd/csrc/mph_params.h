@@ -1,5 +1,5 @@
 // mph_params.h -- plain-old-data structures shared by the host layer (mph_host.cpp) and the
-// HIP kernels (mph_kernels.hip).  No HIP types here, so the host files build with g++/hipcc alike.
+// HIP kernels (mph_kernels.h).  No HIP types here, so the host files build with g++/hipcc alike.
 #pragma once
 #include <cmath>
 
@@ -209,7 +209,7 @@ struct DevState {
     int seam_occ[2];
     int seam_step;
     int seam_pad;
-    // work-balanced XCD map of the two list passes (mph_kernels.hip, list_block): the search adds
+    // work-balanced XCD map of the two list passes (mph_list.h, list_block): the search adds
     // each wave's work (its longest list + a fixed cost) into seg_work[its 1/kXcdSegs of the waves];
     // the next step's k_rank_scatter turns that into the XCDs' contiguous block ranges (xcd_frac:
     // fractions of 2^16, 0 ... 65536) for the passes and clears seg_work
@@ -226,7 +226,7 @@ constexpr size_t kStateHead = offsetof(DevState, seg_work);
 #define MPH_HD
 #endif
 
-// The lists' row jumps (kAlignRows above; mph_kernels.hip RowMask), decoded alike by the kernels and
+// The lists' row jumps (kAlignRows above; mph_list.h RowMask), decoded alike by the kernels and
 // the host readers: byte 7 of a wave's header word is its jump count J; gap k < J of a lane is the
 // rows [byte k of the lane's gap word, byte k of the header).
 MPH_HD inline int jump_count(unsigned long long hdr) { return (int)(hdr >> 56); }

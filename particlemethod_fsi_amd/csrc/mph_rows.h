@@ -8,7 +8,7 @@
 
 namespace mph {
 
-// The lists' rows as the last search left them (mph_kernels.hip RowMask): per particle (sorted
+// The lists' rows as the last search left them (mph_list.h RowMask): per particle (sorted
 // order) its rows [0, rows[s]) and, per wave, the row jumps (jump_count / gap_begin / gap_end).
 struct HostRows {
     std::vector<int> rows;

@@ -69,12 +69,9 @@ __device__ __forceinline__ bool sample_point(const SampleDev& G, const DevParams
     const int k = t2 * G.tile[2] + l2;
     if (l2 >= G.tile[2] || i >= G.count[0] || j >= G.count[1] || k >= G.count[2]) return false;
     pt = ((size_t)k * G.count[1] + j) * G.count[0] + i;
-    const int ijk[3] = {i, j, k};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const double q = G.origin[d] + (double)ijk[d] * G.spacing[d];
-        p[d] = d < dim ? mod_exact(q - P.dmin[d], P.dw[d]) + P.dmin[d] : 0.0;
-    }
+    const double q[3] = {G.origin[0] + (double)i * G.spacing[0], G.origin[1] + (double)j * G.spacing[1],
+                         G.origin[2] + (double)k * G.spacing[2]};
+    wrap_point(P, dim, q, p);
     return true;
 }
 
@@ -84,13 +81,8 @@ __device__ __forceinline__ void sample_term(SampleAcc& a, const DevParams& P, co
 {
 #pragma clang fp contract(off)
     if ((unsigned)t >= (unsigned)kTypes || !((mask >> (t >> 1)) & 1)) return;
-    const double q0 = image_exact<false>(r0.x - p[0], P.dw[0], P.hw[0], P.w075[0]);
-    const double q1 = image_exact<false>(r0.y - p[1], P.dw[1], P.hw[1], P.w075[1]);
-    const double q2 = DIM == 3 ? image_exact<false>(r1.x - p[2], P.dw[2], P.hw[2], P.w075[2]) : 0.0;
-    const double r = sqrt(q0 * q0 + q1 * q1 + q2 * q2);
-    if (r < h) {
-        const double u = 1.0 - r / h;
-        const double w = u * u;
+    double w;
+    if (shepard_weight<DIM>(P, p, h, r0.x, r0.y, r1.x, w)) {
         a.cnt += 1.0;
         a.sw += w;
         a.swp += w * pj;
@@ -110,48 +102,13 @@ __device__ __forceinline__ void sample_store(double2* __restrict__ out, size_t p
     out[3 * pt + 2] = make_double2(any ? a.sv1 / a.sw : 0.0, any ? a.sv2 / a.sw : 0.0);
 }
 
-// The stencil of k_monitor_probe around the cell (cx, cy, cz): kReach cells across the column axes
-// a0 (, a1), P.sa cells along the contiguous axis ca -- the same cells for every column: one range
-// [lo, hi], a second one [lo1, hi1] where the stencil wraps.
-template <int DIM> struct SampleStencil {
-    int ca, a0, a1, c[3], lo, hi, lo1, hi1;
-    static constexpr int ncol = DIM == 3 ? kGroups * kGroups : kGroups;
-    __device__ __forceinline__ SampleStencil(const DevParams& P, const double (&p)[3])
-    {
-        c[0] = cell_axis(p[0], P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
-        c[1] = cell_axis(p[1], P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
-        c[2] = DIM == 3 ? cell_axis(p[2], P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
-        ca = contig_axis(DIM, P.perm);
-        a0 = DIM == 3 ? (ca == 0 ? 1 : 0) : 0;
-        a1 = DIM == 3 ? (ca == 2 ? 1 : 2) : -1;
-        const int cc = ca == 0 ? c[0] : (ca == 1 ? c[1] : c[2]), g = ca == 0 ? P.gc[0] : (ca == 1 ? P.gc[1] : P.gc[2]);
-        lo = cc - P.sa; hi = cc + P.sa; lo1 = 0; hi1 = -1;
-        if (hi - lo + 1 >= g) { lo = 0; hi = g - 1; }
-        else if (lo < 0) { lo1 = lo + g; hi1 = g - 1; lo = 0; }
-        else if (hi >= g) { lo1 = 0; hi1 = hi - g; hi = g - 1; }
-    }
-    // column col's first cell: cell (.., m along ca, ..) is column(col) + m, the contiguous axis
-    // being the fastest of cell_index
-    __device__ __forceinline__ int column(const DevParams& P, int col) const
-    {
-        const int d0 = (DIM == 3 ? col / kGroups : col) - kReach, d1 = DIM == 3 ? col % kGroups - kReach : 0;
-        int q[3] = {c[0], c[1], c[2]};
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if (d == a0) q[d] = wrap_cell(q[d] + d0, P.gc[d]);
-            else if (d == a1) q[d] = wrap_cell(q[d] + d1, P.gc[d]);
-        }
-        return cell_index(P, ca == 0 ? 0 : q[0], ca == 1 ? 0 : q[1], ca == 2 ? 0 : q[2]);
-    }
-};
-
 // a lane walks its point's whole stencil through global memory
 template <int DIM>
-__device__ __forceinline__ void sample_walk(SampleAcc& acc, const DevParams& P, const SampleStencil<DIM>& S,
+__device__ __forceinline__ void sample_walk(SampleAcc& acc, const DevParams& P, const PointStencil<DIM>& S,
                                             const double (&p)[3], double h, int mask, int n, const Soa& A,
                                             const int* __restrict__ start, const double* __restrict__ pres)
 {
-    for (int col = 0; col < SampleStencil<DIM>::ncol; ++col) {
+    for (int col = 0; col < PointStencil<DIM>::ncol; ++col) {
         const int cell0 = S.column(P, col);
         for (int run = 0; run < 2; ++run) {
             if (run == 1 && S.hi1 < S.lo1) break;
@@ -185,7 +142,7 @@ __global__ __launch_bounds__(64) void k_sample_grid(DevParams P, SampleDev G, in
     double p[3] = {0.0, 0.0, 0.0};
     const bool active = sample_point(G, P, DIM, tile, lane, pt, p);
     if (!__any(active)) return;
-    const SampleStencil<DIM> S(P, p);
+    const PointStencil<DIM> S(P, p);
     SampleAcc acc;
     // the first active lane's column cells; do all active lanes share them, none wrapping along ca?
     const int first = __ffsll((unsigned long long)__ballot(active)) - 1;
@@ -207,10 +164,10 @@ __global__ __launch_bounds__(64) void k_sample_grid(DevParams P, SampleDev G, in
     }
     // (every lane's stencil has the first active lane's column cells: inactive lanes take its whole
     // stencil so that column() is the same in all of them)
-    SampleStencil<DIM> W = S;
+    PointStencil<DIM> W = S;
 #pragma unroll
     for (int d = 0; d < 3; ++d) W.c[d] = __shfl(S.c[d], first, 64);
-    for (int col = 0; col < SampleStencil<DIM>::ncol; ++col) {
+    for (int col = 0; col < PointStencil<DIM>::ncol; ++col) {
         const int cell0 = W.column(P, col);
         const int wb = max(start[cell0 + wlo], 0), we = min(start[cell0 + whi + 1], n);
         int b = 0, e = 0;

@@ -393,7 +393,7 @@ def test_boid_parser_refuses_what_the_generator_would_drop(bad, msg):
 
 def test_search_uncounted_loads_land_before_use(tmp_path):
     """The search issues its start[] loads in inline asm, which hipcc does not count
-    (mph_kernels.hip start_load2): on every control-flow path from such a load to the next
+    (mph_search.hip start_load2): on every control-flow path from such a load to the next
     s_waitcnt vmcnt(0) no instruction may read, copy or overwrite its destination register
     (tools/asm_load_audit.py over the gfx950 assembly of every k_neighbors instantiation)."""
     import shutil
@@ -404,7 +404,7 @@ def test_search_uncounted_loads_land_before_use(tmp_path):
     csrc = os.path.join(ROOT, "particlemethod_fsi_amd", "csrc")
     asm = str(tmp_path / "kernels.s")
     subprocess.run([hipcc, "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "--offload-arch=gfx950",
-                    "-munsafe-fp-atomics", "--cuda-device-only", "-S", os.path.join(csrc, "mph_kernels.hip"),
+                    "-munsafe-fp-atomics", "--cuda-device-only", "-S", os.path.join(csrc, "mph_search.hip"),
                     "-o", asm], check=True, capture_output=True, timeout=600)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "asm_load_audit.py"), asm, "k_neighbors"],
                        capture_output=True, text=True, timeout=300)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Audit of uncounted asm loads (mph_kernels.hip start_load) in a gfx950 assembly listing: from
+"""Audit of uncounted asm loads (mph_search.hip start_load2) in a gfx950 assembly listing: from
 every `buffer_load_dword vN ... offen` between ;;#ASMSTART/;;#ASMEND, walk every control-flow path
 until an `s_waitcnt vmcnt(0)`; any other instruction that names vN on the way reads (or copies,
 or overwrites) the register before the load has landed -- a bug (cdna_hip_programming.md 5.7).

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Bitwise A/B of two builds (e.g. the round-6 cleanup against e6081fe): run each case for a
 few steps with the library of MPH_GPU_LIB and save every per-particle field, or compare two saved
-runs.
+runs.  `run` also saves, whatever the cases, what the point stencil of the monitors' probes and of the
+lattice sampling produces (POINT_RUNS): the monitor ring of 11 steps with probes and tracked particles,
+and a lattice slice and a small volume.
 
   MPH_GPU_LIB=.../libmph_gpu.so python tools/lib_bitwise.py run OUT.npz [cases...]
   python tools/lib_bitwise.py compare A.npz B.npz        (exit 1 on any difference)
@@ -18,9 +20,42 @@ FIELDS = ["Position", "Velocity", "PressureP", "PressureA", "NeighborCount", "Fo
           "DensityA", "VolStrainP", "DivergenceP", "GravityCenter", "DeformGradient", "Strain", "Stress"]
 
 
+# case -> (probes, tracked ids, lattices (origin, spacing, count, classes)): the probes of
+# tests/test_gpu_monitor.py test_probes_in_a_tank and test_probe_across_the_periodic_face, a 2-D set,
+# and per case a lattice slice and a small volume (seam3d's across the periodic y face)
+POINT_RUNS = {
+    "box3d_jit": ([(0.00613, 0.01021, 0.00587), (0.00587, 0.01957, 0.00611), (0.00071, 0.00813, 0.00493),
+                   (0.0353, 0.0421, 0.0061)], [3, 0, 1500, 3],
+                  [((0.0005, 0.0035, 0.006), (0.0007, 0.0007, 0.0007), (20, 30, 1), 0),
+                   ((0.0005, 0.0035, 0.0005), (0.0011, 0.0013, 0.0012), (12, 10, 9), 7)]),
+    "seam3d": ([(0.01531, 0.03931, 0.01013)], [7],
+               [((0.014, 0.0, 0.0101), (0.0009, 0.0008, 0.0009), (7, 50, 1), 0),
+                ((0.014, 0.036, 0.009), (0.0009, 0.0009, 0.0009), (6, 8, 5), 0)]),
+    "dam2d": ([(0.0213, 0.0417, 0.0), (0.0007, 0.0513, 0.0), (0.1, 0.3, 0.0)], [11, 2000],
+              [((0.001, 0.004, 0.0), (0.0013, 0.0017, 0.001), (40, 60, 1), 0),
+               ((-0.002, 0.001, 0.0), (0.0009, 0.0009, 0.001), (9, 7, 1), 7)]),
+}
+
+
+def run_points(res):
+    from particlemethod_fsi_amd import MphSolver, cases
+    for name, (probes, track, lattices) in POINT_RUNS.items():
+        cfg, parts = cases.get(name).build()
+        with MphSolver(cfg, parts) as s:
+            s.monitor(stride=1, capacity=16, track=track, probes=probes)
+            s.step(3)
+            s.step(8)
+            rows, lost = s.monitor_read()
+            assert rows.shape[0] == 11 and lost == 0, (rows.shape, lost)
+            res["%s/monitor_ring" % name] = rows
+            for k, (origin, spacing, count, classes) in enumerate(lattices):
+                res["%s/sample_grid%d" % (name, k)] = s.sample_grid(origin, spacing, count, classes=classes)
+
+
 def run(out, names):
     from particlemethod_fsi_amd import MphSolver, cases
     res = {}
+    run_points(res)
     for name in names:
         cfg, parts = cases.get(name).build()
         with MphSolver(cfg, parts) as s:

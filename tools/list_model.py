@@ -1,4 +1,4 @@
-"""Numpy model of the D1M neighbour lists (cell geometry of csrc/mph_kernels.hip): per sampled
+"""Numpy model of the D1M neighbour lists (cell geometry of csrc/mph_search.hip): per sampled
 wavefront, the stencil-column window spans and the lane efficiency of column-by-column lockstep vs
 ELL lockstep, for the compact-list experiment recorded in DESIGN.md section 4.  CPU only, ~5 min."""
 import sys, numpy as np
