@@ -1,4 +1,5 @@
-"""Worker processes of the slab-decomposition tests (tests/test_dist_cpu.py, test_gpu_dist.py).
+"""Worker processes of the slab-decomposition tests (tests/test_dist_cpu.py, test_gpu_dist.py, the
+slab tests of test_gpu_developed.py and test_gpu_d16m.py) and run_ranks, which launches them.
 
 Each worker is one rank: it joins a gloo process group on 127.0.0.1 and either runs a GPU slab
 context (host-staged transport over gloo, several ranks sharing one GPU) or, on CPU, exercises
@@ -17,6 +18,33 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SLAB_AXIS = {"channel3d": 2, "channel3d_st": 2, "channel2d": 0, "dam2d": 0, "box3d": 0,
              "bar2d": 0, "bar3d": 0, "gate2d_sub": 0}
+
+
+def _free_port():
+    import socket
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def run_ranks(target, world, *args, timeout):
+    """Run `target(rank, world, port, *args)` as `world` spawned processes, one per rank, on a free
+    port; wait up to `timeout` seconds for each, kill what is still alive, and assert that every rank
+    exited with 0.  Each rank is started once: a rank that died is reported, not rerun."""
+    import multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    port = _free_port()
+    ps = [ctx.Process(target=target, args=(r, world, port) + args) for r in range(world)]
+    for p in ps:
+        p.start()
+    for p in ps:
+        p.join(timeout)
+    for p in ps:
+        if p.is_alive():
+            p.kill()
+            p.join()
+    codes = [p.exitcode for p in ps]
+    assert all(c == 0 for c in codes), "rank exit codes %s" % codes
 
 
 def _init(rank, world, port):

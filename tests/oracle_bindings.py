@@ -183,6 +183,11 @@ class OracleSolver:
         return self._lib.orc_time(self.h)
 
 
+def use_oracle_threads():
+    """The thread count of the oracle in the large tests: the machine's cores, at most 16."""
+    OracleSolver.set_threads(min(16, os.cpu_count() or 1))
+
+
 def write_case_files(cfg_text: str, grid_text: str, tmpdir: str | None = None):
     d = tmpdir or tempfile.mkdtemp(prefix="mphcase_")
     dp, gp = os.path.join(d, "case.data"), os.path.join(d, "case.grid")

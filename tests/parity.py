@@ -1,0 +1,228 @@
+"""The parity bounds of the GPU path: the one place where the numbers live.
+
+Every GPU test that compares FP64 fields against the reference's golden vectors, the CPU oracle or
+another GPU run takes its bound from `bound` (or `golden_bound`) and asserts through `assert_close`
+(or `assert_close_golden`).  NeighborCount and the other integer fields are always bit-exact.
+tests/test_parity_bounds.py pins the numbers of this module on the CPU.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+# absolute floors: the roundoff level of each quantity (P ~ Kappa * VolStrainP, so one ulp of
+# VolStrainP ~ 1e-16 is 1e-12 Pa; at step 1 the reference's P is itself pure roundoff ~4e-11)
+# Elastic tensors: at rest F = I + O(ulp), so Strain is pure roundoff (~1e-16) and Stress ~
+# (lambda + 2 mu) * 1e-15 ~ 1e-10 Pa until gravity loads the solid.
+FLOOR = {"PressureP": 1e-9, "PressureA": 1e-9, "Force": 1e-15, "Acceleration": 1e-12,
+         "VolStrainP": 1e-13, "DivergenceP": 1e-12, "DensityA": 1e-13, "GravityCenter": 1e-16,
+         "DeformGradient": 1e-13, "Strain": 1e-13, "Stress": 1e-8,
+         "VirialStressAtParticle": 1e-9, "VirialPressureAtParticle": 1e-9}
+
+# Relative bounds, as a fraction of the largest magnitude of the reference field.
+# One step, the goldens and the bar2d long run (where the reference does not amplify roundoff,
+# tests/golden/ulp_bar2d_longrun.json): the GPU sums in its own order with FMA; reassociation only.
+REL_ONE_STEP = 1e-9
+# Fluid against the oracle (or against another decomposition of the same run) over several steps:
+# SURVEY 8c measured the chaotic growth of such differences.
+REL_STEPS = 1e-8
+# A case that holds elastic particles (types 2/3): the solid runs at dt*c/dx = 0.95 (ElasticDt 1e-4,
+# c = 9.5 m/s); near the stability limit reassociation differences grow ~10x per few steps, and the
+# fluid next to it inherits them.
+REL_ELASTIC = 1e-7
+# DivergenceP in such a case -- a difference of nearly equal sums: the growth one GPU context itself
+# shows against the oracle on bar3d (tools/slab_diag.py: 8.9e-9 / 9.7e-8 / 7.4e-7 at steps 10 / 20 /
+# 30).
+REL_ELASTIC_DIVP = 1e-6
+
+
+def elastic_rel(field: str) -> float:
+    """Relative bound of `field` over tens of steps of a case with elastic particles."""
+    return REL_ELASTIC_DIVP if field == "DivergenceP" else REL_ELASTIC
+
+
+def bound(field: str, rel: float, scale: float) -> float:
+    """THE bound rule: positions 1e-12 m, velocities 1e-9 m/s, any other float field `rel` of
+    `scale` (the largest magnitude of the reference) plus the field's roundoff floor."""
+    if field == "Position":
+        return 1e-12
+    if field == "Velocity":
+        return 1e-9
+    return rel * scale + FLOOR.get(field, 1e-12)
+
+
+def golden_bound(field: str, step: int, scale: float) -> float:
+    """The bound against the reference's golden vectors after `step` steps: up to 100 steps the
+    rule above at REL_ONE_STEP, PressureP past the first step at 1e-8; at 1000 steps positions
+    1e-10 m (dx = 1e-3 m), velocities 1e-7 m/s and PressureP 1e-6."""
+    long = step >= 1000
+    if long and field in ("Position", "Velocity"):
+        return {"Position": 1e-10, "Velocity": 1e-7}[field]
+    if field == "PressureP" and step > 1:
+        return bound(field, 1e-6 if long else 1e-8, scale)
+    return bound(field, REL_ONE_STEP, scale)
+
+
+def _assert_within(field, got, ref, bound_of_scale, rows, scale, extra, context):
+    if rows is not None:
+        got, ref = got[rows], ref[rows]
+    if ref.dtype.kind != "f":
+        if not np.array_equal(got, ref):
+            raise AssertionError("%s %s: %d mismatches" % (context, field, int((got != ref).sum())))
+        return 0
+    # no nanmax, no NaN mask: a NaN on either side makes `err <= t` false
+    err = float(np.max(np.abs(got - ref))) if ref.size else 0.0
+    if scale is None:
+        scale = float(np.max(np.abs(ref))) if ref.size else 0.0
+    t = max(bound_of_scale(scale), extra)
+    if not err <= t:
+        raise AssertionError("%s %s: max|diff| %.3e > bound %.3e" % (context, field, err, t))
+    return err
+
+
+def assert_close(field, got, ref, rel, *, rows=None, scale=None, extra=0.0, context=()):
+    """Assert `got` within bound(field, rel, scale) of `ref`; integer fields bit-exact.  Returns
+    the measured max|got - ref| (0 for integers).
+
+    rows:    a mask or index applied to both arrays first.  No row left is error 0, scale 0.
+    scale:   None scales by the compared rows, max|ref[rows]|; a number is taken as given (a
+             rank's rows against a bound scaled by the whole reference array).
+    extra:   a further absolute allowance, combined by max (the reference's own measured
+             sensitivity, test_gpu_fullsize).
+    context: goes into the failure message in front of the field, error and bound."""
+    return _assert_within(field, got, ref, lambda s: bound(field, rel, s), rows, scale, extra, context)
+
+
+def assert_close_golden(field, got, ref, step, *, context=()):
+    """assert_close under golden_bound; the NaN slots of the golden `ref` (entries the reference
+    leaves uninitialised) are skipped -- those of `ref` only, a NaN from the device fails."""
+    rows = ~np.isnan(ref) if ref.dtype.kind == "f" else None
+    return _assert_within(field, got, ref, lambda s: golden_bound(field, step, s), rows, None, 0.0,
+                          context + (step,))
+
+
+def compare(g, solver, step: int):
+    """Every field the golden file of case `g` stores at `step` against the solver's."""
+    from golden_utils import restrict
+    report = {}
+    if g.has(step, "VirialStressAtParticle"):
+        solver.compute_virial()   # the reference's VTK-step diagnostic, main.cpp:672-673
+    for f in g.fields(step):
+        ref = g.get(step, f)
+        err = assert_close_golden(f, restrict(g, f, solver.get(f)), ref, step, context=(g.case,))
+        if ref.dtype.kind == "f":
+            report[f] = err
+    return report
+
+
+def oracle_rel(parts) -> float:
+    """Relative bound of the per-step sums against the oracle: REL_ELASTIC where the case holds
+    elastic particles, else REL_STEPS."""
+    solid = (parts.property >= 2) & (parts.property < 4)
+    return REL_ELASTIC if solid.any() else REL_STEPS
+
+
+def check_fields_against_oracle(s, o, parts, k):
+    """One step's state against the oracle's: NeighborCount bit-exact, every field within
+    bound(f, oracle_rel(parts)) (k: the step, for the failure message)."""
+    solid = (parts.property >= 2) & (parts.property < 4)
+    rel = oracle_rel(parts)
+    assert_close("NeighborCount", s.get("NeighborCount"), o.get("NeighborCount"), rel, context=(k,))
+    for f in ["Position", "Velocity", "Force", "PressureP", "VolStrainP", "DivergenceP",
+              "DensityA", "GravityCenter", "Acceleration"]:
+        rows = ~solid if f in ("DensityA", "GravityCenter") else None
+        if rows is not None and not rows.any():   # an all-solid case (bar3d): no row of these two is defined
+            continue
+        assert_close(f, s.get(f), o.get(f), rel, rows=rows, context=(k,))
+    if solid.any():
+        for f in ["DeformGradient", "Stress", "Strain"]:
+            assert_close(f, s.get(f), o.get(f), REL_STEPS, rows=solid, context=(k,))
+
+
+def check_virial_against_oracle(s, o, parts, k):
+    """The virial diagnostic of the current state against the oracle's."""
+    rel = oracle_rel(parts)
+    s.compute_virial()
+    o.call("calculateVirialStressAtParticle")
+    for f in ["VirialStressAtParticle", "VirialPressureAtParticle"]:
+        assert_close(f, s.get(f), o.get(f), rel, context=(k,))
+
+
+def run_against_oracle_every_step(cfg, parts, nsteps):
+    """Step-by-step against the oracle: NeighborCount and all fields after every step, the virial
+    after the last."""
+    from oracle_bindings import OracleSolver
+    from particlemethod_fsi_amd import MphSolver
+    o = OracleSolver(cfg, parts)
+    o.init()
+    with MphSolver(cfg, parts) as s:
+        for k in range(nsteps):
+            s.step(1)
+            o.step(1)
+            check_fields_against_oracle(s, o, parts, k)
+            if k == nsteps - 1:
+                check_virial_against_oracle(s, o, parts, k)
+
+
+def check_rank_files(out_dir, world, n, ref, ref_time, fields, rel=REL_STEPS):
+    """The rank<r>.npz files of `world` slab ranks (dist_worker.gpu_rank_worker / gpu_state_worker)
+    against one context's `ref` fields over all `n` particles: every rank's time equals ref_time,
+    its owned rows lie within the bound SCALED BY THE WHOLE REFERENCE ARRAY (one bound for all
+    ranks, whichever rows a rank owns), and ownership is a partition.  Returns the owner of every
+    particle at the ranks' creation (-1 where the files do not record it) and at the end."""
+    scale = {f: float(np.max(np.abs(ref[f]))) for f in fields if ref[f].dtype.kind == "f"}
+    seen = np.zeros(n, np.int32)
+    owner0 = np.full(n, -1, np.int32)
+    owner1 = np.full(n, -1, np.int32)
+    for r in range(world):
+        z = np.load(os.path.join(str(out_dir), "rank%d.npz" % r))
+        ids = z["ids"]
+        if "ids0" in z.files:
+            owner0[z["ids0"]] = r
+        owner1[ids] = r
+        seen[ids] += 1
+        assert float(z["time"][0]) == ref_time, (r, float(z["time"][0]), ref_time)
+        for f in fields:
+            assert_close(f, z[f], ref[f][ids], rel, scale=scale.get(f), context=(r,))
+    assert (seen == 1).all(), "ownership is not a partition: %d missing, %d duplicated" % (
+        int((seen == 0).sum()), int((seen > 1).sum()))
+    return owner0, owner1
+
+
+CHUNK_FIELDS = ["Position", "Velocity", "Force", "Acceleration", "GravityCenter", "PressureP",
+                "PressureA", "DensityA", "VolStrainP", "DivergenceP", "NeighborCount", "Kappa",
+                "DeformGradient", "Strain", "Stress"]
+
+
+def check_structure_init_equals_host_build(case, monkeypatch):
+    """The structure lists built on the device against the host build: see
+    test_gpu_structure_init_equals_host_build."""
+    import ctypes
+    from particlemethod_fsi_amd import MphSolver, cases, solver
+    cfg, parts = cases.get(case).build()
+    n = parts.n
+    isnc = np.zeros(n, np.int32)
+    nrm = np.zeros((n, 3, 3))
+    ll, lm = np.zeros(n), np.zeros(n)
+    prop = np.ascontiguousarray(parts.property, np.int32)
+    x0 = np.ascontiguousarray(parts.initial_position)
+    assert solver.load_library().mph_structure_init(ctypes.byref(cfg), n, prop.ctypes.data, x0.ctypes.data,
+                                                    isnc.ctypes.data, nrm.ctypes.data, ll.ctypes.data,
+                                                    lm.ctypes.data) == 0
+    outs = []
+    for mode in ("device", "host"):
+        if mode == "host":
+            monkeypatch.setenv("MPH_STRUCT_INIT", "host")
+        with MphSolver(cfg, parts) as s:
+            got = {f: s.get(f) for f in ("InitialStructureNeighborCount", "Normalizer", "LambdaLames", "MuLames")}
+            s.step(5)
+            got["Position"] = s.get("Position")
+            got["Stress"] = s.get("Stress")
+            outs.append(got)
+    dev, host = outs
+    assert np.array_equal(dev["InitialStructureNeighborCount"], isnc)
+    assert np.array_equal(dev["Normalizer"], nrm)
+    assert np.array_equal(dev["LambdaLames"], ll) and np.array_equal(dev["MuLames"], lm)
+    for f in dev:
+        assert np.array_equal(dev[f], host[f]), f

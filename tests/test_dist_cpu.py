@@ -1,10 +1,6 @@
 """CPU tests of the multi-GPU slab decomposition (no device): slab geometry of the library's
 host functions, and world-size 2/3 gloo runs of the neighbour exchange routing and of the
 halo-band rule (every reference neighbour of an owned particle is owned or a received ghost)."""
-import multiprocessing as mp
-import os
-import socket
-
 import numpy as np
 import pytest
 
@@ -13,24 +9,8 @@ from particlemethod_fsi_amd import cases, solver
 import dist_worker
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _spawn(target, world, *args):
-    ctx = mp.get_context("spawn")
-    port = _free_port()
-    ps = [ctx.Process(target=target, args=(r, world, port) + args) for r in range(world)]
-    for p in ps:
-        p.start()
-    for p in ps:
-        p.join(180)
-    for p in ps:
-        if p.is_alive():
-            p.kill()
-    assert all(p.exitcode == 0 for p in ps), [p.exitcode for p in ps]
+    dist_worker.run_ranks(target, world, *args, timeout=180)
 
 
 @pytest.mark.parametrize("case,axis", [("channel3d", 2), ("d1m", 2), ("dam2d", 0)])

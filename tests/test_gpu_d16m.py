@@ -12,29 +12,21 @@ single-context run, which the smaller parity tests pin to the oracle:
 2. the 8-way z-slab decomposition that the driver's 8-GPU job runs (8 ranks sharing the one test
    GPU, host-staged transport) against the single context after 3 steps: ownership is a partition
    of all particles, NeighborCount exact, positions 1e-12 m, velocities 1e-9 m/s, PressureP
-   1e-8 relative + 1e-9 Pa (the slabs' local cell grids order neighbour sums differently).
+   1e-8 relative + 1e-9 Pa (the slabs' local cell grids order neighbour sums differently;
+   parity.check_rank_files, REL_STEPS of the whole array's max).
 """
-import multiprocessing as mp
-import socket
-
 import numpy as np
 import pytest
 
 from particlemethod_fsi_amd import MphSolver, cases
 
 import dist_worker
+from parity import check_rank_files
 
 pytestmark = pytest.mark.gpu
 
 STEPS = 3
 FIELDS = ["Position", "Velocity", "PressureP", "NeighborCount", "VolStrainP", "DivergenceP"]
-FLOOR = {"PressureP": 1e-9, "VolStrainP": 1e-13, "DivergenceP": 1e-12}
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _single(nsteps):
@@ -93,34 +85,7 @@ def test_d16m_slab8_matches_single_context(tmp_path):
     """The 8-slab configuration of bench.py --gpus 8 (slab-local creation, cuts at the
     particle-count quantiles) against one context over all 16.2M particles."""
     world = 8
-    ctx = mp.get_context("spawn")
-    port = _free_port()
-    ps = [ctx.Process(target=dist_worker.gpu_rank_worker,
-                      args=(r, world, port, "d16m", 2, STEPS, FIELDS, str(tmp_path), "host", "balanced"))
-          for r in range(world)]
-    for p in ps:
-        p.start()
-    for p in ps:
-        p.join(900)
-    for p in ps:
-        if p.is_alive():
-            p.kill()
-    assert all(p.exitcode == 0 for p in ps), [p.exitcode for p in ps]
+    dist_worker.run_ranks(dist_worker.gpu_rank_worker, world, "d16m", 2, STEPS, FIELDS, str(tmp_path), "host",
+                          "balanced", timeout=900)
     cfg, n, ref = _single(STEPS)
-    seen = np.zeros(n, np.int32)
-    for r in range(world):
-        z = np.load(str(tmp_path / ("rank%d.npz" % r)))
-        ids = z["ids"]
-        assert float(z["time"][0]) == ref["time"]
-        seen[ids] += 1
-        for f in FIELDS:
-            a, b = z[f], ref[f][ids]
-            if f == "NeighborCount":
-                assert np.array_equal(a, b), (r, f, int((a != b).sum()))
-                continue
-            err = float(np.max(np.abs(a - b))) if len(ids) else 0.0
-            t = {"Position": 1e-12, "Velocity": 1e-9}.get(
-                f, 1e-8 * float(np.max(np.abs(ref[f]))) + FLOOR.get(f, 1e-12))
-            assert err <= t, (r, f, err, t)
-    assert (seen == 1).all(), "ownership is not a partition: %d missing, %d duplicated" % (
-        int((seen == 0).sum()), int((seen > 1).sum()))
+    check_rank_files(tmp_path, world, n, ref, ref["time"], FIELDS)

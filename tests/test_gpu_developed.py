@@ -12,31 +12,29 @@ handed to the CPU oracle, bit-identical to the reference, as the reference's own
 
   * NeighborCount exact; the neighbour SETS of sample ranges (mph_neighbor_rows of a context built
     from the state with the reference's whole lists) equal to the oracle's lists (main.cpp:1764-1772);
-  * Position 1e-12 m, Velocity 1e-9 m/s, PressureP / VolStrainP / DivergenceP / Force within 1e-8 of
-    their largest magnitude plus the roundoff floors of test_gpu_parity.py;
+  * Position 1e-12 m, Velocity 1e-9 m/s, PressureP / VolStrainP / DivergenceP / Force within
+    REL_STEPS of their largest magnitude plus their roundoff floors (tests/parity.py);
   * the state did leave the lattice: NeighborCount differs from the creation's for >= 1 % of the
     particles, and the fluid front moved by more than 10 dx.
 """
-import multiprocessing as mp
 import os
-import socket
 
 import numpy as np
 import pytest
 
+from parity import REL_STEPS, assert_close, check_rank_files
 from particlemethod_fsi_amd import MphSolver, cases, mphio
 
 pytestmark = pytest.mark.gpu
 
-FLOOR = {"PressureP": 1e-9, "Force": 1e-15, "VolStrainP": 1e-13, "DivergenceP": 1e-12}
 DEVELOPED_STEPS = 2500           # t = 0.25 s at Dt = 1e-4
 SAMPLE_ROWS = [(0, 4000), (485000, 4000), (966000, 4000), (1200000, 4000)]   # fluid (3) and wall
 
 
 @pytest.mark.parametrize("steps", [DEVELOPED_STEPS, 10000])   # t = 0.25 s, and t = 1.0 s: the reference's whole Dam run
 def test_d1m_developed_matches_oracle(steps):
-    from oracle_bindings import OracleSolver
-    OracleSolver.set_threads(min(16, os.cpu_count() or 1))
+    from oracle_bindings import OracleSolver, use_oracle_threads
+    use_oracle_threads()
     cfg, parts = cases.get("d1m").build()
     fluid = parts.property < 2
     with MphSolver(cfg, parts) as s:
@@ -75,11 +73,7 @@ def test_d1m_developed_matches_oracle(steps):
             done = k
             assert np.array_equal(s.get("NeighborCount"), o.get("NeighborCount")), k
             for f in ["Position", "Velocity", "PressureP", "VolStrainP", "DivergenceP", "Force"]:
-                a, b = s.get(f), o.get(f)
-                scale = float(np.max(np.abs(b)))
-                t = {"Position": 1e-12, "Velocity": 1e-9}.get(f, 1e-8 * scale + FLOOR.get(f, 1e-12))
-                err = float(np.max(np.abs(a - b)))
-                assert err <= t, (k, f, err, t)
+                assert_close(f, s.get(f), o.get(f), REL_STEPS, context=(k,))
         assert s.time == o.time
 
 
@@ -92,8 +86,9 @@ def test_d1m_developed_slab8_matches_single_context(tmp_path):
     into the 8 z slabs of bench.py --gpus 8 (8 ranks sharing the test GPU, host-staged transport;
     every rank created from the whole state, equal cuts) against one context started from the same
     state, 10 steps: ownership a partition of all particles, NeighborCount exact, positions 1e-12 m,
-    velocities 1e-9 m/s, the sums 1e-8 relative + the floors above -- and particles did migrate
-    between slabs (owner at the end differs from the owner at creation)."""
+    velocities 1e-9 m/s, the sums REL_STEPS of the whole array's max + their floors
+    (parity.check_rank_files) -- and particles did migrate between slabs (owner at the end differs
+    from the owner at creation)."""
     import dist_worker
     world, steps = 8, 10
     cfg, parts = cases.get("d1m").build()
@@ -110,43 +105,9 @@ def test_d1m_developed_slab8_matches_single_context(tmp_path):
         s.step(steps)
         ref = {f: s.get(f) for f in SLAB_FIELDS}
         ref_time = s.time
-    ctx = mp.get_context("spawn")
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    ps = [ctx.Process(target=dist_worker.gpu_state_worker,
-                      args=(r, world, port, "d1m", state, 2, steps, SLAB_FIELDS, str(tmp_path)))
-          for r in range(world)]
-    for p in ps:
-        p.start()
-    for p in ps:
-        p.join(600)
-    for p in ps:
-        if p.is_alive():
-            p.kill()
-    assert all(p.exitcode == 0 for p in ps), [p.exitcode for p in ps]
-    n = parts.n
-    seen = np.zeros(n, np.int32)
-    owner0 = np.full(n, -1, np.int32)
-    owner1 = np.full(n, -1, np.int32)
-    for r in range(world):
-        z = np.load(str(tmp_path / ("rank%d.npz" % r)))
-        ids = z["ids"]
-        owner0[z["ids0"]] = r
-        owner1[ids] = r
-        seen[ids] += 1
-        assert float(z["time"][0]) == ref_time
-        for f in SLAB_FIELDS:
-            a, b = z[f], ref[f][ids]
-            if f == "NeighborCount":
-                assert np.array_equal(a, b), (r, f, int((a != b).sum()))
-                continue
-            err = float(np.max(np.abs(a - b))) if len(ids) else 0.0
-            tol = {"Position": 1e-12, "Velocity": 1e-9}.get(
-                f, 1e-8 * float(np.max(np.abs(ref[f]))) + FLOOR.get(f, 1e-12))
-            assert err <= tol, (r, f, err, tol)
-    assert (seen == 1).all(), "ownership is not a partition: %d missing, %d duplicated" % (
-        int((seen == 0).sum()), int((seen > 1).sum()))
+    dist_worker.run_ranks(dist_worker.gpu_state_worker, world, "d1m", state, 2, steps, SLAB_FIELDS, str(tmp_path),
+                          timeout=600)
+    owner0, owner1 = check_rank_files(tmp_path, world, parts.n, ref, ref_time, SLAB_FIELDS)
     migrants = int((owner0 != owner1).sum())
     print("developed slab8: %d particles changed slab in %d steps" % (migrants, steps))
     assert (owner0 >= 0).all() and migrants > 0, migrants

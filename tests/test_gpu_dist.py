@@ -5,73 +5,30 @@ csrc/mph_dist.hip); the RCCL transport differs only in who moves the message byt
 channel cases stream at 0.5 m/s along the slab axis, so every face-adjacent layer migrates and
 the periodic seam is crossed within the checked steps.
 
-Tolerances: NeighborCount exact (bit-identical acceptance on owned particles); positions 1e-12 m,
-velocities 1e-9 m/s; other fields relative 1e-8 of the field's max plus the roundoff floors of
-test_gpu_parity (the slab's local cell grid orders neighbour sums differently from the oracle).
+Tolerances (tests/parity.py): NeighborCount exact (bit-identical acceptance on owned particles);
+positions 1e-12 m, velocities 1e-9 m/s; other fields relative REL_STEPS of the field's max plus its
+roundoff floor (the slab's local cell grid orders neighbour sums differently from the oracle).
 """
-import multiprocessing as mp
-import os
-import socket
-
 import numpy as np
 import pytest
 
 from particlemethod_fsi_amd import MphSolver, cases
 
 import dist_worker
+from parity import REL_STEPS, assert_close, elastic_rel
 
 pytestmark = pytest.mark.gpu
 
 FIELDS = ["Position", "Velocity", "PressureP", "NeighborCount", "Force", "VolStrainP", "DivergenceP",
           "DensityA", "GravityCenter", "PressureA", "Acceleration"]
-FLOOR = {"PressureP": 1e-9, "PressureA": 1e-9, "Force": 1e-15, "Acceleration": 1e-12,
-         "VolStrainP": 1e-13, "DivergenceP": 1e-12, "DensityA": 1e-13, "GravityCenter": 1e-16,
-         "DeformGradient": 1e-13, "Strain": 1e-13, "Stress": 1e-8}
 # elastic-solid cases: the per-slot tensors of the owned structure particles as well
 STRUCT_FIELDS = FIELDS + ["DeformGradient", "Strain", "Stress"]
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def run_slab(case, world, checkpoints, out, fields=FIELDS, local=False, cuts_mode=None):
-    ctx = mp.get_context("spawn")
-    port = _free_port()
-    ps = [ctx.Process(target=dist_worker.gpu_worker,
-                      args=(r, world, port, case, checkpoints, fields, out, local, cuts_mode))
-          for r in range(world)]
-    for p in ps:
-        p.start()
-    for p in ps:
-        p.join(300)
-    for p in ps:
-        if p.is_alive():
-            p.kill()
-    assert all(p.exitcode == 0 for p in ps), [p.exitcode for p in ps]
+    dist_worker.run_ranks(dist_worker.gpu_worker, world, case, checkpoints, fields, out, local, cuts_mode,
+                          timeout=300)
     return np.load(out)
-
-
-def close(f, a, b, rel=1e-8):
-    if f == "NeighborCount":
-        return np.array_equal(a, b), int((a != b).sum())
-    err = float(np.max(np.abs(a - b))) if a.size else 0.0
-    if f == "Position":
-        t = 1e-12
-    elif f == "Velocity":
-        t = 1e-9
-    else:
-        t = rel * float(np.max(np.abs(b))) + FLOOR.get(f, 1e-12)
-    return err <= t, (err, t)
-
-
-# Elastic cases run near the solid's stability limit (dt c/dx ~ 0.95), where reassociation
-# roundoff grows ~10x per 10 steps: test_gpu_parity's solid bound (1e-7 relative), and for
-# DivergenceP -- a difference of nearly equal sums -- 1e-6, the growth one GPU context itself shows
-# against the oracle on bar3d (tools/slab_diag.py: 8.9e-9 / 9.7e-8 / 7.4e-7 at steps 10 / 20 / 30).
-STRUCT_REL = {"DivergenceP": 1e-6}
 
 
 @pytest.mark.parametrize("case,world,local,cuts", [("channel3d", 2, False, None), ("channel3d", 3, False, None),
@@ -99,8 +56,7 @@ def test_slab_ranks_match_oracle(tmp_path, case, world, local, cuts):
         if not np.array_equal(owner, r["owner0"]):
             moved = True
         for f in FIELDS:
-            ok, info = close(f, r["s%d/%s" % (k, f)], o.get(f))
-            assert ok, (case, world, k, f, info)
+            assert_close(f, r["s%d/%s" % (k, f)], o.get(f), REL_STEPS, context=(case, world, k))
     if case.startswith("channel"):
         assert moved, "no particle migrated between slabs"
 
@@ -125,9 +81,8 @@ def test_slab_structure_ranks_match_oracle(tmp_path, case, world, local, cuts):
         o.step(k - done)
         done = k
         assert (r["s%d/owner" % k] >= 0).all()
-        for f in STRUCT_FIELDS:
-            ok, info = close(f, r["s%d/%s" % (k, f)], o.get(f), STRUCT_REL.get(f, 1e-7))
-            assert ok, (case, world, k, f, info)
+        for f in STRUCT_FIELDS:   # the tensors over all rows; parity.elastic_rel: REL_ELASTIC, DivergenceP wider
+            assert_close(f, r["s%d/%s" % (k, f)], o.get(f), elastic_rel(f), context=(case, world, k))
     # the structure straddles a slab face (elastic ghosts in use) except in the gate case
     prop = parts.property
     sown = r["owner0"][(prop == 2) | (prop == 3)]
@@ -141,8 +96,7 @@ def test_slab_matches_single_gpu(tmp_path):
     with MphSolver(cfg, parts) as s:
         s.step(10)
         for f in FIELDS:
-            ok, info = close(f, r["s10/%s" % f], s.get(f))
-            assert ok, (f, info)
+            assert_close(f, r["s10/%s" % f], s.get(f), REL_STEPS)
 
 
 def test_rccl_exchange_selftest():
@@ -229,20 +183,9 @@ def test_slab_profile_graphs_leave_state_unchanged(tmp_path, monkeypatch):
 
 
 def _run_capacity(tmp_path, tag, case, world, batches):
-    ctx = mp.get_context("spawn")
-    port = _free_port()
     d = tmp_path / tag
     d.mkdir()
-    ps = [ctx.Process(target=dist_worker.gpu_capacity_worker, args=(r, world, port, case, batches, str(d)))
-          for r in range(world)]
-    for p in ps:
-        p.start()
-    for p in ps:
-        p.join(300)
-    for p in ps:
-        if p.is_alive():
-            p.kill()
-    assert all(p.exitcode == 0 for p in ps), [p.exitcode for p in ps]
+    dist_worker.run_ranks(dist_worker.gpu_capacity_worker, world, case, batches, str(d), timeout=300)
     return [dict(np.load(str(d / ("rank%d.npz" % r)))) for r in range(world)]
 
 

@@ -10,10 +10,9 @@ reference at sizes whose golden files would be too large to commit:
 Compared over the bench's horizon: D1M and FSI after steps 1, 10, 29 and 52 (bench.py's default
 warmup 8 + 40 timed + 4 profiled steps = 52; the driver's bench run 5 + 20 + 4 = 29), Bar 400k
 after steps 1, 10, 50 and 100 (the oracle needs about a second per D1M step on 16 host cores);
-sums of the elastic cases at 1e-7 relative, the solid bound of the other parity tests.  Same
-tolerances as
-test_gpu_parity.py: NeighborCount exact, positions 1e-12 m, velocities 1e-9 m/s, sums 1e-8
-relative + roundoff floor.  Where the reference itself is that sensitive -- the elastic gate
+sums of the elastic cases at parity.elastic_rel, the solid bound of the other parity tests.  The
+tolerances of tests/parity.py: NeighborCount exact, positions 1e-12 m, velocities 1e-9 m/s, sums
+REL_STEPS relative + roundoff floor.  Where the reference itself is that sensitive -- the elastic gate
 after 29 and 52 steps -- a field passes within 4x the difference between two oracle runs whose
 start positions differ by one ulp (tests/golden/ulp_<case>.json, tools/ulp_study.py).  Plus
 size-independent properties of the full D1M run: a rerun is bitwise identical and the time
@@ -24,19 +23,10 @@ import os
 import numpy as np
 import pytest
 
+from parity import REL_STEPS, assert_close, elastic_rel
 from particlemethod_fsi_amd import MphSolver, cases
 
 pytestmark = pytest.mark.gpu
-
-FLOOR = {"PressureP": 1e-9, "PressureA": 1e-9, "Force": 1e-15, "Acceleration": 1e-12,
-         "VolStrainP": 1e-13, "DivergenceP": 1e-12, "DensityA": 1e-13, "GravityCenter": 1e-16,
-         "DeformGradient": 1e-13, "Strain": 1e-13, "Stress": 1e-8}
-
-
-def _oracle_threads():
-    from oracle_bindings import OracleSolver
-    OracleSolver.set_threads(min(16, os.cpu_count() or 1))
-
 
 CHECKPOINTS = {"d1m": (1, 10, 29, 52), "fsi3d": (1, 10, 29, 52), "bar2d_400k": (1, 10, 50, 100)}
 # The reference's own roundoff sensitivity (tools/ulp_study.py: the CPU oracle, bit-identical to
@@ -59,8 +49,8 @@ def _ulp_bound(case, k, f):
 
 @pytest.mark.parametrize("case", ["d1m", "fsi3d", "bar2d_400k"])
 def test_full_size_matches_oracle(case):
-    from oracle_bindings import OracleSolver
-    _oracle_threads()
+    from oracle_bindings import OracleSolver, use_oracle_threads
+    use_oracle_threads()
     cfg, parts = cases.get(case).build()
     solid = (parts.property >= 2) & (parts.property < 4)
     o = OracleSolver(cfg, parts)
@@ -77,18 +67,9 @@ def test_full_size_matches_oracle(case):
             if solid.any():
                 fields += ["DeformGradient", "Stress"]
             for f in fields:
-                a, b = s.get(f), o.get(f)
-                if f in ("DeformGradient", "Stress"):
-                    a, b = a[solid], b[solid]
-                scale = float(np.max(np.abs(b))) if b.size else 0.0
-                # elastic cases run near the solid's stability limit, where reassociation roundoff
-                # grows ~10x per 10 steps: the solid bound of test_gpu_parity / test_gpu_dist
-                # (DivergenceP, a difference of nearly equal sums, 1e-6 as in test_gpu_dist)
-                rel = (1e-6 if f == "DivergenceP" else 1e-7) if solid.any() else 1e-8
-                t = {"Position": 1e-12, "Velocity": 1e-9}.get(f, rel * scale + FLOOR.get(f, 1e-12))
-                t = max(t, _ulp_bound(case, k, f))
-                err = float(np.max(np.abs(a - b))) if b.size else 0.0
-                assert err <= t, (case, k, f, err, t)
+                assert_close(f, s.get(f), o.get(f), elastic_rel(f) if solid.any() else REL_STEPS,
+                             rows=solid if f in ("DeformGradient", "Stress") else None,
+                             extra=_ulp_bound(case, k, f), context=(case, k))
 
 
 def test_d1m_rerun_bitwise_and_time():

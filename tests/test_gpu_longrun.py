@@ -20,29 +20,23 @@ path of DeformationVector / Stress / StressForce / updateElasticPosition (main.c
   in the gate); the state (Position, Velocity, InitialPosition, Time -- a .prof restart,
   main.cpp:788-955) goes to the oracle, and both advance 1 and 10 steps: NeighborCount
   exact, the gate's DeformGradient and Stress, the fluid's pressure and the forces within the
-  bounds of test_gpu_developed.py; the gate has been hit (fluid front past its face, gate
-  displaced).
+  bounds of test_gpu_developed.py (parity.REL_STEPS); the gate has been hit (fluid front past its
+  face, gate displaced).
 """
 import os
 
 import numpy as np
 import pytest
 
+from parity import REL_ONE_STEP, REL_STEPS, assert_close
 from particlemethod_fsi_amd import MphSolver, cases, mphio
 
 pytestmark = pytest.mark.gpu
 
-FLOOR = {"PressureP": 1e-9, "Force": 1e-15, "VolStrainP": 1e-13, "DivergenceP": 1e-12,
-         "DeformGradient": 1e-13, "Strain": 1e-13, "Stress": 1e-8}
-
-
-def _err(a, b):
-    return float(np.max(np.abs(a - b))) if b.size else 0.0
-
 
 def test_bar2d_large_deformation_matches_oracle():
-    from oracle_bindings import OracleSolver
-    OracleSolver.set_threads(min(16, os.cpu_count() or 1))
+    from oracle_bindings import OracleSolver, use_oracle_threads
+    use_oracle_threads()
     cfg, parts = cases.get("bar2d").build()
     solid = (parts.property >= 2) & (parts.property < 4)
     tip = int(np.argmax(np.where(solid, parts.position[:, 0], -np.inf)))
@@ -60,16 +54,9 @@ def test_bar2d_large_deformation_matches_oracle():
             assert np.array_equal(s.get("InitialStructureNeighborCount"),
                                   o.get("InitialStructureNeighborCount")), k
             rep = {}
-            for f, t in (("Position", 1e-12), ("Velocity", 1e-9)):
-                rep[f] = _err(s.get(f), o.get(f))
-                assert rep[f] <= t, (k, f, rep[f], t)
-            for f in ("DeformGradient", "Strain", "Stress", "PressureP", "Force"):
-                a, b = s.get(f), o.get(f)
-                if f in ("DeformGradient", "Strain", "Stress"):
-                    a, b = a[solid], b[solid]
-                t = 1e-9 * float(np.max(np.abs(b))) + FLOOR[f]
-                rep[f] = _err(a, b)
-                assert rep[f] <= t, (k, f, rep[f], t)
+            for f in ("Position", "Velocity", "DeformGradient", "Strain", "Stress", "PressureP", "Force"):
+                rows = solid if f in ("DeformGradient", "Strain", "Stress") else None
+                rep[f] = assert_close(f, s.get(f), o.get(f), REL_ONE_STEP, rows=rows, context=(k,))
             print("bar2d step %d: %s" % (k, " ".join("%s %.2e" % kv for kv in rep.items())))
         # the regime: large deflection and a strain whose nonlinear part is not small
         pos, F = o.get("Position"), o.get("DeformGradient")[solid][:, :2, :2]
@@ -88,8 +75,8 @@ FSI_STEPS = int(os.environ.get("MPH_FSI_HANDOFF", "3500"))
 
 
 def test_fsi3d_sub_developed_matches_oracle():
-    from oracle_bindings import OracleSolver
-    OracleSolver.set_threads(min(16, os.cpu_count() or 1))
+    from oracle_bindings import OracleSolver, use_oracle_threads
+    use_oracle_threads()
     cfg, parts = cases.get("fsi3d_sub").build()
     solid = (parts.property >= 2) & (parts.property < 4)
     fluid = parts.property < 2
@@ -120,12 +107,7 @@ def test_fsi3d_sub_developed_matches_oracle():
             rep = {}
             for f in ("Position", "Velocity", "PressureP", "VolStrainP", "DivergenceP", "Force",
                       "DeformGradient", "Stress"):
-                a, b = s.get(f), o.get(f)
-                if f in ("DeformGradient", "Stress"):
-                    a, b = a[solid], b[solid]
-                scale = float(np.max(np.abs(b)))
-                t = {"Position": 1e-12, "Velocity": 1e-9}.get(f, 1e-8 * scale + FLOOR.get(f, 1e-12))
-                rep[f] = _err(a, b)
-                assert rep[f] <= t, (k, f, rep[f], t)
+                rows = solid if f in ("DeformGradient", "Stress") else None
+                rep[f] = assert_close(f, s.get(f), o.get(f), REL_STEPS, rows=rows, context=(k,))
             print("fsi3d_sub +%d: %s" % (k, " ".join("%s %.2e" % kv for kv in rep.items())))
         assert s.time == o.time

@@ -14,8 +14,8 @@ C. The aligned rows' jumps (mph_list_layout): they happen off the lattice, stop 
    the rows decoded on the host hold exactly the reference's sets.
 
 The reference is the CPU oracle, pinned to the compiled reference on these configurations by
-test_oracle_per_kernel_against_live_reference.  Every bound is test_gpu_parity's (its docstring is
-the statement of the tolerances; the comparison itself is imported from there): the oracle's own
+test_oracle_per_kernel_against_live_reference.  Every bound is that of tests/parity.py (the
+statement of the tolerances; the comparison itself is imported from there): the oracle's own
 sensitivity to a one-ulp change of its input stays below 0.07 of them on every case here.
 """
 import functools
@@ -24,8 +24,8 @@ import numpy as np
 import pytest
 
 from particlemethod_fsi_amd import MphSolver, cases, mphio
-from test_gpu_parity import (CHUNK_FIELDS, check_fields_against_oracle, check_structure_init_equals_host_build,
-                             run_against_oracle_every_step)
+from parity import (CHUNK_FIELDS, check_fields_against_oracle, check_structure_init_equals_host_build,
+                    run_against_oracle_every_step)
 
 pytestmark = pytest.mark.gpu
 
