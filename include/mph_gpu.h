@@ -536,6 +536,13 @@ int mph_list_stats(MphCtx* ctx, double* mean, int* max);
  * their jumps), the most rows of one lane (entries + gaps)}.  Read-only, reduced on the host.
  * Single contexts only (MPH_ERR_UNSUPPORTED in slab mode).  ABI 5.                             */
 int mph_list_layout(MphCtx* ctx, long long out6[6]);
+/* Lazy wall steps, for verification: out2 = {idle wave-steps, lazy steps} since the
+ * creation.  A lazy step is a step that stores no output-only field (every step of an 8-step batch
+ * or of a call's remainder but the last) in a single context without monitors; on it the search
+ * skips, and counts as idle, every wave of wall particles that no fluid or structure particle can
+ * reach.  Both stay 0 in slab mode, with monitors configured, or with MPH_LAZY_WALLS=0 in the
+ * environment at creation.  A flush point.  Additive: no change of MPH_ABI_VERSION.            */
+int mph_idle_wall_stats(MphCtx* ctx, long long out2[2]);
 /* The neighbour lists of calculateNeighbor themselves (main.cpp:1764-1772: Neighbor[i][k] = j for
  * k < 512), for verification: the sets of the `count` particles [first, first + count) (original
  * order) from the last search, each row as ascending original indices (the reference's rows are in

@@ -134,6 +134,7 @@ struct MphCtx {
     double* sample_out = nullptr;
     size_t sample_cap = 0;       // doubles the allocation holds
     bool a_current = false;
+    bool lazy_walls = false;     // lazy wall steps on (ctx_fill_launch; L.cmap allocated at creation)
     MphDist* dist = nullptr;     // non-null in slab mode
 };
 

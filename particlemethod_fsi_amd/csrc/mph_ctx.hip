@@ -73,6 +73,9 @@ void ctx_fill_launch(MphCtx* c)
     // MPH_LIST_FULL=1: the lists keep every neighbour within the search radius, like the reference's
     // Neighbor[] (mph_neighbor_rows needs them); else only those the passes' sums can take
     if (std::getenv("MPH_LIST_FULL") && std::atoi(std::getenv("MPH_LIST_FULL")) == 1) c->P.rlf = 3.0e38f;
+    // MPH_LAZY_WALLS=0: no lazy wall steps (enqueue_step), every step searches and sums every wall
+    // wave; slab contexts never take them (a halo wall may have a fluid neighbour on the next rank)
+    c->lazy_walls = !c->dist && !(std::getenv("MPH_LAZY_WALLS") && std::atoi(std::getenv("MPH_LAZY_WALLS")) == 0);
     L.P = &c->P;
     L.stream = c->stream;
     // work-balanced XCD map of the passes from this many particles (MPH_XCD_BAL_MIN: tests force it
@@ -112,11 +115,20 @@ namespace {
 // ev (phase timing, else null): three events recorded on the stream at the step's phase
 // boundaries -- before the sort, after the search (neighbour search = sort + search, as the
 // reference's calculateNeighbor holds its own cell sort), after the elastic substeps.
+//
+// Lazy wall steps take the same rule one kernel further up.  On a step that is not `last`, a wall
+// walks no list in pass B, so what the search and pass A compute for a wall particle whose
+// neighbours are all walls -- its list, PressureP, the pass-B record, fpart -- has no reader; the
+// batch's last step computes all of it again.  Such a step marks the coarse cells of the non-wall
+// particles in its sort, and its search skips the wall waves out of their reach (wave_idle_walls).
+// Off (every step full) without the map (slab mode, MPH_LAZY_WALLS=0) and while the monitor kernels
+// run, which read the walls' pressure on every step.
 void enqueue_step(const Launch& L, bool last, hipEvent_t* ev = nullptr)
 {
     if (ev) (void)hipEventRecord(ev[0], L.stream);
-    launch_sort(L, 1);
     Launch La = L;
+    La.lazy = !last && L.cmap && !L.mon;
+    launch_sort(La, 1);
     if (!last) {
         La.dens_a = La.vstrain = La.divp = nullptr;
         if (!L.P->surface) La.gx = La.gy = La.gz = La.pa = nullptr;
@@ -134,6 +146,7 @@ void enqueue_step(const Launch& L, bool last, hipEvent_t* ev = nullptr)
         Launch Lb = L;
         Lb.force = nullptr;
         Lb.acc = nullptr;
+        Lb.lazy = La.lazy;   // (the grid of a lazy step's XCD map, list_grid)
         launch_pass_b(Lb);
     }
     launch_structure(L, last);
@@ -661,6 +674,12 @@ static int init_first_sums(MphCtx* c)
     } else {
         launch_sort(c->L, 0);
         launch_search_pass_a(c->L);
+        if (c->lazy_walls) {   // the coarse map of the lazy wall steps: all zero between steps
+            const size_t mb = coarse_map_bytes(c->P.gc);
+            MPH_CK(ctx_dalloc(c, &c->L.cmap, mb));
+            MPH_HIP_OK(c, hipMemsetAsync(c->L.cmap, 0, mb, c->stream));
+            c->L.cmap_bytes = (int)mb;
+        }
     }
     MPH_HIP_OK(c, hipGetLastError());
     MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
@@ -1319,6 +1338,26 @@ int mph_list_layout(MphCtx* c, long long out[6])
         max_rows = std::max<long long>(max_rows, rows);
     }
     out[0] = waves; out[1] = jumped; out[2] = jumps; out[3] = max_jumps; out[4] = gap_rows; out[5] = max_rows;
+    return MPH_OK;
+}
+
+int mph_idle_wall_stats(MphCtx* c, long long out[2])
+{
+    if (!c || !out) return MPH_ERR_ARG;
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    // the tail of DevState: the lazy steps, then the idle waves per run of the waves
+    unsigned long long steps = 0;
+    std::vector<unsigned> seg(kXcdSegs);
+    const char* st = reinterpret_cast<const char*>(c->L.st);
+    MPH_HIP_OK(c, hipMemcpy(&steps, st + offsetof(DevState, lazy_steps), sizeof(steps), hipMemcpyDeviceToHost));
+    MPH_HIP_OK(c, hipMemcpy(seg.data(), st + offsetof(DevState, idle_waves), sizeof(unsigned) * kXcdSegs,
+                            hipMemcpyDeviceToHost));
+    long long idle = 0;
+    for (unsigned v : seg) idle += v;
+    out[0] = idle;
+    out[1] = (long long)steps;
     return MPH_OK;
 }
 

@@ -121,6 +121,13 @@ __device__ __forceinline__ int cell_id(const DevParams& P, double x, double y, d
     return cell_index(P, cx, cy, cz);
 }
 
+// byte of coarse cell (qx, qy, qz) in the coarse map of the non-wall particles (mph_params.h
+// kCoarseShift; (x, y, z) order whatever the cell order)
+__device__ __forceinline__ int coarse_index(const DevParams& P, int qx, int qy, int qz)
+{
+    return (qx * coarse_cells(P.gc[1]) + qy) * coarse_cells(P.gc[2]) + qz;
+}
+
 __device__ __forceinline__ bool dev_is_struct(int t) { return t == 2 || t == 3; }
 __device__ __forceinline__ bool dev_is_fluid(int t) { return t == 0 || t == 1; }
 __device__ __forceinline__ bool dev_is_wall(int t) { return t == 4 || t == 5; }

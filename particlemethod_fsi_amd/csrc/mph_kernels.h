@@ -130,6 +130,12 @@ struct Launch {
     // fewest particles for the work-balanced XCD map of the passes (split in k_rank_scatter);
     // MPH_XCD_BAL_MIN overrides it at creation (tests force the map on small cases)
     int xcd_bal_min = 1 << 20;
+    // lazy wall steps (mph_params.h kCoarseShift): the coarse map of the non-wall particles (null:
+    // the context never takes a lazy step) and its size; lazy: this step is one (enqueue_step) --
+    // k_prep marks the map, the search skips the idle wall waves, pass A clears the map again
+    unsigned char* cmap = nullptr;
+    int cmap_bytes = 0;
+    bool lazy = false;
     // pass A products (A order): pressure values, gravity centre (GC, PressureA), sums
     double *pres = nullptr, *gx = nullptr, *gy = nullptr, *gz = nullptr, *pa = nullptr;
     double *dens_a = nullptr, *vstrain = nullptr, *divp = nullptr;

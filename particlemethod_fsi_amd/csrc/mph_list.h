@@ -30,12 +30,12 @@ constexpr int kWaveCost = 16;   // a wave's fixed cost, in list entries, for the
 
 // rev: each XCD takes its range from the far end (pass A: it starts on the list tiles the search
 // wrote last, which the Infinity Cache still holds)
-__device__ __forceinline__ int list_block(const DevState* st, int n, bool rev = false)
+// fr: the map's fractions (DevState.xcd_frac for the passes; xcd_sfrac for a lazy step's search)
+__device__ __forceinline__ int list_block(const int* fr, int n, bool rev = false)
 {
     const int nb = list_blocks(n);
     const int b = blockIdx.x;
-    if (st) {
-        const int* fr = st->xcd_frac;
+    if (fr) {
         const int cap = gridDim.x >> 3;
         const int j = b & 7;
         bool ok = fr[0] == 0 && fr[8] == 65536;
@@ -60,28 +60,44 @@ __device__ __forceinline__ int list_block(const DevState* st, int n, bool rev = 
     const int cnt = q + (xcd < r ? 1 : 0);
     return lo + cnt - 1 - (b >> 3);
 }
+__device__ __forceinline__ int list_block(const DevState* st, int n, bool rev = false)
+{
+    return list_block(st ? st->xcd_frac : nullptr, n, rev);
+}
 
 // Grid of the two list passes: the XCD map (list_block) needs a multiple of 8 blocks, with 25 %
 // slack for its unequal ranges.  Below Launch.xcd_bal_min particles (default 2^20) the split
 // kernel's ~7 us costs more than the balance gains (Bar 400k, 0.23 ms per step: 1.76e9 p-steps/s
 // with it, 1.80e9 without), so the passes keep the equal ranges and the search feeds no histogram.
-static inline int list_grid(int n)
+// A lazy step's maps (DevState.seg_lwork, seg_swork) need more: its idle waves weigh next to nothing
+// and lie together, so the XCD that holds them takes a range of ~30 % of the blocks at D1M at rest
+// (22 % of the waves idle, the far half of the tank), which 25 % slack cannot hold -- list_block
+// would fall back to the equal ranges and leave that XCD idle.  lazy: three blocks per live block,
+// any range up to 3/8 of them; the blocks past a range exit at once.
+static inline int list_grid(int n, bool lazy = false)
 {
     const int nb = blocks(n, MPH_LB);
-    return (nb + nb / 4 + 15) / 8 * 8;
+    return ((lazy ? 3 * nb : nb + nb / 4) + 15) / 8 * 8;
 }
 
-// The search's contribution to the work histogram: its wave's longest list (all lanes converged;
-// one atomic per wave, spread over the 4096 runs).
-__device__ __forceinline__ void add_wave_work(DevState* st, int cnt, int i, int n)
+// a lazy step's search (DevState.seg_swork): a searched wave's cost and an idle wave's (its type and
+// position loads and the coarse map's bytes against 49 stencil columns)
+constexpr int kSearchCost = 16, kIdleCost = 2;
+
+// The search's contribution to a work histogram (seg: DevState.seg_work, or a lazy step's
+// seg_lwork): its wave's longest list (all lanes converged; one atomic per wave, spread over the
+// 4096 runs); sseg set (a lazy step): the wave's search cost too.
+__device__ __forceinline__ void add_wave_work(int* seg, int cnt, int i, int n, int* sseg = nullptr, bool idle = false)
 {
-    if (!st) return;
     int m = cnt;
     for (int o = 32; o; o >>= 1) m = max(m, __shfl_xor(m, o));
     const int tile = __builtin_amdgcn_readfirstlane(i >> 6);
     const int ntile = (n + 63) >> 6;
-    if ((threadIdx.x & 63) == 0 && tile < ntile)
-        atomicAdd(&st->seg_work[(int)(((long long)tile * kXcdSegs) / ntile)], m + kWaveCost);
+    if ((threadIdx.x & 63) == 0 && tile < ntile) {
+        const int r = (int)(((long long)tile * kXcdSegs) / ntile);
+        atomicAdd(&seg[r], m + kWaveCost);
+        if (sseg) atomicAdd(&sseg[r], idle ? kIdleCost : kSearchCost);
+    }
 }
 
 __device__ __forceinline__ int nbr_entry(int j, int type) { return j | (type << kTypeShift); }

@@ -188,6 +188,25 @@ inline void set_uniforms(DevParams& P)
     P.rlf = (float)(rmax * rmax * (1.0 + delta));
 }
 
+// Lazy wall steps.  On a step whose output-only fields are not stored, a
+// wall particle with no fluid or structure particle in reach is read by nobody: its neighbours are
+// walls, and a wall walks no list in pass B on such a step.  k_prep marks, per step, the coarse
+// cells that hold a non-wall particle (one byte each, blocks of 2^kCoarseShift grid cells per
+// axis: 4 cells are 3.5 dx across the columns and 5.2 dx along the contiguous axis at RadiusRatio
+// 2.5), and the search skips an interior wave of walls none of whose lanes' stencil boxes touches a
+// marked cell (mph_search.hip wave_idle_walls).
+constexpr int kCoarseShift = 2;
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr inline int coarse_cells(int g) { return (g + (1 << kCoarseShift) - 1) >> kCoarseShift; }
+// bytes of the coarse map of a grid, a multiple of 16 (pass A clears it in 16-byte stores)
+inline size_t coarse_map_bytes(const int gc[3])
+{
+    const size_t b = (size_t)coarse_cells(gc[0]) * coarse_cells(gc[1]) * coarse_cells(gc[2]);
+    return (b + 15) & ~(size_t)15;
+}
+
 // work histogram of the XCD map: waves in 4096 equal runs (D16M: ~60 waves per run, so the
 // search's per-wave atomics spread over ~100 addresses at a time; 512 runs cost its search 7 %)
 constexpr int kXcdSegs = 4096;
@@ -216,6 +235,22 @@ struct DevState {
     int seg_work[kXcdSegs];
     int xcd_frac[9];
     int xcd_pad[3];
+    // lazy wall steps (kCoarseShift above): the steps searched with the idle-wave exit since the
+    // creation, and the waves that took it -- counted like seg_work, one add per idle wave into
+    // its run of the waves, summed on the host (mph_idle_wall_stats)
+    unsigned long long lazy_steps;
+    unsigned idle_waves[kXcdSegs];
+    // The XCD maps of a lazy step.  Its idle waves are no work, and they lie together (at D1M the
+    // far half of the tank: the last XCD's whole equal share of the search), so a lazy step keeps
+    // histograms of its own, each turned into a map by the next lazy step's k_rank_scatter: the
+    // passes' work as seg_work (seg_lwork -> xcd_frac, which a full step takes from seg_work, fed
+    // by the last full step), and the search's -- a fixed cost per searched wave, a small one per
+    // idle wave (kSearchCost, kIdleCost) -- for the search itself (seg_swork -> xcd_sfrac; a full
+    // step's search keeps the equal ranges of xcd_block, mph_list.h)
+    int seg_lwork[kXcdSegs];
+    int seg_swork[kXcdSegs];
+    int xcd_sfrac[9];
+    int xcd_spad[3];
 };
 // the part of DevState the host reads back after steps (the error bits and the step scalars)
 constexpr size_t kStateHead = offsetof(DevState, seg_work);

@@ -234,9 +234,15 @@ __global__ __launch_bounds__(MPH_LB) MPH_PA_ATTR void k_pass_a(DevParams P, cons
                                                 const int* __restrict__ ncount,
                                                 const unsigned long long* __restrict__ lhdr,
                                                 const unsigned long long* __restrict__ lgap, PassAOut pout,
-                                                const DevState* __restrict__ st)
+                                                const DevState* __restrict__ st,
+                                                unsigned char* __restrict__ cmap, int cmap_bytes)
 {
     const int n = dev_n(P);
+    // a lazy wall step (cmap set): its search, the coarse map's only reader, is done -- back to
+    // all zero for the next step's k_prep, 16 bytes per thread of the grid's first blocks
+    if (cmap)
+        for (int q = blockIdx.x * MPH_LB + threadIdx.x; q * 16 < cmap_bytes; q += gridDim.x * MPH_LB)
+            reinterpret_cast<int4*>(cmap)[q] = make_int4(0, 0, 0, 0);
     const int lb = list_block(st, n, MPH_PASS_A_REV);
     if (lb < 0) return;
     __shared__ double s_ratio[kTypes * kTypes];
@@ -607,8 +613,9 @@ void launch_pass_a(const Launch& L)
     const DevParams& P = *L.P;
     if (P.n == 0) return;
     by_dim(P.dim, [&](auto D) {
-        launch(L.prof, "pass_a", L.stream, k_pass_a<decltype(D)::value>, dim3(list_grid(P.n)), dim3(MPH_LB), P, L.T,
-               L.A, L.nbr, L.ncount, L.lhdr, L.lgap, pass_a_out(L), L.st);
+        launch(L.prof, "pass_a", L.stream, k_pass_a<decltype(D)::value>,
+               dim3(list_grid(P.n, L.lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T,
+               L.A, L.nbr, L.ncount, L.lhdr, L.lgap, pass_a_out(L), L.st, L.lazy ? L.cmap : nullptr, L.cmap_bytes);
     });
 }
 
@@ -646,7 +653,8 @@ void launch_pass_b(const Launch& L, int phase)
     auto go = [&](auto SURF) {
         by_dim(P.dim, [&](auto D) {
             launch(L.prof, phase == 2 ? "pass_b_face" : "pass_b", L.stream,
-                   k_pass_b<decltype(SURF)::value, decltype(D)::value>, dim3(list_grid(P.n)), dim3(MPH_LB), P, L.T, L.A,
+                   k_pass_b<decltype(SURF)::value, decltype(D)::value>,
+                   dim3(list_grid(P.n, L.lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T, L.A,
                    L.rec, L.fpart, L.gx, L.gy, L.gz, L.pa, L.nbr, L.ncount, L.lhdr, L.lgap, L.force, L.acc, L.B, phase,
                    L.wface, struct_hook(L), L.st);
         });

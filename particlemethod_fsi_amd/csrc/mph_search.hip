@@ -504,6 +504,63 @@ __device__ __forceinline__ void slab_wave_flag(const DevParams& P, const Soa& A,
     if ((threadIdx.x & 63) == 0) wface[i >> 6] = face ? 1 : 0;
 }
 
+// Lazy wall steps (mph_params.h kCoarseShift; cmap: this step's coarse map of the non-wall
+// particles, from k_prep): true when the wave is idle -- every live lane is a wall, the wave is
+// interior (wave_search_interior: no stencil wraps), and no coarse cell that a lane's stencil can
+// reach holds a non-wall particle.  The bound is geometric and conservative: each lane takes the
+// box of its own cell widened by kReach cells on every axis (the stencil reaches kReach cells
+// across the columns and kContigReach <= kReach along the contiguous axis; clamping the box to the
+// grid loses nothing for an interior lane), at most 3 x 3 x 3 coarse cells, and one ballot decides.
+// (The lanes' own boxes, not the box of the wave's cells shared out over the lanes: no wave-wide
+// minima and maxima, no cap for a wave that straddles two walls, and a tighter bound; the wave-box
+// form took the 3-D search from 63 VGPRs to 13 spilled ones.)  No list of a non-wall particle then
+// holds a lane of this wave, and on a step that stores no output-only field nothing else reads
+// what the search and pass A compute for it (enqueue_step).  The wave gets empty lists, as a wave
+// of ghosts does, and is counted in its run of the waves like the work histogram (never one same-
+// address atomic per wave, see neighbors_body).  It runs ahead of neighbors_body on values of its
+// own, which end with it: the search's register budget is the parent's.
+template <int DIM>
+__device__ __forceinline__ bool wave_idle_walls(const DevParams& P, const Soa& A, const unsigned char* cmap,
+                                                DevState* st, int* ncount, int* nbcount,
+                                                unsigned long long* lhdr, int i, int n)
+{
+    static_assert(kContigReach <= kReach, "the box is widened by kReach on every axis");
+    static_assert(2 * kReach < 2 << kCoarseShift, "a lane's box spans at most 3 coarse cells per axis");
+    const int tile = __builtin_amdgcn_readfirstlane(i >> 6);
+    if (tile * kTile >= n) return false;
+    const bool live = i < n;
+    int ii = live ? i : n - 1;
+    asm volatile("" : "+v"(ii));   // (its loads are not kept for neighbors_body)
+    if (!__all(!live || dev_is_wall(A.type[ii]))) return false;
+    const double xi = A.x[ii], yi = A.y[ii], zi = A.z[ii];
+    if (!wave_search_interior(P, st, live, xi, yi, zi)) return false;
+    const int cx = cell_axis(xi, P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
+    const int cy = cell_axis(yi, P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
+    const int cz = DIM == 3 ? cell_axis(zi, P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
+    const int ax = max(cx - kReach, 0) >> kCoarseShift, bx = min(cx + kReach, P.gc[0] - 1) >> kCoarseShift;
+    const int ay = max(cy - kReach, 0) >> kCoarseShift, by = min(cy + kReach, P.gc[1] - 1) >> kCoarseShift;
+    const int az = DIM == 3 ? max(cz - kReach, 0) >> kCoarseShift : 0;
+    const int bz = DIM == 3 ? min(cz + kReach, P.gc[2] - 1) >> kCoarseShift : 0;
+    const int ny = coarse_cells(P.gc[1]), nz = coarse_cells(P.gc[2]);
+    int hit = 0;
+#pragma unroll 1
+    for (int kx = 0; kx < 3; ++kx) {
+#pragma unroll 1
+        for (int ky = 0; ky < 3; ++ky) {
+            const unsigned char* row = cmap + (min(ax + kx, bx) * ny + min(ay + ky, by)) * nz;
+            hit |= row[az] | row[min(az + 1, bz)] | row[bz];
+        }
+    }
+    if (__ballot(hit != 0)) return false;
+    if (live) ncount[i] = 0;
+    if (live) nbcount[i] = 0;
+    if ((threadIdx.x & 63) == 0) {
+        lhdr[tile] = 0;
+        atomicAdd(&st->idle_waves[(int)(((long long)tile * kXcdSegs) / ((n + 63) >> 6))], 1u);
+    }
+    return true;
+}
+
 // ncount: the rows of each particle's stored list, gaps included (what the passes walk; the
 // entries, r^2 <= P.rlf, are the rows outside the gaps, RowMask); nbcount: NeighborCount, every
 // neighbour within the search radius; lhdr / lgap: the row jumps (RowMask)
@@ -558,21 +615,40 @@ __device__ __forceinline__ int neighbors_body(const DevParams& P, const Soa& A, 
 #ifndef MPH_NB_WPE
 #define MPH_NB_WPE 8
 #endif
-template <int DIM, int PERM>
+// LAZY: a lazy wall step's search (cmap set); a full step's is a kernel of its own, so that it keeps
+// the registers it had before the lazy steps (their map and histograms cost the search ~50 SGPR
+// spills and 1.3 % at D1M when both were one kernel).
+template <int DIM, int PERM, bool LAZY>
 __global__ __launch_bounds__(MPH_LB) __attribute__((amdgpu_waves_per_eu(MPH_NB_WPE))) void k_neighbors(
     DevParams P, Soa A, const int* __restrict__ start, int* __restrict__ nbr, int* __restrict__ ncount,
     int* __restrict__ nbcount, unsigned long long* __restrict__ lhdr, unsigned long long* __restrict__ lgap,
-    DevState* __restrict__ st, int* __restrict__ wface, int bal)
+    DevState* __restrict__ st, int* __restrict__ wface, int bal, const unsigned char* __restrict__ cmap_arg)
 {
+    const unsigned char* cmap = LAZY ? cmap_arg : nullptr;
     const int n = dev_n(P);
-    if ((int)blockIdx.x >= list_blocks(n)) return;
-    const int tb = xcd_block(blockIdx.x, list_blocks(n));
+    if (cmap && blockIdx.x == 0 && threadIdx.x == 0) st->lazy_steps += 1;   // (the one writer)
+    // the wave's block: a lazy step with the XCD split takes the map made from the last lazy step's
+    // search costs (list_block over xcd_sfrac, a list_grid launch), else the equal ranges
+    int tb;
+    if (cmap && bal) {
+        tb = list_block(st->xcd_sfrac, n);
+        if (tb < 0) return;
+    } else {
+        if ((int)blockIdx.x >= list_blocks(n)) return;
+        tb = xcd_block(blockIdx.x, list_blocks(n));
+    }
     __shared__ __attribute__((aligned(16))) double stage[kWB][stage_words(MPH_LDS_CAP, MPH_SB)];
     const int i = tb * blockDim.x + threadIdx.x;
     slab_wave_flag(P, A, i, n, wface);
-    const int cnt = neighbors_body<DIM, PERM>(P, A, start, nbr, ncount, nbcount, lhdr, lgap, st,
-                                              stage[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)], i);
-    if (bal) add_wave_work(st, cnt, i, n);
+    // a lazy wall step (cmap set): an idle wave of walls only adds its fixed costs to the histograms
+    const bool idle = cmap && wave_idle_walls<DIM>(P, A, cmap, st, ncount, nbcount, lhdr, i, n);
+    const int cnt = idle ? 0
+                         : neighbors_body<DIM, PERM>(P, A, start, nbr, ncount, nbcount, lhdr, lgap, st,
+                                                     stage[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)], i);
+    if (bal) {
+        if (cmap) add_wave_work(st->seg_lwork, cnt, i, n, st->seg_swork, idle);
+        else add_wave_work(st->seg_work, cnt, i, n);
+    }
 }
 
 // ---------------------------------------------------------------------------- launchers -----
@@ -582,11 +658,18 @@ void launch_neighbors(const Launch& L)
     const DevParams& P = *L.P;
     if (P.n == 0) return;
     const int bal = P.n >= L.xcd_bal_min;
+    const bool lazy = L.lazy && L.cmap;
     by_dim(P.dim, [&](auto D) {
         constexpr int DIM = decltype(D)::value;
         auto go = [&](auto PERM) {
-            launch(L.prof, "neighbors", L.stream, k_neighbors<DIM, decltype(PERM)::value>, dim3(blocks(P.n, MPH_LB)),
-                   dim3(MPH_LB), P, L.A, L.start, L.nbr, L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, bal);
+            if (lazy)
+                launch(L.prof, "neighbors", L.stream, k_neighbors<DIM, decltype(PERM)::value, true>,
+                       dim3(bal ? list_grid(P.n, true) : blocks(P.n, MPH_LB)), dim3(MPH_LB), P, L.A, L.start, L.nbr,
+                       L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, bal, L.cmap);
+            else
+                launch(L.prof, "neighbors", L.stream, k_neighbors<DIM, decltype(PERM)::value, false>,
+                       dim3(blocks(P.n, MPH_LB)), dim3(MPH_LB), P, L.A, L.start, L.nbr, L.ncount, L.nbcount, L.lhdr,
+                       L.lgap, L.st, L.wface, bal, nullptr);
         };
         if constexpr (DIM == 3) {   // (the 2-D grid has the one cell order)
             switch (P.perm) {

@@ -36,15 +36,17 @@ static_assert(kScanBlock == 4096, "mph_ctx.hip sizes the bsum buffer for 4096-ce
 // scan of the runs' work (kXcdSegs / blockDim.x consecutive runs per thread), the 7 inner cut
 // points at equal shares of the total (interpolated inside their run), then the histogram cleared.
 // Block 0 of the next step's k_rank_scatter calls it (see there).
+// seg / fr: the histogram and the map it becomes (DevState: seg_work or a lazy step's seg_lwork ->
+// xcd_frac; a lazy step's seg_swork -> xcd_sfrac).
 template <int T>
-__device__ __forceinline__ void xcd_split_block(DevState* st)
+__device__ __forceinline__ void xcd_split_block(int* seg, int* fr)
 {
     constexpr int R = kXcdSegs / T;
     static_assert(kXcdSegs % T == 0, "whole runs per thread");
     __shared__ long long s[T];
     const int t = threadIdx.x;
     long long sum = 0;
-    for (int r = 0; r < R; ++r) sum += max(st->seg_work[t * R + r], 0);
+    for (int r = 0; r < R; ++r) sum += max(seg[t * R + r], 0);
     s[t] = sum;
     __syncthreads();
     for (int o = 1; o < T; o <<= 1) {
@@ -54,7 +56,6 @@ __device__ __forceinline__ void xcd_split_block(DevState* st)
         __syncthreads();
     }
     const long long tot = s[T - 1];
-    int* fr = st->xcd_frac;
     if (tot < 8) {
         if (t < 9) fr[t] = 8192 * t;
     } else {
@@ -63,7 +64,7 @@ __device__ __forceinline__ void xcd_split_block(DevState* st)
             long long prev = t ? s[t - 1] : 0;
             if (!(prev < tgt && s[t] >= tgt)) continue;
             for (int r = 0; r < R; ++r) {
-                const int w = max(st->seg_work[t * R + r], 0);
+                const int w = max(seg[t * R + r], 0);
                 if (w > 0 && prev < tgt && prev + w >= tgt) {
                     const double f = (t * R + r + (double)(tgt - prev) / (double)w) / kXcdSegs;
                     fr[x] = min(65536, max(0, (int)(f * 65536.0 + 0.5)));
@@ -77,15 +78,18 @@ __device__ __forceinline__ void xcd_split_block(DevState* st)
         }
     }
     __syncthreads();   // every thread has read its runs
-    for (int r = 0; r < R; ++r) st->seg_work[t * R + r] = 0;
+    for (int r = 0; r < R; ++r) seg[t * R + r] = 0;
+    __syncthreads();   // (a second split may follow: the scan's LDS is free again)
 }
 
 // calculateWall (main.cpp:3031-3060) + calculatePeriodicBoundary (3322-3333) + cell histogram.
 // mode 0: initialisation (no motion), 1: time step, 2: time step whose motion was already applied
-// (slab mode, k_dist_prep).
-__global__ __launch_bounds__(256) void k_prep(DevParams P, const DevState* __restrict__ st, Soa C,
-                                              int* __restrict__ key, int* __restrict__ slot,
-                                              int* __restrict__ cnt, int mode, VSrc vs)
+// (slab mode, k_dist_prep).  cmap: a lazy wall step's coarse map of the non-wall particles
+// (mph_params.h kCoarseShift), else null.  Held to 64 VGPRs (8 waves per SIMD) as before the map:
+// without the hint the marking took it to 66 and 7 waves.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_prep(
+    DevParams P, const DevState* __restrict__ st, Soa C, int* __restrict__ key, int* __restrict__ slot,
+    int* __restrict__ cnt, int mode, VSrc vs, unsigned char* __restrict__ cmap)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     const int n = dev_n(P);
@@ -103,8 +107,15 @@ __global__ __launch_bounds__(256) void k_prep(DevParams P, const DevState* __res
             double x = B.x[b], y = B.y[b], z = B.z[b];
             if (mode == 1) move_and_wrap(P, st, B, b, x, y, z);
             if (!isfinite(x + y + z)) atomicOr(const_cast<int*>(&st->overflow), 4);   // MPH_ERR_NONFINITE
-            k = cell_id(P, x, y, z);
+            const int cx = cell_axis(x, P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
+            const int cy = cell_axis(y, P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
+            const int cz = P.dim == 3 ? cell_axis(z, P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
+            k = cell_index(P, cx, cy, cz);   // (cell_id)
             key[p] = k;
+            // a lazy wall step (cmap set): a non-wall particle marks its coarse cell -- a plain store
+            // of the same byte by every marker, no atomic (the search reads the map, pass A clears it)
+            if (cmap && !dev_is_wall(B.type[b]))
+                cmap[coarse_index(P, cx >> kCoarseShift, cy >> kCoarseShift, cz >> kCoarseShift)] = 1;
             occ = seam_bits(P, x, y, z);
         }
         const int lane = threadIdx.x & 63;
@@ -319,7 +330,11 @@ __global__ __launch_bounds__(256) void k_rank_scatter(DevParams P, const int* __
     // map only decides which block runs which wave, so no launch of its own sits between the
     // search and pass A (its own launch after the search cost 0.45 % at rest, 0.24 % developed,
     // profiles/r05/split_in_sort/)
-    if (split && blockIdx.x == 0) xcd_split_block<256>(st);
+    // (split 2, a lazy step: the histograms its own kind of step fed last, and its search's map)
+    if (split && blockIdx.x == 0) {
+        xcd_split_block<256>(split == 2 ? st->seg_lwork : st->seg_work, st->xcd_frac);
+        if (split == 2) xcd_split_block<256>(st->seg_swork, st->xcd_sfrac);
+    }
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= dev_n(P)) return;
     const int k = key[p];
@@ -370,9 +385,11 @@ void launch_sort(const Launch& L, int mode)
     const DevParams& P = *L.P;
     const int n = P.n;
     if (n == 0) return;
-    const int split = n >= L.xcd_bal_min;   // the passes' XCD split (list_grid, k_rank_scatter)
+    // the passes' XCD split (list_grid, k_rank_scatter): 0 none, 1 a full step's, 2 a lazy step's
+    const int split = n >= L.xcd_bal_min ? (L.lazy ? 2 : 1) : 0;
     const dim3 g(blocks(n, 256)), b(256);
-    launch(L.prof, "prep", L.stream, k_prep, g, b, P, L.st, L.B, L.key, L.slot, L.cnt, mode, L.vsrc);
+    launch(L.prof, "prep", L.stream, k_prep, g, b, P, L.st, L.B, L.key, L.slot, L.cnt, mode, L.vsrc,
+           L.lazy ? L.cmap : nullptr);
     launch_scan(L.cnt, P.ncell, L.bsum, L.start, n, P.n_dev, L.stream, L.prof);
     launch(L.prof, "place", L.stream, k_place, g, b, P, L.st, L.key, L.slot, L.start, L.tmp, mode);
     launch(L.prof, "rank_scatter", L.stream, k_rank_scatter, g, b, P, L.key, L.start, L.tmp, L.B, L.A,
