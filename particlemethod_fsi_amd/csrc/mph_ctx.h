@@ -4,7 +4,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <string>
 #include <thread>
 #include <vector>
@@ -12,67 +11,7 @@
 #include "mph_internal.h"
 #include "mph_kernels.h"
 
-// Multi-GPU state of one rank (one process per GPU).  Local particle arrays hold
-// [owned | ghosts] in cell order; see mph_dist.hip for the step protocol.
-struct MphDist {
-    int rank = 0, nranks = 1, left = 0, right = 0;
-    mph::SlabGeom g{};
-    std::vector<double> cuts;     // interior slab boundaries (MphSlabOptions.cuts); empty: equal widths
-    int cap = 0;                  // capacity of every local per-particle array
-    int n_own = 0;                // owned particles after the last redistribution (host mirror)
-    // Every size of a step lives on the device (DistLayout), so a step has no host round trip and
-    // the RCCL transport replays whole steps from captured graphs.  Messages travel with fixed
-    // capacities (particles) per direction; a pair of neighbours derives the same capacity for
-    // its shared direction from the same counts (send of one = receive of the other).
-    mph::DistLayout* lay = nullptr;    // device
-    mph::DistLayout* hlay = nullptr;   // pinned host mirror (read after a step batch)
-    int cap_sl = 0, cap_sr = 0, cap_rl = 0, cap_rr = 0;
-    size_t region = 0;            // bytes of each of the four message buffers
-    mph::Soa C;                   // redistributed state (pre-sort order)
-    int* cls = nullptr;           // class of every B entry
-    // the kept entries of C stay in B (VSrc: C holds the received tail only, vidx[v] = where
-    // entry v lives in B); MPH_SLAB_VIRTUAL_C=0 copies them into C
-    int* vidx = nullptr;
-    bool virt = !(std::getenv("MPH_SLAB_VIRTUAL_C") && std::string(std::getenv("MPH_SLAB_VIRTUAL_C")) == "0");
-    int* bcnt = nullptr;          // per (class, block) counts -> offsets
-    int* boff = nullptr;
-    int* bsum = nullptr;
-    char *send_l = nullptr, *send_r = nullptr, *recv_l = nullptr, *recv_r = nullptr;  // device, resizable
-    hipStream_t stream2 = nullptr;                   // halo exchange beside the inner pass B
-    hipEvent_t ev_a = nullptr, ev_h = nullptr;       // pass A done / halo landed
-    // transport: RCCL communicator, or a host callback (tests / hosts without RCCL)
-    bool rccl = false;
-    bool graphs = false;          // steps replayed from captured graphs (RCCL transport)
-    // overlap: pass B of the inner particles overlaps the pass-A halo (and the early send below);
-    // off: halo, then one pass B over all particles.  MPH_SLAB_OVERLAP=1 / =0 forces the mode;
-    // unset (or "auto") the ranks choose it together at creation (overlap_probe, mph_dist.hip): on
-    // when the measured exchanges take longer than the split pass B costs over the single one
-    bool overlap = false;
-    int overlap_mode = [] {
-        const char* e = std::getenv("MPH_SLAB_OVERLAP");
-        return (e && std::string(e) == "1") ? 1 : ((e && std::string(e) == "0") ? 0 : -1);
-    }();
-    // the probe's measurements, max over ranks (ms): halo exchange, redistribution exchange (both at
-    // their message capacities), pass B split in two launches minus pass B in one; -1: not probed
-    double probe_ms[3] = {-1.0, -1.0, -1.0};
-    // early send: within a batch of steps, the redistribution messages of the next step leave
-    // while the interior pass B of this one runs (no elastic particles; MPH_SLAB_EARLY=0: off)
-    bool early = !(std::getenv("MPH_SLAB_EARLY") && std::string(std::getenv("MPH_SLAB_EARLY")) == "0");
-    int* wface = nullptr;                             // face-wavefront flags of the last pass B
-    hipEvent_t ev_s = nullptr, ev_x = nullptr;       // early messages packed / exchanged
-    char uid[128] = {0};          // ncclUniqueId
-    void* comm = nullptr;         // ncclComm_t
-    mph_host_exchange_fn host_fn = nullptr;
-    void* host_user = nullptr;
-    char* host_stage = nullptr;   // pinned staging for the host transport (4 messages)
-    // the last host-staged exchange's copies into the device (they read host_stage): the next
-    // exchange, possibly on the other stream, waits for them before the callback refills it
-    hipEvent_t ev_stage = nullptr;
-    bool stage_busy = false;
-    // elastic ghost slots (static): local slot indices sent to / received from each neighbour
-    int *ss_l = nullptr, *ss_r = nullptr, *sr_l = nullptr, *sr_r = nullptr;
-    int nss_l = 0, nss_r = 0, nsr_l = 0, nsr_r = 0;
-};
+struct MphDist;   // the slab decomposition's state of one rank (mph_dist.h)
 
 struct MphCtx {
     int device = 0;
@@ -175,6 +114,9 @@ inline int stencil_margin(const DevParams& P, int d)
     return (d == ca ? P.sa : kReach) + 1;
 }
 int ctx_state_status(MphCtx* c, const DevState& hs);   // kernel error flags -> MphStatus
+// the step graphs hold sizes and kernel arguments (monitors, slab message capacities): wait for
+// the stream and destroy them; the next step captures again
+int drop_graphs(MphCtx* c);
 
 void ctx_set_global_error(const std::string& msg);   // mph_last_error(NULL)
 // ids/n_glob: slab-local creation (the arrays hold n of n_glob particles, original indices ids)
@@ -193,7 +135,8 @@ int fetch(MphCtx* c, const T* d, std::vector<T>& h, size_t count)
 // original index of host input k (identity unless created slab-local)
 inline int glob_id(const MphCtx* c, int k) { return c->gid.empty() ? k : c->gid[k]; }
 
-// slab mode (mph_dist.hip)
+// slab mode (setup: mph_slab_geom.hip; steps: mph_dist.hip; output: mph_dist_output.hip; what those
+// units share among themselves: mph_dist.h)
 int dist_setup(MphCtx* c, const double* pos, std::vector<int>& owned);   // geometry + owned set
 // elastic slots of this rank: lsl = [owned | ghosts from the left | ghosts from the right] (global
 // slot ids), n_own owned; records the per-substep ghost exchange lists

@@ -13,7 +13,8 @@
 #include <string>
 #include <vector>
 
-#include "mph_ctx.h"
+#include "mph_dist.h"
+#include "mph_env.h"
 #include "mph_rows.h"
 
 using namespace mph;
@@ -66,22 +67,32 @@ int ctx_state_status(MphCtx* c, const DevState& hs)
     return MPH_OK;
 }
 
+int drop_graphs(MphCtx* c)
+{
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    for (hipGraphExec_t* g : {&c->graph1, &c->graph1t, &c->graph8})
+        if (*g) {
+            MPH_HIP_OK(c, hipGraphExecDestroy(*g));
+            *g = nullptr;
+        }
+    return MPH_OK;
+}
+
 void ctx_fill_launch(MphCtx* c)
 {
     Launch& L = c->L;
     set_uniforms(c->P);
     // MPH_LIST_FULL=1: the lists keep every neighbour within the search radius, like the reference's
     // Neighbor[] (mph_neighbor_rows needs them); else only those the passes' sums can take
-    if (std::getenv("MPH_LIST_FULL") && std::atoi(std::getenv("MPH_LIST_FULL")) == 1) c->P.rlf = 3.0e38f;
+    if (env_int("MPH_LIST_FULL", 0) == 1) c->P.rlf = 3.0e38f;
     // MPH_LAZY_WALLS=0: no lazy wall steps (enqueue_step), every step searches and sums every wall
     // wave; slab contexts never take them (a halo wall may have a fluid neighbour on the next rank)
-    c->lazy_walls = !c->dist && !(std::getenv("MPH_LAZY_WALLS") && std::atoi(std::getenv("MPH_LAZY_WALLS")) == 0);
+    c->lazy_walls = !c->dist && env_int("MPH_LAZY_WALLS", 1) != 0;
     L.P = &c->P;
     L.stream = c->stream;
     // work-balanced XCD map of the passes from this many particles (MPH_XCD_BAL_MIN: tests force it
     // on small cases, the default keeps it off below 2^20 where the split kernel costs more)
-    const char* bm = std::getenv("MPH_XCD_BAL_MIN");
-    L.xcd_bal_min = bm && *bm ? std::atoi(bm) : (1 << 20);
+    L.xcd_bal_min = env_is("MPH_XCD_BAL_MIN", "") ? (1 << 20) : env_int("MPH_XCD_BAL_MIN", 1 << 20);
     L.S = &c->Sd;
 }
 
@@ -338,8 +349,7 @@ static int init_host_state(MphCtx* c, CreateArgs& a)
     // InitialNeighbor + calculateNormalizer as kernels, launch_struct_init); in slab mode on the
     // host over the particles this rank was given, which also routes the static ghost slots
     // (dist_struct_setup).  MPH_STRUCT_INIT=host selects the host build everywhere.
-    const char* sie = std::getenv("MPH_STRUCT_INIT");
-    a.gpu_init = !c->dist && !(sie && std::string(sie) == "host");
+    a.gpu_init = !c->dist && !env_is("MPH_STRUCT_INIT", "host");
     MPH_CK(ctx_fail(c, build_structure(c->cfg, c->h, a.n, a.property, a.pos0, c->S, err, !a.gpu_init), err));
     make_dev_params(c->cfg, c->h, a.n, (int)c->S.orig.size(), c->P);
     return MPH_OK;
@@ -355,8 +365,7 @@ static int init_grid(MphCtx* c, const CreateArgs& a)
         // faces are long runs (whole wavefronts) at the ends of every plane (DevParams.perm;
         // MPH_SLAB_PERM=0 keeps (x, y, z); =1..4 force an order on any 3-D context, =force
         // orders a single 3-D context the z-slab way -- A/B timing and the parity tests)
-        const char* pe = std::getenv("MPH_SLAB_PERM");
-        const std::string pv = pe ? pe : "";
+        const std::string pv = env_str("MPH_SLAB_PERM");
         const bool zslab = a.cfg->dim == 3 && c->dist && c->dist->g.axis == 2;
         const bool forced = pv.size() == 1 && pv[0] >= '1' && pv[0] <= '4';
         c->P.perm = 0;
@@ -375,8 +384,7 @@ static int init_grid(MphCtx* c, const CreateArgs& a)
     c->P.seam_always = 0;
     // the grid's origin in an empty band of the initial particles (choose_grid_origin;
     // MPH_GRID_SHIFT=0 keeps dmin): the search's interior box is then in grid offsets
-    const char* gsh = std::getenv("MPH_GRID_SHIFT");
-    const bool shift = !(gsh && gsh[0] == '0');
+    const bool shift = env_str("MPH_GRID_SHIFT")[0] != '0';
     for (int d = 0; d < 3; ++d) {
         if (d == 2 && a.cfg->dim == 2) {
             c->P.inner_lo[d] = c->P.sinner_lo[d] = -1e300;
@@ -1424,18 +1432,6 @@ int mph_neighbor_rows(MphCtx* c, int first, int count, int* counts, int* ids, lo
 }
 
 // ---- per-step monitors (kernels: mph_monitor.hip) ----------------------------------------------
-
-// the step graphs hold the monitor kernels and their arguments: captured again at the next step
-static int drop_graphs(MphCtx* c)
-{
-    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
-    for (hipGraphExec_t* g : {&c->graph1, &c->graph1t, &c->graph8})
-        if (*g) {
-            MPH_HIP_OK(c, hipGraphExecDestroy(*g));
-            *g = nullptr;
-        }
-    return MPH_OK;
-}
 
 int mph_monitor_configure(MphCtx* c, const MphMonitorConfig* m)
 {

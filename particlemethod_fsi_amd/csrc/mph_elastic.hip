@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "mph_device.h"
+#include "mph_env.h"
 
 namespace mph {
 
@@ -485,8 +486,7 @@ constexpr long kStructLanesTarget = 8L * 1024 * 64;
 
 int struct_lanes(int nslots)
 {
-    const char* e = std::getenv("MPH_STRUCT_LANES");   // read per launch (graphs capture once)
-    const int forced = e ? std::atoi(e) : 0;
+    const int forced = env_int("MPH_STRUCT_LANES", 0);   // read per launch (graphs capture once)
     if (forced == 1 || forced == 2 || forced == 4 || forced == 8) return forced;
     int g = 1;
     while (g < 4 && (long)nslots * g < kStructLanesTarget) g *= 2;

@@ -223,7 +223,7 @@ void launch_struct_pack(const Launch& L, const double4* src, int w, const int* i
 void launch_struct_unpack(const Launch& L, const double4* buf, int w, const int* idx, int m, double4* dst);
 void launch_virial(const Launch& L, const Soa& X, double* vir, double* vpres);   // X: state in A order
 
-// slab decomposition (mph_dist.hip)
+// slab decomposition (mph_dist.hip; the left / right arguments are the two DistSide records' values)
 struct HaloFields {
     double* f[5];
     int nf;

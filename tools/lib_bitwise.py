@@ -6,7 +6,10 @@ lattice sampling produces (POINT_RUNS): the monitor ring of 11 steps with probes
 and a lattice slice and a small volume.
 
   MPH_GPU_LIB=.../libmph_gpu.so python tools/lib_bitwise.py run OUT.npz [cases...]
+  MPH_GPU_LIB=.../libmph_gpu.so MPH_SLAB_OVERLAP=1 python tools/lib_bitwise.py slab OUT.npz
   python tools/lib_bitwise.py compare A.npz B.npz        (exit 1 on any difference)
+
+`slab` saves the slab decomposition's results instead (SLAB_RUNS: 2-4 host-staged ranks on the one GPU).
 """
 import os
 import sys
@@ -35,6 +38,14 @@ POINT_RUNS = {
               [((0.001, 0.004, 0.0), (0.0013, 0.0017, 0.001), (40, 60, 1), 0),
                ((-0.002, 0.001, 0.0), (0.0009, 0.0009, 0.001), (9, 7, 1), 7)]),
 }
+
+
+# slab runs: (case, ranks, slab-local creation, fields); the fields of tests/test_gpu_dist.py
+SLAB_FIELDS = ["Position", "Velocity", "PressureP", "NeighborCount", "Force", "VolStrainP", "DivergenceP",
+               "DensityA", "GravityCenter", "PressureA", "Acceleration"]
+SLAB_STRUCT_FIELDS = SLAB_FIELDS + ["DeformGradient", "Strain", "Stress"]
+SLAB_RUNS = [("channel3d", 3, True, SLAB_FIELDS), ("channel2d", 4, False, SLAB_FIELDS),
+             ("bar2d", 3, False, SLAB_STRUCT_FIELDS), ("gate2d_sub", 2, True, SLAB_STRUCT_FIELDS)]
 
 
 def run_points(res):
@@ -66,20 +77,43 @@ def run(out, names):
     np.savez(out, **res)
 
 
+def run_slab(out):
+    """Every SLAB_RUNS case as host-staged ranks sharing the GPU (tests/dist_worker.py), the gathered
+    arrays of all checkpoints in one file.  Force MPH_SLAB_OVERLAP to 1 or 0: unset, the ranks time
+    their exchanges and two builds may choose differently."""
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dist_worker
+    res = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for case, world, local, fields in SLAB_RUNS:
+            path = os.path.join(tmp, "%s.npz" % case)
+            dist_worker.run_ranks(dist_worker.gpu_worker, world, case, [1, 5, 20], fields, path, local, None,
+                                  timeout=300)
+            with np.load(path) as z:
+                for k in z.files:
+                    res["slab/%s/%s" % (case, k)] = z[k]
+    np.savez(out, **res)
+
+
 def compare(a, b):
     A, B = np.load(a), np.load(b)
     bad = 0
-    for k in sorted(A.files):
+    assert sorted(A.files) == sorted(B.files), "the two runs saved different arrays"
+    keys = [k for k in sorted(A.files) if not k.endswith("/overlap")]   # the slab ranks' pass-B mode report: timings
+    for k in keys:
         same = np.array_equal(A[k], B[k])
         if not same:
             bad += 1
             print("DIFF", k, float(np.max(np.abs(A[k].astype(float) - B[k].astype(float)))))
-    print("compared %d arrays: %s" % (len(A.files), "bit-identical" if not bad else "%d differ" % bad))
+    print("compared %d arrays: %s" % (len(keys),"bit-identical" if not bad else "%d differ" % bad))
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
     if sys.argv[1] == "run":
         run(sys.argv[2], sys.argv[3:] or ["box3d", "box3d_st", "gate3d", "seam3d", "d1m"])
+    elif sys.argv[1] == "slab":
+        run_slab(sys.argv[2])
     else:
         sys.exit(compare(sys.argv[2], sys.argv[3]))

@@ -18,7 +18,7 @@ host staging's own copies.  The first run's figures are "serialised", the replay
 ("consistent": every rank ended with the recorded run's held and owned counts).  The replay
 exposed a race of the host transport (an exchange on one stream refilled the pinned staging
 buffers while the previous exchange's copies on the other stream still read them; a rank then
-diverged): each host-staged exchange now waits for the previous one's copies (mph_dist.hip).
+diverged): each host-staged exchange now waits for the previous one's copies (mph_transport.hip).
 
 usage: python tools/slab_serial.py [--case d16m] [--ranks 8] [--steps 4] [--warmup 2] [--replay]
 prints one JSON line: per-rank kernel averages, held/owned counts, their GPU time per step (the
