@@ -221,7 +221,11 @@ int mph_create(MphCtx** ctx, const MphConfig* cfg, int n, const int* property,
  * neighbours.  The output-only fields (Force, Acceleration, DensityA, VolStrainP, DivergenceP,
  * and GravityCenter/PressureA without surface tension) are stored by the last step of each
  * replayed batch, so after a successful mph_step they hold that step's values; after an error
- * they are undefined (the state itself -- Position, Velocity -- is the failing step's).        */
+ * they are undefined (the state itself -- Position, Velocity -- is the failing step's).
+ * The overflow is reported after the batch that held it.  A lean step (mph_lean_step_stats) counts
+ * only the pairs within the list radius (MaxRadius), so a count that passes 512 only through pairs
+ * of the shell MaxRadius < r <= MaxRadius + MARGIN raises the error at the batch's last step, which
+ * counts every pair: at most 7 steps later, and still in the mph_step call that took the step.  */
 int mph_step(MphCtx* ctx, int nsteps);
 /* Step batching for the drop-in loop that calls mph_step(ctx, 1) once per iteration
  * (INTEGRATION.md section 2); single contexts only (slab mode: MPH_ERR_ARG for on != 0).
@@ -543,6 +547,13 @@ int mph_list_layout(MphCtx* ctx, long long out6[6]);
  * reach.  Both stay 0 in slab mode, with monitors configured, or with MPH_LAZY_WALLS=0 in the
  * environment at creation.  A flush point.  Additive: no change of MPH_ABI_VERSION.            */
 int mph_idle_wall_stats(MphCtx* ctx, long long out2[2]);
+/* Lean steps, for verification: out2 = {steps whose search ran its lean form, steps
+ * whose pass A did} since the creation.  A lean step is a lazy step (above) of a context created
+ * without MPH_LEAN_STEPS=0: its search accepts only the pairs it stores and counts no
+ * NeighborCount (not with MPH_LIST_FULL=1), its pass A leaves out the DensityA and GravityCenter
+ * sums (not with surface tension, where pass B reads them).  Both stay 0 wherever no step is lazy.
+ * A flush point.  Additive: no change of MPH_ABI_VERSION.                                        */
+int mph_lean_step_stats(MphCtx* ctx, long long out2[2]);
 /* The neighbour lists of calculateNeighbor themselves (main.cpp:1764-1772: Neighbor[i][k] = j for
  * k < 512), for verification: the sets of the `count` particles [first, first + count) (original
  * order) from the last search, each row as ascending original indices (the reference's rows are in

@@ -88,6 +88,11 @@ void ctx_fill_launch(MphCtx* c)
     // MPH_LAZY_WALLS=0: no lazy wall steps (enqueue_step), every step searches and sums every wall
     // wave; slab contexts never take them (a halo wall may have a fluid neighbour on the next rank)
     c->lazy_walls = !c->dist && env_int("MPH_LAZY_WALLS", 1) != 0;
+    // MPH_LEAN_STEPS=0: the lazy steps launch the kernels of the full steps' arithmetic (enqueue_step);
+    // the lean search also needs the list radius below the search radius' FP32 band (lean_search_ok:
+    // not with MPH_LIST_FULL=1)
+    L.lean_ok = env_int("MPH_LEAN_STEPS", 1) != 0;
+    L.lean_search = L.lean_ok && lean_search_ok(c->P);
     L.P = &c->P;
     L.stream = c->stream;
     // work-balanced XCD map of the passes from this many particles (MPH_XCD_BAL_MIN: tests force it
@@ -139,6 +144,10 @@ void enqueue_step(const Launch& L, bool last, hipEvent_t* ev = nullptr)
     if (ev) (void)hipEventRecord(ev[0], L.stream);
     Launch La = L;
     La.lazy = !last && L.cmap && !L.mon;
+    // a lean step: a lazy step that also leaves out what it would compute only to drop it -- the
+    // search NeighborCount and the shell's candidates, pass A the DensityA and GravityCenter sums when
+    // they are not stored (below).  Under the conditions of a lazy step and no others.
+    La.lean = La.lazy && L.lean_ok;
     launch_sort(La, 1);
     if (!last) {
         La.dens_a = La.vstrain = La.divp = nullptr;
@@ -1366,6 +1375,22 @@ int mph_idle_wall_stats(MphCtx* c, long long out[2])
     for (unsigned v : seg) idle += v;
     out[0] = idle;
     out[1] = (long long)steps;
+    return MPH_OK;
+}
+
+int mph_lean_step_stats(MphCtx* c, long long out[2])
+{
+    if (!c || !out) return MPH_ERR_ARG;
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    unsigned long long steps[2] = {0, 0};   // lean_search_steps, lean_pass_a_steps
+    static_assert(offsetof(DevState, lean_pass_a_steps) == offsetof(DevState, lean_search_steps) + sizeof(steps[0]),
+                  "the two counters are read in one copy");
+    MPH_HIP_OK(c, hipMemcpy(steps, reinterpret_cast<const char*>(c->L.st) + offsetof(DevState, lean_search_steps),
+                            sizeof(steps), hipMemcpyDeviceToHost));
+    out[0] = (long long)steps[0];
+    out[1] = (long long)steps[1];
     return MPH_OK;
 }
 

@@ -136,6 +136,12 @@ struct Launch {
     unsigned char* cmap = nullptr;
     int cmap_bytes = 0;
     bool lazy = false;
+    // Lean steps: a lazy step also drops the per-candidate and per-neighbour
+    // work whose results it does not store.  lean_ok: the context takes them (MPH_LEAN_STEPS, set at
+    // creation); lean_search: and its radii let the search (lean_search_ok); lean: this step is one
+    // (enqueue_step: lazy && lean_ok) -- the search takes its lean form when lean_search holds, pass A
+    // its own when neither GravityCenter nor DensityA is stored (launch_pass_a)
+    bool lean_ok = false, lean_search = false, lean = false;
     // pass A products (A order): pressure values, gravity centre (GC, PressureA), sums
     double *pres = nullptr, *gx = nullptr, *gy = nullptr, *gz = nullptr, *pa = nullptr;
     double *dens_a = nullptr, *vstrain = nullptr, *divp = nullptr;

@@ -162,7 +162,14 @@ struct DevParams {
     // shell MaxRadius < r <= MaxRadius + MARGIN that the reference's list carries and NeighborCount
     // counts.  FLT_MAX (MPH_LIST_FULL=1): the reference's whole list.
     float rlf;
+    // The lean search's column-trimming bound (a lean step: mph_kernels.h Launch.lean), in the place
+    // rc2_trim has in the full search, as the FP32 value the trimming runs in.  (The last member, in
+    // the struct's tail padding: the kernels' argument offsets are those of the builds before it.)
+    float rl_trimf;
 };
+static_assert(offsetof(DevParams, rl_trimf) == offsetof(DevParams, rlf) + sizeof(float) &&
+              offsetof(DevParams, rl_trimf) + sizeof(float) == sizeof(DevParams),
+              "rl_trimf fills the tail padding behind rlf: the size is the one without it");
 
 // Derived uniforms of DevParams (same expressions the kernels used, so the same bits).
 inline void set_uniforms(DevParams& P)
@@ -186,7 +193,24 @@ inline void set_uniforms(DevParams& P)
     P.rc2f_hi = (float)(P.rc2 * (1.0 + delta));
     const double rmax = std::fmax(std::fmax(P.ra, P.rg), std::fmax(P.rp, P.rv));
     P.rlf = (float)(rmax * rmax * (1.0 + delta));
+    // The lean search trims its columns to the list radius.  It stores candidate j exactly when the
+    // FP32 r^2 of the records, r2f, is <= rlf.  r2f is within delta (relative) of the exact r^2, and
+    // rlf within 2^-24 of rmax^2 (1 + delta), so
+    //     r2f <= rlf  =>  r^2 <= r2f (1 + delta) <= rmax^2 (1 + delta)^2 (1 + 2^-24) < rmax^2 (1 + delta)^3,
+    // and with the cell geometry's 4e-6 of rc2_trim the bound is rmax^2 (1 + delta)^3 (1 + 4e-6): every
+    // stored candidate lies inside the ranges trimmed to it.  Never wider than the full search's
+    // bound (it is narrower whenever the lean search runs, lean_search_ok below); scan_candidates_lds
+    // rounds it outwards once more (kUp), as it does rc2_trim.
+    const double d1 = 1.0 + delta;
+    P.rl_trimf = (float)std::fmin(rmax * rmax * d1 * d1 * d1 * (1.0 + 4e-6), P.rc2_trim);
 }
+
+// The lean search (mph_search.hip scan_candidates_lds<.., LEAN>) accepts with the one test
+// r2f <= rlf.  That is the full search's stored set only while the list radius lies below the FP32
+// band of the search radius: the full search stores live && a && r2f <= rlf, and r2f <= rlf <=
+// rc2f_lo gives a = true without the FP64 test.  False under MPH_LIST_FULL=1 (rlf = FLT_MAX) and
+// for a MARGIN so small that the two radii meet: the lazy steps then keep the full acceptance.
+inline bool lean_search_ok(const DevParams& P) { return P.rlf <= P.rc2f_lo; }
 
 // Lazy wall steps.  On a step whose output-only fields are not stored, a
 // wall particle with no fluid or structure particle in reach is read by nobody: its neighbours are
@@ -251,6 +275,10 @@ struct DevState {
     int seg_swork[kXcdSegs];
     int xcd_sfrac[9];
     int xcd_spad[3];
+    // lean steps (Launch.lean), counted like lazy_steps: the lazy steps whose search ran its lean
+    // form, and those whose pass A did, since the creation -- each bumped by block 0 of its kernel
+    // (mph_lean_step_stats).  Behind every older member, whose offsets the other kernels keep.
+    unsigned long long lean_search_steps, lean_pass_a_steps;
 };
 // the part of DevState the host reads back after steps (the error bits and the step scalars)
 constexpr size_t kStateHead = offsetof(DevState, seg_work);

@@ -30,7 +30,10 @@ struct PassA {
 // viscous force; (dvx, dvy, dvz) = v_j - v_i.  No implicit contraction: every accumulation is an
 // explicit fma, so this branching form and the selecting form of the round-3 fused kernel
 // give the same bits (a deselected fma(a, 0, acc) leaves acc unchanged).
-template <bool FORCE, bool EQR = false>
+// LEAN (a lean step's pass A, launch_pass_a): neither DensityA nor GravityCenter is stored, so their
+// sums (o.da, o.g0..g2) and the InteractionRatio they read are left out; every other sum is the
+// same expression in the same order.
+template <bool FORCE, bool EQR = false, bool LEAN = false>
 __device__ __forceinline__ void pass_a_term(const DevParams& P, const double* s_ratio, const double* s_mu, int ti,
                                             int tj, bool solid, double q0, double q1, double q2, double r2,
                                             double dvx, double dvy, double dvz, PassA& o)
@@ -57,12 +60,14 @@ __device__ __forceinline__ void pass_a_term(const DevParams& P, const double* s_
                 o.s2 = fma(c, q2, o.s2);
             }
             if (!solid) {
-                const double ratio = s_ratio[ti * kTypes + tj];
-                o.da = fma(ratio, (P.ca * t) * omt2, o.da);
-                const double w = (ratio * (P.cg * omt2)) * P.rg_r2g;
-                o.g0 = fma(q0, w, o.g0);
-                o.g1 = fma(q1, w, o.g1);
-                o.g2 = fma(q2, w, o.g2);
+                if (!LEAN) {
+                    const double ratio = s_ratio[ti * kTypes + tj];
+                    o.da = fma(ratio, (P.ca * t) * omt2, o.da);
+                    const double w = (ratio * (P.cg * omt2)) * P.rg_r2g;
+                    o.g0 = fma(q0, w, o.g0);
+                    o.g1 = fma(q1, w, o.g1);
+                    o.g2 = fma(q2, w, o.g2);
+                }
                 if (FORCE && strict) {
                     const double c = ((s_mu[ti * kTypes + tj] * omt) * dot) * ((ir * ir) * ir);
                     o.v0 = fma(c, q0, o.v0);
@@ -88,18 +93,20 @@ __device__ __forceinline__ void pass_a_term(const DevParams& P, const double* s_
         }
     }
     if (!solid) {
-        const double ratio = s_ratio[ti * kTypes + tj];
-        if (r2 <= P.ra2) {
-            const double t = r * P.inv_ra;
-            const double omt = 1.0 - t;
-            o.da = fma(ratio, ((P.ca * t) * omt) * omt, o.da);
-        }
-        if (r2 <= P.rg2) {
-            const double omt = 1.0 - r * P.inv_rg;
-            const double w = (ratio * ((P.cg * omt) * omt)) * P.rg_r2g;
-            o.g0 = fma(q0, w, o.g0);
-            o.g1 = fma(q1, w, o.g1);
-            o.g2 = fma(q2, w, o.g2);
+        if (!LEAN) {
+            const double ratio = s_ratio[ti * kTypes + tj];
+            if (r2 <= P.ra2) {
+                const double t = r * P.inv_ra;
+                const double omt = 1.0 - t;
+                o.da = fma(ratio, ((P.ca * t) * omt) * omt, o.da);
+            }
+            if (r2 <= P.rg2) {
+                const double omt = 1.0 - r * P.inv_rg;
+                const double w = (ratio * ((P.cg * omt) * omt)) * P.rg_r2g;
+                o.g0 = fma(q0, w, o.g0);
+                o.g1 = fma(q1, w, o.g1);
+                o.g2 = fma(q2, w, o.g2);
+            }
         }
         if (FORCE && r2 < P.rv2) {
             // s_mu holds -cvis cdv vol mu_ij (k_pass_a): dw_v(r) = -cdv (1 - r / rv)
@@ -181,7 +188,7 @@ __device__ __forceinline__ void list_batch(const NbrList& NL, Bits bits_of, int 
     }
 }
 
-template <bool FAST, int DIM, bool EQR, int U = MPH_UA>
+template <bool FAST, int DIM, bool EQR, bool LEAN, int U = MPH_UA>
 __device__ __forceinline__ void pass_a_loop(const DevParams& P, const double* s_ratio, const double* s_mu,
                                             const Soa& A,
                                             NbrList NL, bool plain, const unsigned* lm, int end, int ti,
@@ -214,8 +221,8 @@ __device__ __forceinline__ void pass_a_loop(const DevParams& P, const double* s_
             const double q0 = image_exact<FAST>(X[u] - xi, P.dw[0], P.hw[0], P.w075[0]);
             const double q1 = image_exact<FAST>(Y[u] - yi, P.dw[1], P.hw[1], P.w075[1]);
             const double q2 = image_exact<FAST || DIM == 2>(Z[u] - zi, P.dw[2], P.hw[2], P.w075[2]);
-            pass_a_term<true, EQR>(P, s_ratio, s_mu, ti, TT[u], solid, q0, q1, q2, r2_exact(q0, q1, q2),
-                                   VX[u] - vxi, VY[u] - vyi, VZ[u] - vzi, o);
+            pass_a_term<true, EQR, LEAN>(P, s_ratio, s_mu, ti, TT[u], solid, q0, q1, q2, r2_exact(q0, q1, q2),
+                                         VX[u] - vxi, VY[u] - vyi, VZ[u] - vzi, o);
         }
     }
 }
@@ -228,7 +235,9 @@ __device__ __forceinline__ void pass_a_loop(const DevParams& P, const double* s_
 #else
 #define MPH_PA_ATTR
 #endif
-template <int DIM>
+// LEAN: a lean step's pass A (pass_a_term; pout.gx and pout.dens_a are null), a kernel of its own, so
+// that the full one keeps its code.
+template <int DIM, bool LEAN = false>
 __global__ __launch_bounds__(MPH_LB) MPH_PA_ATTR void k_pass_a(DevParams P, const DevTables* __restrict__ T, Soa A,
                                                 const int* __restrict__ nbr,
                                                 const int* __restrict__ ncount,
@@ -238,6 +247,9 @@ __global__ __launch_bounds__(MPH_LB) MPH_PA_ATTR void k_pass_a(DevParams P, cons
                                                 unsigned char* __restrict__ cmap, int cmap_bytes)
 {
     const int n = dev_n(P);
+    // counted like the lazy steps in the search (one writer; st is written by no other kernel of
+    // the step from here on)
+    if (LEAN && blockIdx.x == 0 && threadIdx.x == 0) const_cast<DevState*>(st)->lean_pass_a_steps += 1;
     // a lazy wall step (cmap set): its search, the coarse map's only reader, is done -- back to
     // all zero for the next step's k_prep, 16 bytes per thread of the grid's first blocks
     if (cmap)
@@ -286,11 +298,14 @@ __global__ __launch_bounds__(MPH_LB) MPH_PA_ATTR void k_pass_a(DevParams P, cons
     // the interior waves; waves at a periodic face keep the general form
     const bool eqr = pass_a_equal_radii(P);
     if (fast && eqr)
-        pass_a_loop<true, DIM, true>(P, s_ratio, s_mu, A, NL, plain, lm, end, ti, solid, xi, yi, zi, vxi, vyi, vzi, o);
+        pass_a_loop<true, DIM, true, LEAN>(P, s_ratio, s_mu, A, NL, plain, lm, end, ti, solid, xi, yi, zi, vxi, vyi,
+                                           vzi, o);
     else if (fast)
-        pass_a_loop<true, DIM, false>(P, s_ratio, s_mu, A, NL, plain, lm, end, ti, solid, xi, yi, zi, vxi, vyi, vzi, o);
+        pass_a_loop<true, DIM, false, LEAN>(P, s_ratio, s_mu, A, NL, plain, lm, end, ti, solid, xi, yi, zi, vxi, vyi,
+                                            vzi, o);
     else
-        pass_a_loop<false, DIM, false>(P, s_ratio, s_mu, A, NL, plain, lm, end, ti, solid, xi, yi, zi, vxi, vyi, vzi, o);
+        pass_a_loop<false, DIM, false, LEAN>(P, s_ratio, s_mu, A, NL, plain, lm, end, ti, solid, xi, yi, zi, vxi, vyi,
+                                             vzi, o);
     pass_a_finish(P, T, ti, i, o, pout, xi, yi, zi);
 }
 
@@ -612,11 +627,18 @@ void launch_pass_a(const Launch& L)
 {
     const DevParams& P = *L.P;
     if (P.n == 0) return;
-    by_dim(P.dim, [&](auto D) {
-        launch(L.prof, "pass_a", L.stream, k_pass_a<decltype(D)::value>,
-               dim3(list_grid(P.n, L.lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T,
-               L.A, L.nbr, L.ncount, L.lhdr, L.lgap, pass_a_out(L), L.st, L.lazy ? L.cmap : nullptr, L.cmap_bytes);
-    });
+    // a lean step that stores neither GravityCenter / PressureA nor the diagnostics (enqueue_step:
+    // not the batch's last step, no surface tension) leaves their sums out
+    const bool lean = L.lean && L.lazy && !L.gx && !L.dens_a;
+    auto go = [&](auto LEAN) {
+        by_dim(P.dim, [&](auto D) {
+            launch(L.prof, "pass_a", L.stream, k_pass_a<decltype(D)::value, decltype(LEAN)::value>,
+                   dim3(list_grid(P.n, L.lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T, L.A, L.nbr, L.ncount,
+                   L.lhdr, L.lgap, pass_a_out(L), L.st, L.lazy ? L.cmap : nullptr, L.cmap_bytes);
+        });
+    };
+    if (lean) go(std::true_type{});
+    else go(std::false_type{});
 }
 
 // calculateNeighbor + the pass-A sums

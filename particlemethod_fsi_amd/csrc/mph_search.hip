@@ -196,7 +196,18 @@ __device__ __forceinline__ int scan_candidates(const DevParams& P, const Soa& A,
 // the same counter -- each made it emit vmcnt(0) right after issuing them: two round trips per
 // column), so they are issued in asm (start_load), which hipcc does not count, and every path of a
 // column ends in an explicit vmcnt(0) before the next column reads them (start_landed).
-template <int DIM, int PERM, int SB = MPH_SB, int CAP = MPH_LDS_CAP>
+//
+// LEAN (a lean step's search, enqueue_step; the caller has checked lean_search_ok): the stored list
+// is {live && r2f <= rlf} (the full form stores live && a && r2f <= rlf, and rlf <= rc2f_lo makes a
+// true wherever r2f <= rlf), and NeighborCount has no reader on such a step.  So the columns are
+// trimmed to the list radius (DevParams.rl_trimf: every stored candidate lies inside, set_uniforms),
+// a candidate is accepted by that one compare -- no band, no ballots, no FP64 test -- and the
+// counter's total field advances with the stored one.  Candidate order, group ends, row jumps and
+// the lhdr / lgap bytes are the full form's, so every lane stores the same entries in the same
+// rows; the return value counts the stored entries.  (A window that only the wider ranges push past
+// the staging area takes the gather loop in the full form alone, which then also stores the
+// shell's pairs: more rows, the same entries within the passes' radii in the same order.)
+template <int DIM, int PERM, bool LEAN, int SB = MPH_SB, int CAP = MPH_LDS_CAP>
 __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa& A, const int* start,
                                                    int i, bool act, double xi, double yi, double zi,
                                                    int cx, int cy, int cz, int* out, double* sx, int* stored,
@@ -238,7 +249,7 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
     // Each added rounding is below 1e-5 cells or 2^-24 of a cell width, far inside the margins.
     constexpr float kDn = 1.0f - 1.0f / (1 << 20), kUp = 1.0f + 1.0f / (1 << 19);
     constexpr float kBias = 32.0f;
-    const float rcm2f = act ? (float)P.rc2_trim * kUp : -1.0f;
+    const float rcm2f = act ? (LEAN ? P.rl_trimf : (float)P.rc2_trim) * kUp : -1.0f;
     float gx2f = 0.0f;
     const int c0l = cc[X::A0], c1l = DIM == 3 ? cc[X::A1] : 0;
     const float cw0f = (float)cw0, cw1f = (float)cw1;
@@ -415,6 +426,14 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
                         bool live = true;
                         if (u > 0) live = j < je;
                         if (SELF) live = live & (j != i);
+                        if constexpr (LEAN) {
+                            if (live & (r2f <= P.rlf)) {
+                                __builtin_amdgcn_raw_buffer_store_b32(nbr_entry(j, __float_as_int(r[u].w)), tile_rsrc,
+                                                                      soff & kSoffMask, 0, 0);
+                                soff += kListKeep;
+                            }
+                            continue;
+                        }
                         // two compares; the band as wave masks (SALU), its lane bit read only inside
                         // the rare branch
                         const bool le_lo = r2f <= lof, le_hi = r2f <= hif;
@@ -485,7 +504,7 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
     }
     *stored = soff_stored(soff);  // the list's rows, gaps included (entries: r^2 <= P.rlf)
     if (lane == 0) *hdr_byte(7) = (unsigned char)(jumps > kMaxJumps ? jumps - kMaxJumps - 1 : jumps);
-    return soff_total(soff);      // every neighbour (NeighborCount)
+    return soff_total(soff);      // every neighbour (NeighborCount; LEAN: the stored entries)
 }
 
 // Slab mode: wface[w] = 1 when wave w holds an owned particle within slab_h of a slab face (pass B
@@ -519,7 +538,7 @@ __device__ __forceinline__ void slab_wave_flag(const DevParams& P, const Soa& A,
 // of ghosts does, and is counted in its run of the waves like the work histogram (never one same-
 // address atomic per wave, see neighbors_body).  It runs ahead of neighbors_body on values of its
 // own, which end with it: the search's register budget is the parent's.
-template <int DIM>
+template <int DIM, bool LEAN>
 __device__ __forceinline__ bool wave_idle_walls(const DevParams& P, const Soa& A, const unsigned char* cmap,
                                                 DevState* st, int* ncount, int* nbcount,
                                                 unsigned long long* lhdr, int i, int n)
@@ -553,7 +572,7 @@ __device__ __forceinline__ bool wave_idle_walls(const DevParams& P, const Soa& A
     }
     if (__ballot(hit != 0)) return false;
     if (live) ncount[i] = 0;
-    if (live) nbcount[i] = 0;
+    if (!LEAN && live) nbcount[i] = 0;   // (a lean step stores no NeighborCount)
     if ((threadIdx.x & 63) == 0) {
         lhdr[tile] = 0;
         atomicAdd(&st->idle_waves[(int)(((long long)tile * kXcdSegs) / ((n + 63) >> 6))], 1u);
@@ -564,7 +583,9 @@ __device__ __forceinline__ bool wave_idle_walls(const DevParams& P, const Soa& A
 // ncount: the rows of each particle's stored list, gaps included (what the passes walk; the
 // entries, r^2 <= P.rlf, are the rows outside the gaps, RowMask); nbcount: NeighborCount, every
 // neighbour within the search radius; lhdr / lgap: the row jumps (RowMask)
-template <int DIM, int PERM>
+// LEAN (a lean step, scan_candidates_lds): nbcount is not stored -- it has no reader before the
+// batch's last step, which is full -- and the overflow flag follows the stored entries.
+template <int DIM, int PERM, bool LEAN>
 __device__ __forceinline__ int neighbors_body(const DevParams& P, const Soa& A, const int* start, int* nbr,
                                                int* ncount, int* nbcount, unsigned long long* lhdr,
                                                unsigned long long* lgap, DevState* st, double* stage, int i)
@@ -592,7 +613,7 @@ __device__ __forceinline__ int neighbors_body(const DevParams& P, const Soa& A, 
     const int cz = DIM == 3 ? cell_axis(zi, P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
     int* out = nbr + (size_t)(i >> 6) * kTileStride + (i & 63);
     if (fast) {
-        cnt = scan_candidates_lds<DIM, PERM>(P, A, start, i, own, xi, yi, zi, cx, cy, cz, out, stage, &stored,
+        cnt = scan_candidates_lds<DIM, PERM, LEAN>(P, A, start, i, own, xi, yi, zi, cx, cy, cz, out, stage, &stored,
                                              lgap, lhdr);
     } else {
         if (own)
@@ -601,7 +622,7 @@ __device__ __forceinline__ int neighbors_body(const DevParams& P, const Soa& A, 
         if ((threadIdx.x & 63) == 0) lhdr[tile] = 0;   // plain rows
     }
     if (live) ncount[i] = stored;
-    if (live) nbcount[i] = cnt;
+    if (!LEAN && live) nbcount[i] = cnt;
     // overflow flag (main.cpp:1766-1768 is the reference's limit).  No per-step statistics here:
     // one same-address device atomic per wave serialises at ~11 ns each (21.8k waves at D1M took
     // 0.5 ms); mph_neighbor_stats reduces ncount on demand.
@@ -618,7 +639,8 @@ __device__ __forceinline__ int neighbors_body(const DevParams& P, const Soa& A, 
 // LAZY: a lazy wall step's search (cmap set); a full step's is a kernel of its own, so that it keeps
 // the registers it had before the lazy steps (their map and histograms cost the search ~50 SGPR
 // spills and 1.3 % at D1M when both were one kernel).
-template <int DIM, int PERM, bool LAZY>
+// LEAN: a lean step's search (LAZY too: scan_candidates_lds<.., LEAN>, neighbors_body), a third kernel.
+template <int DIM, int PERM, bool LAZY, bool LEAN = false>
 __global__ __launch_bounds__(MPH_LB) __attribute__((amdgpu_waves_per_eu(MPH_NB_WPE))) void k_neighbors(
     DevParams P, Soa A, const int* __restrict__ start, int* __restrict__ nbr, int* __restrict__ ncount,
     int* __restrict__ nbcount, unsigned long long* __restrict__ lhdr, unsigned long long* __restrict__ lgap,
@@ -626,7 +648,11 @@ __global__ __launch_bounds__(MPH_LB) __attribute__((amdgpu_waves_per_eu(MPH_NB_W
 {
     const unsigned char* cmap = LAZY ? cmap_arg : nullptr;
     const int n = dev_n(P);
-    if (cmap && blockIdx.x == 0 && threadIdx.x == 0) st->lazy_steps += 1;   // (the one writer)
+    static_assert(LAZY || !LEAN, "only a lazy step is lean");
+    if (cmap && blockIdx.x == 0 && threadIdx.x == 0) {   // (the one writer)
+        st->lazy_steps += 1;
+        if (LEAN) st->lean_search_steps += 1;
+    }
     // the wave's block: a lazy step with the XCD split takes the map made from the last lazy step's
     // search costs (list_block over xcd_sfrac, a list_grid launch), else the equal ranges
     int tb;
@@ -641,9 +667,9 @@ __global__ __launch_bounds__(MPH_LB) __attribute__((amdgpu_waves_per_eu(MPH_NB_W
     const int i = tb * blockDim.x + threadIdx.x;
     slab_wave_flag(P, A, i, n, wface);
     // a lazy wall step (cmap set): an idle wave of walls only adds its fixed costs to the histograms
-    const bool idle = cmap && wave_idle_walls<DIM>(P, A, cmap, st, ncount, nbcount, lhdr, i, n);
+    const bool idle = cmap && wave_idle_walls<DIM, LEAN>(P, A, cmap, st, ncount, nbcount, lhdr, i, n);
     const int cnt = idle ? 0
-                         : neighbors_body<DIM, PERM>(P, A, start, nbr, ncount, nbcount, lhdr, lgap, st,
+                         : neighbors_body<DIM, PERM, LEAN>(P, A, start, nbr, ncount, nbcount, lhdr, lgap, st,
                                                      stage[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)], i);
     if (bal) {
         if (cmap) add_wave_work(st->seg_lwork, cnt, i, n, st->seg_swork, idle);
@@ -659,10 +685,17 @@ void launch_neighbors(const Launch& L)
     if (P.n == 0) return;
     const int bal = P.n >= L.xcd_bal_min;
     const bool lazy = L.lazy && L.cmap;
+    // a lean step's search, when the radii allow it (lean_search_ok; asked again here for a caller
+    // that changed rlf after the context was filled, as virial_full_lists does)
+    const bool lean = lazy && L.lean && L.lean_search && lean_search_ok(P);
     by_dim(P.dim, [&](auto D) {
         constexpr int DIM = decltype(D)::value;
         auto go = [&](auto PERM) {
-            if (lazy)
+            if (lean)
+                launch(L.prof, "neighbors", L.stream, k_neighbors<DIM, decltype(PERM)::value, true, true>,
+                       dim3(bal ? list_grid(P.n, true) : blocks(P.n, MPH_LB)), dim3(MPH_LB), P, L.A, L.start, L.nbr,
+                       L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, bal, L.cmap);
+            else if (lazy)
                 launch(L.prof, "neighbors", L.stream, k_neighbors<DIM, decltype(PERM)::value, true>,
                        dim3(bal ? list_grid(P.n, true) : blocks(P.n, MPH_LB)), dim3(MPH_LB), P, L.A, L.start, L.nbr,
                        L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, bal, L.cmap);

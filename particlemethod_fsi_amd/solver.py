@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "mph_set_step_batching", "mph_neighbor_rows", "mph_dist_overlap", "mph_list_layout",
     "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
     "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
+    "mph_lean_step_stats",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -221,12 +222,14 @@ def load_library() -> ctypes.CDLL:
         "mph_sample_grid_timed": (ip, [vp, ctypes.POINTER(MphSampleGrid), vp, ctypes.POINTER(ctypes.c_double), vp]),
         "mph_write_vti_arrays": (ip, [ctypes.c_char_p, ctypes.POINTER(MphSampleGrid), vp]),
         "mph_idle_wall_stats": (ip, [vp, vp]),
+        "mph_lean_step_stats": (ip, [vp, vp]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
                 "mph_dist_overlap", "mph_profile_graphs", "mph_list_stats", "mph_list_layout",
                 "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
-                "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats"}
+                "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
+                "mph_lean_step_stats"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -650,6 +653,16 @@ class MphSolver:
         if hasattr(self._L, "mph_idle_wall_stats"):
             _check(self._L.mph_idle_wall_stats(self._h, a.ctypes.data), self._h)
         return {"idle_wave_steps": int(a[0]), "lazy_steps": int(a[1])}
+
+    def lean_step_stats(self) -> dict:
+        """Lean steps since the creation (mph_lean_step_stats): the lazy steps whose search ran its
+        lean form ("search_steps") and those whose pass A did ("pass_a_steps"); both 0 wherever no
+        step is lazy, with MPH_LEAN_STEPS=0 at creation, or from a library built before the entry
+        point."""
+        a = np.zeros(2, np.int64)
+        if hasattr(self._L, "mph_lean_step_stats"):
+            _check(self._L.mph_lean_step_stats(self._h, a.ctypes.data), self._h)
+        return {"search_steps": int(a[0]), "pass_a_steps": int(a[1])}
 
     def neighbor_rows(self, first: int = 0, count: int | None = None):
         """(counts, offsets, ids): the neighbour sets of the particles [first, first + count) from

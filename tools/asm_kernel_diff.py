@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Per-kernel comparison of two sets of gfx950 assembly listings (hipcc --cuda-device-only -S):
+r"""Per-kernel comparison of two sets of gfx950 assembly listings (hipcc --cuda-device-only -S):
 did moving code between translation units change any kernel?
 
-    asm_kernel_diff.py --old OLD.s [OLD.s ...] --new NEW.s [NEW.s ...] [--show]
+    asm_kernel_diff.py --old OLD.s [OLD.s ...] --new NEW.s [NEW.s ...] [--show] [--rename RE REPL ...]
 
 Each listing is split at its kernel symbols (the .amdhsa_kernel names).  A kernel is its instruction
 stream (from its label to .Lfunc_end) and its descriptor (.amdhsa_* lines, and the .set lines the
@@ -10,7 +10,10 @@ descriptor's expressions refer to: VGPRs, SGPRs, LDS, scratch).  Before comparin
 a kernel's place in its file is normalised: `;` comments are dropped, the function number in local
 labels (.LBB<n>_, .Lfunc_*<n>, .LJTI<n>_, .LCPI<n>_) is blanked, and the per-unit __hip_cuid_* symbol is
 masked.  Prints SAME or DIFF per kernel, and ONLY-OLD / ONLY-NEW for a kernel of one side; exits 1
-unless every kernel is SAME.  --show adds a unified diff of every DIFF.  CPU only.
+unless every kernel is SAME.  --show adds a unified diff of every DIFF.  --rename RE REPL (repeatable)
+rewrites the new listings' text with re.sub before they are split, for a template that gained a
+parameter: `--rename 'k_pass_aILi(\d)ELb0EE' 'k_pass_aILi\1EE'` gives k_pass_a<D, false> the name
+k_pass_a<D> had.  CPU only.
 """
 import argparse
 import difflib
@@ -28,9 +31,12 @@ def normalise(line):
     return " ".join(line.split())
 
 
-def kernels(path):
+def kernels(path, renames=()):
     """{symbol: (instruction lines, descriptor lines)} of one listing"""
-    lines = open(path).read().split("\n")
+    text = open(path).read()
+    for pat, repl in renames:
+        text = re.sub(pat, repl, text)
+    lines = text.split("\n")
     names = [l.split()[1] for l in lines if l.strip().startswith(".amdhsa_kernel ")]
     out = {}
     for sym in names:
@@ -79,12 +85,14 @@ def main():
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
     ap.add_argument("--show", action="store_true", help="print a unified diff of every DIFF")
+    ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("RE", "REPL"),
+                    help="re.sub applied to the new listings' text")
     a = ap.parse_args()
     side = []
-    for paths in (a.old, a.new):
+    for paths, renames in ((a.old, ()), (a.new, a.rename)):
         ks = {}
         for p in paths:
-            for sym, k in kernels(p).items():
+            for sym, k in kernels(p, renames).items():
                 assert sym not in ks, "kernel in two listings of one side: " + sym
                 ks[sym] = k
         side.append(ks)
