@@ -1,9 +1,14 @@
-// mph_ctx.h -- the device context behind the C ABI (include/mph_gpu.h), shared by the single-GPU
-// implementation (mph_ctx.hip) and the slab-decomposed multi-GPU step (mph_dist.hip).
+// mph_ctx.h -- the device context behind the C ABI (include/mph_gpu.h) and what its host units share:
+// mph_ctx.hip (errors, allocation, the helpers below, destroy), mph_create.hip (the create phases),
+// mph_step.hip (the step sequencer: graphs, batching, phase timing), mph_fields.hip (download, upload,
+// virial, writers), mph_profile.hip (per-kernel profilers, list and counter diagnostics),
+// mph_observe.hip (host half of the monitors and of the lattice sampling), and the slab-decomposed
+// multi-GPU step (mph_dist.h and its units).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <map>
 #include <string>
 #include <thread>
 #include <vector>
@@ -31,11 +36,11 @@ struct MphCtx {
     hipGraphExec_t graph1t = nullptr;   // one step without the output-only stores (single context)
     // step batching (mph_set_step_batching): single mph_step calls accumulate into 8-step graphs;
     // `pending` steps are accepted but not launched yet, `unchecked`: batches launched whose error
-    // flags have not been read; the flags of the last launched batch land in hs_pin (pinned)
+    // flags have not been read (ev_status: their copy has landed)
     bool batch_steps = false;
     int pending = 0;
     bool unchecked = false;
-    void* hs_pin = nullptr;
+    void* hs_pin = nullptr;      // pinned: where every status read lands (ctx_status_enqueue)
     hipEvent_t ev_status = nullptr;
     // phase timing (mph_phase_timing): steps launched directly (no graph) with events at every
     // step's phase boundaries -- before the sort, after the search, after the elastic substeps --
@@ -118,6 +123,114 @@ int ctx_state_status(MphCtx* c, const DevState& hs);   // kernel error flags -> 
 // the stream and destroy them; the next step captures again
 int drop_graphs(MphCtx* c);
 
+// The status read.  ctx_status_enqueue copies the kernels' error flags (the head of DevState) into
+// the pinned hs_pin behind the stream, allocating it on first use (a pageable copy is staged by the
+// runtime); ctx_status_landed maps the flags that have arrived to an MphStatus; ctx_status is both
+// with the wait for the stream between them.  Polling the stream instead of the blocking wait
+// measured the same per call (profiles/r05/sync_path/).
+int ctx_status_enqueue(MphCtx* c);
+int ctx_status_landed(MphCtx* c);
+int ctx_status(MphCtx* c);
+
+// The host's bookkeeping of nsteps steps: Time by the device's own repeated additions (the host
+// mirror keeps them bit for bit), and that a step has run; a_current: the sorted set A and pres are
+// now the current state's (mph_sample_grid; single contexts)
+inline void ctx_advance_time(MphCtx* c, int nsteps)
+{
+    for (int k = 0; k < nsteps; ++k) c->time += c->cfg.dt;
+}
+inline void ctx_stepped(MphCtx* c, int nsteps, bool a_current)
+{
+    ctx_advance_time(c, nsteps);
+    c->stepped = true;
+    if (a_current) c->a_current = true;
+}
+
+// `steps` steps captured from the context's stream into an uploaded graph (so the first launch costs
+// what later ones do): enqueue(k) puts step k on the stream and returns MPH_OK or the status that
+// ends the capture, whose graph is then destroyed.
+template <typename Enqueue>
+int ctx_capture(MphCtx* c, int steps, hipGraphExec_t* out, Enqueue enqueue)
+{
+    hipGraph_t g = nullptr;
+    MPH_HIP_OK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    int rc = MPH_OK;
+    for (int k = 0; k < steps && rc == MPH_OK; ++k) rc = enqueue(k);
+    const hipError_t e = hipStreamEndCapture(c->stream, &g);
+    if (rc != MPH_OK) {
+        if (g) (void)hipGraphDestroy(g);
+        return rc;
+    }
+    MPH_HIP_OK(c, e);
+    const hipError_t ei = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    MPH_HIP_OK(c, ei);
+    MPH_HIP_OK(c, hipGraphUpload(*out, c->stream));
+    return MPH_OK;
+}
+
+// n steps replayed from the captured graphs: graph8 while 8 or more are left, then single steps --
+// graph1t (no output-only stores) for all but the last where the context has it, graph1 for the
+// last, so the outputs are stored on the last step as in an 8-step batch; a slab context has
+// graph1 only
+int ctx_replay(MphCtx* c, int n);
+
+// Step batching: launch the steps accepted but not launched and read the error flags of everything
+// launched (mph_step.hip).  Every entry point that reads or changes the state, or waits for it,
+// calls this first.
+int ctx_flush(MphCtx* c);
+// the entry of an extern "C" function on a context: null check, flush, device
+inline int ctx_enter(MphCtx* c)
+{
+    if (!c) return MPH_ERR_ARG;
+    MPH_CK(ctx_flush(c));
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    return MPH_OK;
+}
+
+// Per-kernel HIP event timing (mph_profile_steps, mph_sample_grid_timed).  A launch's start event
+// behind a cross-stream wait reads as early as the wait packet itself (the time the stream went
+// idle), so each launch that follows a join also keeps a floor: an event on the other stream at the
+// joined point; its start is the later of the two.
+struct EventProfiler final : Profiler {
+    struct Rec { std::string name; hipEvent_t a, b; int floor; };
+    std::vector<Rec> recs;
+    std::vector<hipEvent_t> floors;
+    std::map<hipStream_t, int> pending;
+    bool events(const char* name, hipStream_t s, hipEvent_t* start, hipEvent_t* stop) override
+    {
+        Rec r{name, nullptr, nullptr, -1};
+        const auto it = pending.find(s);
+        if (it != pending.end()) {
+            r.floor = it->second;
+            pending.erase(it);
+        }
+        (void)hipEventCreate(&r.a);
+        (void)hipEventCreate(&r.b);
+        recs.push_back(r);
+        *start = r.a;
+        *stop = r.b;
+        return true;
+    }
+    void join(hipStream_t waiting, hipStream_t from) override
+    {
+        hipEvent_t e = nullptr;
+        (void)hipEventCreate(&e);
+        (void)hipEventRecord(e, from);
+        floors.push_back(e);
+        pending[waiting] = (int)floors.size() - 1;
+    }
+    ~EventProfiler() override
+    {
+        for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+        for (auto e : floors) (void)hipEventDestroy(e);
+    }
+};
+
+// one step of a single context on L's stream (mph_step.hip); last: the batch's last step; ev: the
+// phase events
+void enqueue_step(const Launch& L, bool last, hipEvent_t* ev = nullptr);
+
 void ctx_set_global_error(const std::string& msg);   // mph_last_error(NULL)
 // ids/n_glob: slab-local creation (the arrays hold n of n_glob particles, original indices ids)
 int ctx_create(MphCtx** out, const MphConfig* cfg, int n, const int* property, const double* pos,
@@ -151,7 +264,7 @@ int dist_sync(MphCtx* c, bool grow_ok = true);
 constexpr int kOutProf = 0, kOutVtk = 1, kOutVtu = 2, kOutVtkAsync = 3;
 int dist_write_output(MphCtx* c, const char* path, int kind);
 int dist_virial(MphCtx* c);
-int virial_full_lists(MphCtx* c);   // the step's lists again with every neighbour (mph_ctx.hip)
+int virial_full_lists(MphCtx* c);   // the step's lists again with every neighbour (mph_fields.hip)
 void dist_free(MphCtx* c);
 
 }  // namespace mph

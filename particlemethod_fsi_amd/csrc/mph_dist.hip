@@ -489,22 +489,9 @@ bool early_at(const MphCtx* c, int k, int steps, int out)
 
 int dist_capture(MphCtx* c, int steps, hipGraphExec_t* out)
 {
-    hipGraph_t g = nullptr;
-    MPH_HIP_OK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    int rc = MPH_OK;
-    for (int k = 0; k < steps && rc == MPH_OK; ++k) rc = dist_enqueue_step(c, nullptr, early_at(c, k, steps, 0),
-                                                                           early_at(c, k, steps, 1));
-    const hipError_t e = hipStreamEndCapture(c->stream, &g);
-    if (rc != MPH_OK) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-    }
-    MPH_HIP_OK(c, e);
-    const hipError_t ei = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    MPH_HIP_OK(c, ei);
-    MPH_HIP_OK(c, hipGraphUpload(*out, c->stream));   // the first launch then costs what later ones do
-    return MPH_OK;
+    return ctx_capture(c, steps, out, [&](int k) {
+        return dist_enqueue_step(c, nullptr, early_at(c, k, steps, 0), early_at(c, k, steps, 1));
+    });
 }
 
 int dist_step_batch(MphCtx* c, int nsteps, Profiler* prof);
@@ -523,7 +510,6 @@ int dist_step(MphCtx* c, int nsteps, Profiler* prof)
 int dist_step_batch(MphCtx* c, int nsteps, Profiler* prof)
 {
     MphDist& D = *c->dist;
-    int left = nsteps;
     // the 8-step graph at the first call whatever its count (every rank makes the same calls),
     // so a short warm-up does not leave its capture to the first long run.  A capture the runtime
     // refuses (an RCCL build without graph support) falls back to the same steps as direct
@@ -536,15 +522,13 @@ int dist_step_batch(MphCtx* c, int nsteps, Profiler* prof)
         c->err.clear();
     }
     if (D.graphs && !prof) {
-        while (left >= 8) { MPH_HIP_OK(c, hipGraphLaunch(c->graph8, c->stream)); left -= 8; }
-        while (left > 0) { MPH_HIP_OK(c, hipGraphLaunch(c->graph1, c->stream)); left -= 1; }
+        MPH_CK(ctx_replay(c, nsteps));
     } else {
         for (int k = 0; k < nsteps; ++k)
             MPH_CK(dist_enqueue_step(c, prof, early_at(c, k, nsteps, 0), early_at(c, k, nsteps, 1)));
     }
     MPH_HIP_OK(c, hipGetLastError());
-    for (int k = 0; k < nsteps; ++k) c->time += c->cfg.dt;
-    c->stepped = true;
+    ctx_stepped(c, nsteps, false);   // (a slab context has no reader of a_current: no lattice sampling)
     return dist_sync(c);
 }
 

@@ -1,7 +1,8 @@
 // mph_kernels.h -- launch interface of the hand-written HIP/CDNA4 (gfx950) kernels of the MPH explicit
 // hot path, the one host-visible interface of the kernel units (mph_sort.hip, mph_search.hip,
-// mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip, mph_sample.hip), used by mph_ctx.hip
-// and mph_dist.hip.
+// mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip, mph_sample.hip), used by the context's
+// host units (mph_ctx.h) and the slab layer's (mph_dist.h).  It also decides a step's form
+// (step_launch): plain host C++, so a host compiler can include this header and test it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -108,6 +109,18 @@ struct MonitorDev {
     const double* probes = nullptr;    // [nprobe][3]
 };
 
+// A step's form: which variant of its kernels a step launches.  Decided by
+// step_launch below and nowhere else; all false in the context's own Launch, in the slab steps and
+// in every launch outside a step.
+struct StepForm {
+    // a lazy wall step (mph_params.h kCoarseShift): k_prep marks the coarse map, the search skips the
+    // idle wall waves, pass A clears the map again; the passes run on the lazy step's XCD map
+    bool lazy = false;
+    // lean steps: a lazy step whose search accepts only the pairs it stores
+    // and counts no NeighborCount / whose pass A leaves out the DensityA and GravityCenter sums
+    bool lean_search = false, lean_pass_a = false;
+};
+
 // Everything one launch sequence needs.
 struct Launch {
     const DevParams* P = nullptr;
@@ -130,18 +143,14 @@ struct Launch {
     // fewest particles for the work-balanced XCD map of the passes (split in k_rank_scatter);
     // MPH_XCD_BAL_MIN overrides it at creation (tests force the map on small cases)
     int xcd_bal_min = 1 << 20;
-    // lazy wall steps (mph_params.h kCoarseShift): the coarse map of the non-wall particles (null:
-    // the context never takes a lazy step) and its size; lazy: this step is one (enqueue_step) --
-    // k_prep marks the map, the search skips the idle wall waves, pass A clears the map again
+    // lazy wall steps: the coarse map of the non-wall particles (null: the context never takes a
+    // lazy step) and its size
     unsigned char* cmap = nullptr;
     int cmap_bytes = 0;
-    bool lazy = false;
-    // Lean steps: a lazy step also drops the per-candidate and per-neighbour
-    // work whose results it does not store.  lean_ok: the context takes them (MPH_LEAN_STEPS, set at
-    // creation); lean_search: and its radii let the search (lean_search_ok); lean: this step is one
-    // (enqueue_step: lazy && lean_ok) -- the search takes its lean form when lean_search holds, pass A
-    // its own when neither GravityCenter nor DensityA is stored (launch_pass_a)
-    bool lean_ok = false, lean_search = false, lean = false;
+    // lean steps, the context's capabilities (set at creation, ctx_fill_launch): lean_ok, it takes
+    // them (MPH_LEAN_STEPS); lean_search, and its radii let the search (lean_search_ok)
+    bool lean_ok = false, lean_search = false;
+    StepForm form;   // this step's (step_launch)
     // pass A products (A order): pressure values, gravity centre (GC, PressureA), sums
     double *pres = nullptr, *gx = nullptr, *gy = nullptr, *gz = nullptr, *pa = nullptr;
     double *dens_a = nullptr, *vstrain = nullptr, *divp = nullptr;
@@ -151,6 +160,38 @@ struct Launch {
     const StructDev* S = nullptr;
     const MonitorDev* mon = nullptr;   // monitors on: sampled at the end of every step
 };
+
+// The Launch of a step that is not the last of its batch.  Force and Acceleration (main.cpp:2085-2096,
+// 2892-2956) are outputs only: no kernel reads them, and every step overwrites all of them, so only
+// a batch's last step stores them (pass B -6 % at D1M); mph_get after any mph_step sees the last
+// step's values as before.  The same holds in pass A for DensityA, VolStrainP, DivergenceP and,
+// without surface tension (pass B then reads neither), GravityCenter and PressureA.
+inline Launch trim_outputs(Launch L)
+{
+    L.dens_a = L.vstrain = L.divp = nullptr;
+    if (!L.P->surface) L.gx = L.gy = L.gz = L.pa = nullptr;
+    L.force = L.acc = nullptr;
+    return L;
+}
+
+// The Launch of one step of a single context, from the context's: the outputs trimmed unless the
+// step is the `last` of its batch, and the step's form.
+// Lazy wall steps take the output rule one kernel further up.  On a step that is not `last`, a wall
+// walks no list in pass B, so what the search and pass A compute for a wall particle whose
+// neighbours are all walls -- its list, PressureP, the pass-B record, fpart -- has no reader; the
+// batch's last step computes all of it again.  Off (every step full) without the map (slab mode,
+// MPH_LAZY_WALLS=0) and while the monitor kernels run, which read the walls' pressure on every step.
+// A lean step is a lazy step that also leaves out what it would compute only to drop it: the search
+// where the context's radii allow (Launch.lean_search), pass A where GravityCenter is not stored
+// (DensityA never is on a lazy step).
+inline Launch step_launch(const Launch& L, bool last)
+{
+    Launch S = last ? L : trim_outputs(L);
+    S.form.lazy = !last && L.cmap && !L.mon;
+    S.form.lean_search = S.form.lazy && L.lean_ok && L.lean_search;
+    S.form.lean_pass_a = S.form.lazy && L.lean_ok && !L.P->surface;
+    return S;
+}
 
 // Lattice sampling (mph_sample.hip, mph_sample_grid): the lattice, the wave tiling chosen for it
 // (sample_tiling) and the resolved radius and class mask, passed to the kernel by value.

@@ -627,17 +627,17 @@ void launch_pass_a(const Launch& L)
 {
     const DevParams& P = *L.P;
     if (P.n == 0) return;
-    // a lean step that stores neither GravityCenter / PressureA nor the diagnostics (enqueue_step:
-    // not the batch's last step, no surface tension) leaves their sums out
-    const bool lean = L.lean && L.lazy && !L.gx && !L.dens_a;
+    // a lean step stores neither GravityCenter / PressureA nor the diagnostics (step_launch) and
+    // leaves their sums out
+    const bool lazy = L.form.lazy;
     auto go = [&](auto LEAN) {
         by_dim(P.dim, [&](auto D) {
             launch(L.prof, "pass_a", L.stream, k_pass_a<decltype(D)::value, decltype(LEAN)::value>,
-                   dim3(list_grid(P.n, L.lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T, L.A, L.nbr, L.ncount,
-                   L.lhdr, L.lgap, pass_a_out(L), L.st, L.lazy ? L.cmap : nullptr, L.cmap_bytes);
+                   dim3(list_grid(P.n, lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T, L.A, L.nbr, L.ncount,
+                   L.lhdr, L.lgap, pass_a_out(L), L.st, lazy ? L.cmap : nullptr, L.cmap_bytes);
         });
     };
-    if (lean) go(std::true_type{});
+    if (L.form.lean_pass_a) go(std::true_type{});
     else go(std::false_type{});
 }
 
@@ -666,8 +666,8 @@ void launch_pass_b(const Launch& L, int phase)
 {
     const DevParams& P = *L.P;
     if (P.n == 0) return;
-    // pass B reads GravityCenter and PressureA of every neighbour with surface tension; enqueue_step
-    // may leave them unstored on the non-last steps of a batch only without it
+    // pass B reads GravityCenter and PressureA of every neighbour with surface tension; trim_outputs
+    // leaves them unstored on the non-last steps of a batch only without it
     if (P.surface && !(L.gx && L.gy && L.gz && L.pa)) {
         std::fprintf(stderr, "mph: launch_pass_b with surface tension needs GravityCenter/PressureA\n");
         std::abort();
@@ -676,7 +676,7 @@ void launch_pass_b(const Launch& L, int phase)
         by_dim(P.dim, [&](auto D) {
             launch(L.prof, phase == 2 ? "pass_b_face" : "pass_b", L.stream,
                    k_pass_b<decltype(SURF)::value, decltype(D)::value>,
-                   dim3(list_grid(P.n, L.lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T, L.A,
+                   dim3(list_grid(P.n, L.form.lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T, L.A,
                    L.rec, L.fpart, L.gx, L.gy, L.gz, L.pa, L.nbr, L.ncount, L.lhdr, L.lgap, L.force, L.acc, L.B, phase,
                    L.wface, struct_hook(L), L.st);
         });

@@ -684,10 +684,10 @@ void launch_neighbors(const Launch& L)
     const DevParams& P = *L.P;
     if (P.n == 0) return;
     const int bal = P.n >= L.xcd_bal_min;
-    const bool lazy = L.lazy && L.cmap;
-    // a lean step's search, when the radii allow it (lean_search_ok; asked again here for a caller
-    // that changed rlf after the context was filled, as virial_full_lists does)
-    const bool lean = lazy && L.lean && L.lean_search && lean_search_ok(P);
+    const bool lazy = L.form.lazy;
+    // a lean step's search (lean_search_ok is asked again here for a caller that changed rlf after
+    // the context was filled, as virial_full_lists does)
+    const bool lean = L.form.lean_search && lean_search_ok(P);
     by_dim(P.dim, [&](auto D) {
         constexpr int DIM = decltype(D)::value;
         auto go = [&](auto PERM) {

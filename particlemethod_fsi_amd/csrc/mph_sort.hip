@@ -28,9 +28,9 @@ constexpr int kScanThreads = 256;
 #endif
 constexpr int kScanItems = MPH_SCAN_ITEMS;   // cells per thread (a multiple of 4)
 constexpr int kScanBlock = kScanThreads * kScanItems;   // 4096 cells per block
-// ints of the scan's block totals (mph_ctx.hip allocates them)
+// ints of the scan's block totals (mph_create.hip allocates them)
 __host__ __device__ inline int bsum_stride(int ncell) { return ncell / kScanBlock + 2; }
-static_assert(kScanBlock == 4096, "mph_ctx.hip sizes the bsum buffer for 4096-cell blocks");
+static_assert(kScanBlock == 4096, "mph_create.hip sizes the bsum buffer for 4096-cell blocks");
 
 // The XCD split of the list passes (see list_block) from the search's work histogram: an inclusive
 // scan of the runs' work (kXcdSegs / blockDim.x consecutive runs per thread), the 7 inner cut
@@ -386,10 +386,10 @@ void launch_sort(const Launch& L, int mode)
     const int n = P.n;
     if (n == 0) return;
     // the passes' XCD split (list_grid, k_rank_scatter): 0 none, 1 a full step's, 2 a lazy step's
-    const int split = n >= L.xcd_bal_min ? (L.lazy ? 2 : 1) : 0;
+    const int split = n >= L.xcd_bal_min ? (L.form.lazy ? 2 : 1) : 0;
     const dim3 g(blocks(n, 256)), b(256);
     launch(L.prof, "prep", L.stream, k_prep, g, b, P, L.st, L.B, L.key, L.slot, L.cnt, mode, L.vsrc,
-           L.lazy ? L.cmap : nullptr);
+           L.form.lazy ? L.cmap : nullptr);
     launch_scan(L.cnt, P.ncell, L.bsum, L.start, n, P.n_dev, L.stream, L.prof);
     launch(L.prof, "place", L.stream, k_place, g, b, P, L.st, L.key, L.slot, L.start, L.tmp, mode);
     launch(L.prof, "rank_scatter", L.stream, k_rank_scatter, g, b, P, L.key, L.start, L.tmp, L.B, L.A,

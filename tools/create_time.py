@@ -27,8 +27,11 @@ def main():
             s = MphSolver(cfg, parts)
             s.synchronize()
             res[mode] = time.perf_counter() - t0
+            res.setdefault("first", res[mode])
             s.close()
-        out[name] = {"particles": parts.n, "mph_create_s_device_init": res["device"],
+        # first: this case's first create -- the process's first one (runtime start-up, the load of
+        # every device code object) for the first case named
+        out[name] = {"particles": parts.n, "mph_create_s_first": res["first"], "mph_create_s_device_init": res["device"],
                      "mph_create_s_host_init": res["host"]}
         print(name, out[name], flush=True)
     print(json.dumps(out))
