@@ -219,13 +219,15 @@ int mph_create(MphCtx** ctx, const MphConfig* cfg, int n, const int* property,
 /* Advance nsteps time steps (main.cpp:597-686 each).  Steps are replayed from captured
  * hipGraphs of 8 and 1 steps; returns MPH_ERR_NEIGHBOR_OVERFLOW if any particle reached 512
  * neighbours.  The output-only fields (Force, Acceleration, DensityA, VolStrainP, DivergenceP,
- * and GravityCenter/PressureA without surface tension) are stored by the last step of each
- * replayed batch, so after a successful mph_step they hold that step's values; after an error
+ * and GravityCenter/PressureA without surface tension) are stored by the call's last step (and by
+ * the last step of its last whole batch of 8), so after a successful mph_step they hold that
+ * step's values; after an error
  * they are undefined (the state itself -- Position, Velocity -- is the failing step's).
- * The overflow is reported after the batch that held it.  A lean step (mph_lean_step_stats) counts
+ * The overflow is reported when the call returns.  A lean step (mph_lean_step_stats) counts
  * only the pairs within the list radius (MaxRadius), so a count that passes 512 only through pairs
- * of the shell MaxRadius < r <= MaxRadius + MARGIN raises the error at the batch's last step, which
- * counts every pair: at most 7 steps later, and still in the mph_step call that took the step.  */
+ * of the shell MaxRadius < r <= MaxRadius + MARGIN raises the error at the next step that counts
+ * every pair -- the last step of the call's last whole batch, or the call's last step: later in the
+ * call by up to its length, and still in the mph_step call that took the step.                 */
 int mph_step(MphCtx* ctx, int nsteps);
 /* Step batching for the drop-in loop that calls mph_step(ctx, 1) once per iteration
  * (INTEGRATION.md section 2); single contexts only (slab mode: MPH_ERR_ARG for on != 0).
@@ -554,6 +556,14 @@ int mph_idle_wall_stats(MphCtx* ctx, long long out2[2]);
  * sums (not with surface tension, where pass B reads them).  Both stay 0 wherever no step is lazy.
  * A flush point.  Additive: no change of MPH_ABI_VERSION.                                        */
 int mph_lean_step_stats(MphCtx* ctx, long long out2[2]);
+/* The key fold, for verification: out2 = {steps whose pass B left the next step's
+ * cell keys, steps that opened with a k_prep launch} since the creation.  Inside one replayed graph
+ * (or one phase-timed or profiled batch) pass B moves and wraps the particles and computes the next
+ * step's keys, slots and cell histogram before it stores them, so only the graph's first step
+ * launches k_prep.  Single contexts without structure particles and without monitors, created
+ * without MPH_KEY_FOLD=0; elsewhere the first stays 0 and the second counts every step.  A flush
+ * point.  Additive: no change of MPH_ABI_VERSION.                                               */
+int mph_key_fold_stats(MphCtx* ctx, long long out2[2]);
 /* The neighbour lists of calculateNeighbor themselves (main.cpp:1764-1772: Neighbor[i][k] = j for
  * k < 512), for verification: the sets of the `count` particles [first, first + count) (original
  * order) from the last search, each row as ascending original indices (the reference's rows are in

@@ -34,6 +34,10 @@ struct MphCtx {
     hipStream_t stream = nullptr;
     hipGraphExec_t graph1 = nullptr, graph8 = nullptr;
     hipGraphExec_t graph1t = nullptr;   // one step without the output-only stores (single context)
+    // eight steps without them: every whole batch of a call but its last (replay_plan); captured
+    // only where lean_calls (a single context, MPH_LEAN_CALLS not 0 at creation: ctx_fill_launch)
+    hipGraphExec_t graph8t = nullptr;
+    bool lean_calls = false;
     // step batching (mph_set_step_batching): single mph_step calls accumulate into 8-step graphs;
     // `pending` steps are accepted but not launched yet, `unchecked`: batches launched whose error
     // flags have not been read (ev_status: their copy has landed)
@@ -169,10 +173,10 @@ int ctx_capture(MphCtx* c, int steps, hipGraphExec_t* out, Enqueue enqueue)
     return MPH_OK;
 }
 
-// n steps replayed from the captured graphs: graph8 while 8 or more are left, then single steps --
-// graph1t (no output-only stores) for all but the last where the context has it, graph1 for the
-// last, so the outputs are stored on the last step as in an 8-step batch; a slab context has
-// graph1 only
+// n steps replayed from the captured graphs in the order of replay_plan (mph_kernels.h): graph8t (no
+// output-only stores) for every whole batch but the last where the context has it, graph8 for the
+// last, then single steps -- graph1t for all but the last where the context has it, graph1 for the
+// last, so the outputs are stored on the call's last step; a slab context has graph8 and graph1 only
 int ctx_replay(MphCtx* c, int n);
 
 // Step batching: launch the steps accepted but not launched and read the error flags of everything
@@ -228,8 +232,9 @@ struct EventProfiler final : Profiler {
 };
 
 // one step of a single context on L's stream (mph_step.hip); last: the batch's last step; ev: the
-// phase events
-void enqueue_step(const Launch& L, bool last, hipEvent_t* ev = nullptr);
+// phase events; k of `steps` enqueued together, next_last: step k + 1 is a last one (the key fold)
+void enqueue_step(const Launch& L, bool last, hipEvent_t* ev = nullptr, int k = 0, int steps = 1,
+                  bool next_last = true);
 
 void ctx_set_global_error(const std::string& msg);   // mph_last_error(NULL)
 // ids/n_glob: slab-local creation (the arrays hold n of n_glob particles, original indices ids)

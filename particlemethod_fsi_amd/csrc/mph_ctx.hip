@@ -84,7 +84,7 @@ int ctx_status(MphCtx* c)
 int drop_graphs(MphCtx* c)
 {
     MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
-    for (hipGraphExec_t* g : {&c->graph1, &c->graph1t, &c->graph8})
+    for (hipGraphExec_t* g : {&c->graph1, &c->graph1t, &c->graph8, &c->graph8t})
         if (*g) {
             MPH_HIP_OK(c, hipGraphExecDestroy(*g));
             *g = nullptr;
@@ -94,9 +94,11 @@ int drop_graphs(MphCtx* c)
 
 int ctx_replay(MphCtx* c, int n)
 {
-    for (; n >= 8; n -= 8) MPH_HIP_OK(c, hipGraphLaunch(c->graph8, c->stream));
-    for (; n > 1; --n) MPH_HIP_OK(c, hipGraphLaunch(c->graph1t ? c->graph1t : c->graph1, c->stream));
-    if (n == 1) MPH_HIP_OK(c, hipGraphLaunch(c->graph1, c->stream));
+    const ReplayPlan p = replay_plan(n, c->graph8t != nullptr, c->graph1t != nullptr);
+    for (int k = 0; k < p.batch8t; ++k) MPH_HIP_OK(c, hipGraphLaunch(c->graph8t, c->stream));
+    for (int k = 0; k < p.batch8; ++k) MPH_HIP_OK(c, hipGraphLaunch(c->graph8, c->stream));
+    for (int k = 0; k < p.single1t; ++k) MPH_HIP_OK(c, hipGraphLaunch(c->graph1t, c->stream));
+    for (int k = 0; k < p.single1; ++k) MPH_HIP_OK(c, hipGraphLaunch(c->graph1, c->stream));
     return MPH_OK;
 }
 
@@ -115,6 +117,12 @@ void ctx_fill_launch(MphCtx* c)
     // not with MPH_LIST_FULL=1)
     L.lean_ok = env_int("MPH_LEAN_STEPS", 1) != 0;
     L.lean_search = L.lean_ok && lean_search_ok(c->P);
+    // MPH_LEAN_CALLS=0: every whole batch of a call ends in a step that stores the output-only fields
+    // (no graph8t, replay_plan), not only the call's last; slab contexts never take the lean batches
+    c->lean_calls = !c->dist && env_int("MPH_LEAN_CALLS", 1) != 0;
+    // MPH_KEY_FOLD=0: every step opens with k_prep, no pass B leaves the next step's cell keys
+    // (step_keys); slab contexts never fold
+    L.key_fold = !c->dist && env_int("MPH_KEY_FOLD", 1) != 0;
     L.P = &c->P;
     L.stream = c->stream;
     // work-balanced XCD map of the passes from this many particles (MPH_XCD_BAL_MIN: tests force it
@@ -159,6 +167,7 @@ void mph_destroy(MphCtx* c)
     if (c->graph1) (void)hipGraphExecDestroy(c->graph1);
     if (c->graph1t) (void)hipGraphExecDestroy(c->graph1t);
     if (c->graph8) (void)hipGraphExecDestroy(c->graph8);
+    if (c->graph8t) (void)hipGraphExecDestroy(c->graph8t);
     for (auto* v : {&c->ev8, &c->ev_vir})
         for (hipEvent_t e : *v) (void)hipEventDestroy(e);
     if (c->dist) dist_free(c);

@@ -195,6 +195,22 @@ __device__ __forceinline__ int wave_reduce_dpp(int v)
 __device__ __forceinline__ int wave_min(int v) { return wave_reduce_dpp<false>(v); }
 __device__ __forceinline__ int wave_max(int v) { return wave_reduce_dpp<true>(v); }
 
+// Particles of this lane within the face box margin of a periodic face: bit 2k low face, 2k + 1
+// high face of axis k (k_prep, or the previous step's pass B, gathers them per step into DevState.seam_occ).
+__device__ __forceinline__ int seam_bits(const DevParams& P, double x, double y, double z)
+{
+    const double v[3] = {x, y, z};
+    int b = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (k == 2 && P.dim == 2) break;
+        if ((P.seam_always >> k) & 1) continue;   // (the slab axis: the face box always applies)
+        b |= (v[k] < P.inner_lo[k] ? 1 : 0) << (2 * k);
+        b |= (v[k] > P.inner_hi[k] ? 2 : 0) << (2 * k);
+    }
+    return b;
+}
+
 // calculateWall (3031-3060) then calculatePeriodicBoundary (3322-3333) for particle p of B.
 __device__ __forceinline__ void move_and_wrap(const DevParams& P, const DevState* st, Soa& B, int p,
                                               double& x, double& y, double& z)

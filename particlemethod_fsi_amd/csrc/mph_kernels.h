@@ -119,6 +119,10 @@ struct StepForm {
     // lean steps: a lazy step whose search accepts only the pairs it stores
     // and counts no NeighborCount / whose pass A leaves out the DensityA and GravityCenter sums
     bool lean_search = false, lean_pass_a = false;
+    // the key fold (step_keys below): keys_done, the previous step's pass B has moved and wrapped the
+    // particles and left this step's cell keys, slots and histogram, so the sort launches no k_prep;
+    // keys_next, this step's pass B does that for the next step
+    bool keys_done = false, keys_next = false;
 };
 
 // Everything one launch sequence needs.
@@ -150,7 +154,11 @@ struct Launch {
     // lean steps, the context's capabilities (set at creation, ctx_fill_launch): lean_ok, it takes
     // them (MPH_LEAN_STEPS); lean_search, and its radii let the search (lean_search_ok)
     bool lean_ok = false, lean_search = false;
-    StepForm form;   // this step's (step_launch)
+    // the key fold, the context's choice (MPH_KEY_FOLD, ctx_fill_launch); step_keys has the rest
+    bool key_fold = false;
+    // keys_next: the coarse map the next step's search reads -- set where that step is lazy, else null
+    unsigned char* cmap_next = nullptr;
+    StepForm form;   // this step's (step_launch, step_keys)
     // pass A products (A order): pressure values, gravity centre (GC, PressureA), sums
     double *pres = nullptr, *gx = nullptr, *gy = nullptr, *gz = nullptr, *pa = nullptr;
     double *dens_a = nullptr, *vstrain = nullptr, *divp = nullptr;
@@ -191,6 +199,50 @@ inline Launch step_launch(const Launch& L, bool last)
     S.form.lean_search = S.form.lazy && L.lean_ok && L.lean_search;
     S.form.lean_pass_a = S.form.lazy && L.lean_ok && !L.P->surface;
     return S;
+}
+
+// The key fold.  A step opens with k_prep: wall motion, periodic wrap, cell
+// key, histogram -- all of it from what the previous step's pass B had in registers when it stored
+// them.  Where nothing can come between the two, pass B does k_prep's work before its stores
+// (k_pass_b<.., KEYS>) and the next step's sort starts at the scan.  Nothing comes between them
+// inside one enqueued sequence of steps (a captured graph, a phase-timed or profiled batch): k is the
+// step's index there, `steps` their number, next_last whether step k + 1 stores the output-only
+// fields.  Never across the sequence's end (the state a caller reads is the unmoved one), never with
+// structure particles (the elastic substeps write the set after pass B), monitors (they read the
+// unmoved set) or a slab context (vsrc).  S: the step's Launch from step_launch; L: the context's.
+inline bool key_fold_ok(const Launch& L)
+{
+    return L.key_fold && L.P->n_struct == 0 && !L.mon && !L.vsrc.idx;
+}
+inline Launch step_keys(Launch S, const Launch& L, int k, int steps, bool next_last)
+{
+    const bool ok = key_fold_ok(L);
+    S.form.keys_done = ok && k > 0;
+    S.form.keys_next = ok && k + 1 < steps;
+    S.cmap_next = S.form.keys_next && step_launch(L, next_last).form.lazy ? L.cmap : nullptr;
+    return S;
+}
+
+// How n steps of one call are cut into batches, launched in this order:
+// batch8t whole batches of eight steps none of which stores the output-only fields, batch8 of eight
+// whose last step stores them, single1t single steps that store none, single1 that do.  A call can
+// only be observed after it returns, so only its last step needs them: with `lean8` (the context has
+// the all-lean 8-step graph) every whole batch but the last is a batch8t, and with `lean1` every
+// step of the remainder but the last is a single1t.  Without either, every batch and every single
+// step ends in a storing step of its own (a slab context's sequence).  Plain host C++, no HIP call.
+struct ReplayPlan {
+    int batch8t = 0, batch8 = 0, single1t = 0, single1 = 0;
+};
+inline ReplayPlan replay_plan(int n, bool lean8, bool lean1)
+{
+    ReplayPlan p;
+    if (n <= 0) return p;
+    const int whole = n / 8, rest = n % 8;
+    p.batch8t = lean8 && whole >= 2 ? whole - 1 : 0;
+    p.batch8 = whole - p.batch8t;
+    p.single1t = lean1 && rest > 1 ? rest - 1 : 0;
+    p.single1 = rest - p.single1t;
+    return p;
 }
 
 // Lattice sampling (mph_sample.hip, mph_sample_grid): the lattice, the wave tiling chosen for it

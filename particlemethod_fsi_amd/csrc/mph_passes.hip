@@ -410,11 +410,27 @@ __device__ __forceinline__ void pass_b_loop(const DevParams& P, const double* s_
     }
 }
 
+// What pass B's KEYS form writes for the next step's sort: key and slot per particle, the cell
+// histogram, the coarse map where that step is lazy (else null).
+struct KeyOut {
+    int *key, *slot, *cnt;
+    unsigned char* cmap;
+};
+
 // Pair forces of PressureP (2394-2424), PressureA (2225-2258), DiffuseInterface (2261-2312),
 // ViscosityV (2478-2522) for non-structure i; InterfaceForce (2439-2472) for structure i; then
 // Gravity (2917-2936), Acceleration/kick (2938-2956) and Convection/drift (1892-1907).  The sums
 // start from pass A's fpart (P_i half of the pressure force + viscous force).
-template <bool SURF, int DIM>
+// KEYS (the key fold, mph_kernels.h step_keys; single contexts without structure particles): the
+// kernel ends with the next step's k_prep on the values it is about to store -- the same
+// move_and_wrap, cell_axis and cell_index, so the same bits -- and leaves key, slot, the cell
+// histogram, the non-finite flag, the face bits and (cmap set: the next step is lazy) the coarse
+// map.  This step's k_place has advanced Time, WallCenter and seam_step, its k_scan_down has
+// re-zeroed cnt and its pass A has cleared the map, so the tail sees what that k_prep would.  The
+// run detection needs every lane of the wave, so the lanes past n stay to the end -- they read
+// particle n - 1's entries (ir) and store nothing -- and no barrier follows the list loop: the face
+// bits are reduced per wave.
+template <bool SURF, int DIM, bool KEYS = false>
 #ifndef MPH_PB_WPE
 #define MPH_PB_WPE 0   // pass B occupancy hint (0: the compiler's choice, 112 VGPRs / 4 waves at U = 8)
 #endif
@@ -436,11 +452,12 @@ __global__ __launch_bounds__(MPH_LB) MPH_PB_ATTR void k_pass_b(DevParams P, cons
                                                 const unsigned long long* __restrict__ lgap,
                                                 double4* __restrict__ force, double4* __restrict__ acc,
                                                 Soa B, int phase, int* __restrict__ wface, StructHook H,
-                                                const DevState* __restrict__ st)
+                                                const DevState* __restrict__ st, KeyOut K)
 {
     const int n = dev_n(P);
     const int lb = list_block(st, n);
     if (lb < 0) return;
+    if (KEYS && lb == 0 && threadIdx.x == 0) const_cast<DevState*>(st)->key_fold_steps += 1;
     __shared__ double s_ratio[kTypes * kTypes];
     if (SURF) {
         if (threadIdx.x < kTypes * kTypes) s_ratio[threadIdx.x] = T->ratio[threadIdx.x];
@@ -467,7 +484,9 @@ __global__ __launch_bounds__(MPH_LB) MPH_PB_ATTR void k_pass_b(DevParams P, cons
         live = false;
     }
     const bool fast = wave_search_interior(P, st, live, xi, yi, zi);
-    if (!live) return;
+    if (!KEYS && !live) return;
+    if (KEYS && !__any(live)) return;
+    const int ir = KEYS ? ii : i;   // the entry this lane reads
     const int ti = A.type[ii];
     const bool solid = dev_is_struct(ti);
     const double4 fp = fpart[ii];
@@ -479,11 +498,11 @@ __global__ __launch_bounds__(MPH_LB) MPH_PB_ATTR void k_pass_b(DevParams P, cons
     }
     // a wall's pair forces only go to the Force output (walls are not kicked or drifted, K17/K18):
     // on the steps that do not store it (force null, enqueue_step) its list loop is skipped
-    const int end = !force && dev_is_wall(ti) ? 0 : (ncount[i] < kTileRows ? ncount[i] : kTileRows);
-    const unsigned long long hdr = wave_hdr(lhdr, i);
+    const int end = !force && dev_is_wall(ti) ? 0 : (ncount[ir] < kTileRows ? ncount[ir] : kTileRows);
+    const unsigned long long hdr = wave_hdr(lhdr, ir);
     const bool plain = (hdr >> 56) == 0;   // no jumps: rows [0, end) (see k_pass_a)
-    const RowMask M = row_mask(hdr, lgap, i, end);
-    const NbrList NL = nbr_list(nbr, i);
+    const RowMask M = row_mask(hdr, lgap, ir, end);
+    const NbrList NL = nbr_list(nbr, ir);
     if (fast)
         pass_b_loop<true, SURF, DIM>(P, s_ratio, rec, gx, gy, gz, pa, NL, plain, M, end, ti, solid, xi, yi, zi, gxi,
                                      gyi, gzi, pai, ai, f0, f1, f2);
@@ -491,7 +510,7 @@ __global__ __launch_bounds__(MPH_LB) MPH_PB_ATTR void k_pass_b(DevParams P, cons
         pass_b_loop<false, SURF, DIM>(P, s_ratio, rec, gx, gy, gz, pa, NL, plain, M, end, ti, solid, xi, yi, zi, gxi,
                                       gyi, gzi, pai, ai, f0, f1, f2);
     double vxi, vyi, vzi;
-    own_velocity(A, i, vxi, vyi, vzi);
+    own_velocity(A, ir, vxi, vyi, vzi);
     double vo0 = vxi, vo1 = vyi, vo2 = vzi;
     double xo0 = xi, xo1 = yi, xo2 = zi;
     double4 ao = make_double4(0.0, 0.0, 0.0, 0.0);
@@ -509,6 +528,53 @@ __global__ __launch_bounds__(MPH_LB) MPH_PB_ATTR void k_pass_b(DevParams P, cons
             xo1 += vo1 * P.dt;
             xo2 += vo2 * P.dt;
         }
+    }
+    if (KEYS) {
+        // (force is null and no particle is a structure's: launch_pass_b)
+        const int lane = threadIdx.x & 63;
+        int k = -1 - lane;   // the lanes past n: runs of their own, as in k_prep
+        int occ = 0;
+        if (live) {
+            B.vx[i] = vo0;
+            B.vy[i] = vo1;
+            B.vz[i] = vo2;
+            B.type[i] = ti;
+            B.id[i] = A.id[i];
+            double x = xo0, y = xo1, z = xo2;
+            move_and_wrap(P, st, B, i, x, y, z);   // (reads the type just stored; stores the position)
+            if (!isfinite(x + y + z)) atomicOr(const_cast<int*>(&st->overflow), 4);   // MPH_ERR_NONFINITE
+            const int cx = cell_axis(x, P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
+            const int cy = cell_axis(y, P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
+            const int cz = P.dim == 3 ? cell_axis(z, P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
+            k = cell_index(P, cx, cy, cz);
+            K.key[i] = k;
+            if (K.cmap && !dev_is_wall(ti))
+                K.cmap[coarse_index(P, cx >> kCoarseShift, cy >> kCoarseShift, cz >> kCoarseShift)] = 1;
+            occ = seam_bits(P, x, y, z);
+        }
+        // one histogram atomic per run of equal keys (k_prep has the derivation)
+        const int kprev = __shfl_up(k, 1, 64);
+        const bool head = lane == 0 || kprev != k;
+        const unsigned long long heads = __ballot(head);
+        const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+        const int hl = 63 - __clzll(heads & upto);
+        const unsigned long long above = heads & ~upto;
+        const int next = above ? __ffsll((long long)above) - 1 : 64;
+        int base = 0;
+        if (live && head) base = atomicAdd(&K.cnt[k], next - lane);
+        base = __shfl(base, hl, 64);
+        if (live) K.slot[i] = base + (lane - hl);
+        // the wave's face bits: one device atomic, only for bits the next step's word does not hold
+        if (__ballot(occ != 0)) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) occ |= __shfl_xor(occ, o, 64);
+            if (lane == 0) {
+                int* w = const_cast<int*>(&st->seam_occ[st->seam_step & 1]);
+                const int cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (occ & ~cur) atomicOr(w, occ);
+            }
+        }
+        return;
     }
     if (force) {   // null on all but the last step of a replayed batch (enqueue_step)
         force[i] = make_double4(f0, f1, f2, 0.0);
@@ -672,17 +738,24 @@ void launch_pass_b(const Launch& L, int phase)
         std::fprintf(stderr, "mph: launch_pass_b with surface tension needs GravityCenter/PressureA\n");
         std::abort();
     }
-    auto go = [&](auto SURF) {
+    // the key fold (step_keys): never on a step that stores Force, with structure particles, in a
+    // slab's phases or on a slab's set
+    const bool keys = L.form.keys_next;
+    if (keys && (L.force || P.n_struct > 0 || phase || P.slab_axis >= 0 || P.n_dev)) {
+        std::fprintf(stderr, "mph: launch_pass_b: the key fold on a step that cannot take it\n");
+        std::abort();
+    }
+    auto go = [&](auto SURF, auto KEYS) {
         by_dim(P.dim, [&](auto D) {
             launch(L.prof, phase == 2 ? "pass_b_face" : "pass_b", L.stream,
-                   k_pass_b<decltype(SURF)::value, decltype(D)::value>,
+                   k_pass_b<decltype(SURF)::value, decltype(D)::value, decltype(KEYS)::value>,
                    dim3(list_grid(P.n, L.form.lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T, L.A,
                    L.rec, L.fpart, L.gx, L.gy, L.gz, L.pa, L.nbr, L.ncount, L.lhdr, L.lgap, L.force, L.acc, L.B, phase,
-                   L.wface, struct_hook(L), L.st);
+                   L.wface, struct_hook(L), L.st, keys ? KeyOut{L.key, L.slot, L.cnt, L.cmap_next} : KeyOut{});
         });
     };
-    if (P.surface) go(std::true_type{});
-    else go(std::false_type{});
+    if (P.surface) keys ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+    else keys ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
 }
 
 void launch_virial(const Launch& L, const Soa& X, double* vir, double* vpres)

@@ -1,6 +1,7 @@
 // mph_profile.hip -- measurement and diagnostics of a context: the per-kernel profilers
 // (mph_profile_steps, mph_profile_graphs) and the list and counter readers (mph_neighbor_stats,
-// mph_list_stats, mph_list_layout, mph_idle_wall_stats, mph_lean_step_stats, mph_neighbor_rows).
+// mph_list_stats, mph_list_layout, mph_idle_wall_stats, mph_lean_step_stats, mph_key_fold_stats,
+// mph_neighbor_rows).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,7 +28,7 @@ int mph_profile_steps(MphCtx* c, int nsteps, double* avg_ms, int* launches, char
     } else {
         Launch L = c->L;
         L.prof = &prof;
-        for (int k = 0; k < nsteps; ++k) enqueue_step(L, k == nsteps - 1);
+        for (int k = 0; k < nsteps; ++k) enqueue_step(L, k == nsteps - 1, nullptr, k, nsteps, k + 1 == nsteps - 1);
         MPH_HIP_OK(c, hipGetLastError());
         MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
         ctx_stepped(c, nsteps, true);
@@ -234,6 +235,21 @@ int mph_lean_step_stats(MphCtx* c, long long out[2])
     static_assert(offsetof(DevState, lean_pass_a_steps) == offsetof(DevState, lean_search_steps) + sizeof(steps[0]),
                   "the two counters are read in one copy");
     MPH_HIP_OK(c, hipMemcpy(steps, reinterpret_cast<const char*>(c->L.st) + offsetof(DevState, lean_search_steps),
+                            sizeof(steps), hipMemcpyDeviceToHost));
+    out[0] = (long long)steps[0];
+    out[1] = (long long)steps[1];
+    return MPH_OK;
+}
+
+int mph_key_fold_stats(MphCtx* c, long long out[2])
+{
+    if (!out) return MPH_ERR_ARG;
+    MPH_CK(ctx_enter(c));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    unsigned long long steps[2] = {0, 0};   // key_fold_steps, prep_steps
+    static_assert(offsetof(DevState, prep_steps) == offsetof(DevState, key_fold_steps) + sizeof(steps[0]),
+                  "the two counters are read in one copy");
+    MPH_HIP_OK(c, hipMemcpy(steps, reinterpret_cast<const char*>(c->L.st) + offsetof(DevState, key_fold_steps),
                             sizeof(steps), hipMemcpyDeviceToHost));
     out[0] = (long long)steps[0];
     out[1] = (long long)steps[1];

@@ -6,22 +6,6 @@ namespace mph {
 
 // ------------------------------------------------------------------------- sort phase -------
 
-// Particles of this lane within the face box margin of a periodic face: bit 2k low face, 2k + 1
-// high face of axis k (k_prep gathers them per step into DevState.seam_occ).
-__device__ __forceinline__ int seam_bits(const DevParams& P, double x, double y, double z)
-{
-    const double v[3] = {x, y, z};
-    int b = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (k == 2 && P.dim == 2) break;
-        if ((P.seam_always >> k) & 1) continue;   // (the slab axis: the face box always applies)
-        b |= (v[k] < P.inner_lo[k] ? 1 : 0) << (2 * k);
-        b |= (v[k] > P.inner_hi[k] ? 2 : 0) << (2 * k);
-    }
-    return b;
-}
-
 constexpr int kScanThreads = 256;
 #ifndef MPH_SCAN_ITEMS
 #define MPH_SCAN_ITEMS 16
@@ -286,11 +270,12 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_down(int* __restrict__ cn
 }
 
 // Unordered placement; block 0 also advances Time and WallCenter (main.cpp:685, 3066-3070)
-// after k_prep consumed them.
+// after k_prep consumed them.  prep: a step (mode 1) that opened with k_prep, counted for
+// mph_key_fold_stats -- 0 where the previous step's pass B left the keys (StepForm.keys_done).
 __global__ __launch_bounds__(256) void k_place(DevParams P, DevState* __restrict__ st,
                                                const int* __restrict__ key, const int* __restrict__ slot,
                                                const int* __restrict__ start, int* __restrict__ tmp,
-                                               int mode)
+                                               int mode, int prep)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -304,6 +289,7 @@ __global__ __launch_bounds__(256) void k_place(DevParams P, DevState* __restrict
                 for (int d = 0; d < 3; ++d) st->wall_c[t][d] += st->wall_vel[t][d] * P.dt;
             st->time += P.dt;
         }
+        if (prep) st->prep_steps += 1;
     }
     const int n = dev_n(P);
     if (p >= n) return;
@@ -388,10 +374,14 @@ void launch_sort(const Launch& L, int mode)
     // the passes' XCD split (list_grid, k_rank_scatter): 0 none, 1 a full step's, 2 a lazy step's
     const int split = n >= L.xcd_bal_min ? (L.form.lazy ? 2 : 1) : 0;
     const dim3 g(blocks(n, 256)), b(256);
-    launch(L.prof, "prep", L.stream, k_prep, g, b, P, L.st, L.B, L.key, L.slot, L.cnt, mode, L.vsrc,
-           L.form.lazy ? L.cmap : nullptr);
+    // keys_done (step_keys): the previous step's pass B has done k_prep's work
+    const bool prep = !(mode == 1 && L.form.keys_done);
+    if (prep)
+        launch(L.prof, "prep", L.stream, k_prep, g, b, P, L.st, L.B, L.key, L.slot, L.cnt, mode, L.vsrc,
+               L.form.lazy ? L.cmap : nullptr);
     launch_scan(L.cnt, P.ncell, L.bsum, L.start, n, P.n_dev, L.stream, L.prof);
-    launch(L.prof, "place", L.stream, k_place, g, b, P, L.st, L.key, L.slot, L.start, L.tmp, mode);
+    launch(L.prof, "place", L.stream, k_place, g, b, P, L.st, L.key, L.slot, L.start, L.tmp, mode,
+           (int)(prep && mode == 1));
     launch(L.prof, "rank_scatter", L.stream, k_rank_scatter, g, b, P, L.key, L.start, L.tmp, L.B, L.A,
            nullptr /* rank_of: no reader (fields return through A.id, slab mode uses dst_of) */, L.dst_of, mode,
            L.vsrc, L.st, split);

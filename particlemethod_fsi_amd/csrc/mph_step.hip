@@ -18,10 +18,12 @@ namespace mph {
 // ev (phase timing, else null): three events recorded on the stream at the step's phase
 // boundaries -- before the sort, after the search (neighbour search = sort + search, as the
 // reference's calculateNeighbor holds its own cell sort), after the elastic substeps.
-void enqueue_step(const Launch& L, bool last, hipEvent_t* ev)
+// k, steps, next_last: the step's place in the sequence it is enqueued with (a graph, a phase-timed or
+// profiled batch) and whether the step after it is a last one, for the key fold (step_keys).
+void enqueue_step(const Launch& L, bool last, hipEvent_t* ev, int k, int steps, bool next_last)
 {
     if (ev) (void)hipEventRecord(ev[0], L.stream);
-    const Launch S = step_launch(L, last);
+    const Launch S = step_keys(step_launch(L, last), L, k, steps, next_last);
     launch_sort(S, 1);
     if (ev) {   // phase timing: the boundary between the search and pass A
         launch_neighbors(S);
@@ -37,11 +39,11 @@ void enqueue_step(const Launch& L, bool last, hipEvent_t* ev)
 }
 
 // store_last = false: no step of the graph stores the output-only fields (graph1t, the steps of a
-// remainder before its last one)
+// remainder before its last one; graph8t, the whole batches of a call before its last one)
 static int capture(MphCtx* c, int steps, hipGraphExec_t* out, bool store_last = true)
 {
     return ctx_capture(c, steps, out, [&](int k) {
-        enqueue_step(c->L, store_last && k == steps - 1);
+        enqueue_step(c->L, store_last && k == steps - 1, nullptr, k, steps, store_last && k + 1 == steps - 1);
         return MPH_OK;
     });
 }
@@ -54,6 +56,7 @@ static int capture_graphs(MphCtx* c)
     if (!c->graph1) MPH_CK(capture(c, 1, &c->graph1));
     if (!c->graph1t) MPH_CK(capture(c, 1, &c->graph1t, false));
     if (!c->graph8) MPH_CK(capture(c, 8, &c->graph8));
+    if (c->lean_calls && !c->graph8t) MPH_CK(capture(c, 8, &c->graph8t, false));
     return MPH_OK;
 }
 
@@ -137,16 +140,19 @@ int mph_step(MphCtx* c, int nsteps)
     if (c->batch_steps && !c->phase_timing) return step_batched(c, nsteps);
     MPH_CK(ctx_flush(c));
     if (c->phase_timing) {
-        // the graphs' batches (8 steps, then single steps; the output-only stores on each batch's
-        // last step) as direct launches with the phase events (HIP cannot time events recorded
-        // inside a captured graph), read after every batch
-        for (int left = nsteps; left > 0;) {
-            const int b = left >= 8 ? 8 : 1;
-            for (int k = 0; k < b; ++k) enqueue_step(c->L, k == b - 1, c->ev8.data() + 3 * k);
-            MPH_HIP_OK(c, hipGetLastError());
-            MPH_CK(accumulate_phases(c, c->ev8, b));
-            left -= b;
-        }
+        // the graphs' batches (replay_plan: the same steps store the output-only fields) as direct
+        // launches with the phase events (HIP cannot time events recorded inside a captured graph),
+        // read after every batch
+        const ReplayPlan p = replay_plan(nsteps, c->lean_calls, true);
+        const int batches[4][3] = {{p.batch8t, 8, 0}, {p.batch8, 8, 1}, {p.single1t, 1, 0}, {p.single1, 1, 1}};
+        for (const auto& [count, b, store_last] : batches)
+            for (int r = 0; r < count; ++r) {
+                for (int k = 0; k < b; ++k)
+                    enqueue_step(c->L, store_last && k == b - 1, c->ev8.data() + 3 * k, k, b,
+                                 store_last && k + 1 == b - 1);
+                MPH_HIP_OK(c, hipGetLastError());
+                MPH_CK(accumulate_phases(c, c->ev8, b));
+            }
     } else {
         MPH_CK(capture_graphs(c));
         MPH_CK(ctx_replay(c, nsteps));

@@ -60,7 +60,7 @@ EXPORTED_SYMBOLS = [
     "mph_set_step_batching", "mph_neighbor_rows", "mph_dist_overlap", "mph_list_layout",
     "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
     "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
-    "mph_lean_step_stats",
+    "mph_lean_step_stats", "mph_key_fold_stats",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -223,13 +223,14 @@ def load_library() -> ctypes.CDLL:
         "mph_write_vti_arrays": (ip, [ctypes.c_char_p, ctypes.POINTER(MphSampleGrid), vp]),
         "mph_idle_wall_stats": (ip, [vp, vp]),
         "mph_lean_step_stats": (ip, [vp, vp]),
+        "mph_key_fold_stats": (ip, [vp, vp]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
                 "mph_dist_overlap", "mph_profile_graphs", "mph_list_stats", "mph_list_layout",
                 "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
                 "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
-                "mph_lean_step_stats"}
+                "mph_lean_step_stats", "mph_key_fold_stats"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -663,6 +664,16 @@ class MphSolver:
         if hasattr(self._L, "mph_lean_step_stats"):
             _check(self._L.mph_lean_step_stats(self._h, a.ctypes.data), self._h)
         return {"search_steps": int(a[0]), "pass_a_steps": int(a[1])}
+
+    def key_fold_stats(self) -> dict:
+        """The key fold since the creation (mph_key_fold_stats): the steps whose pass B left the next
+        step's cell keys ("folded_steps") and the steps that opened with a k_prep launch
+        ("prep_launches"); the first 0 with structure particles, monitors, in slab mode or with
+        MPH_KEY_FOLD=0 at creation, both 0 from a library built before the entry point."""
+        a = np.zeros(2, dtype=np.int64)
+        if hasattr(self._L, "mph_key_fold_stats"):
+            _check(self._L.mph_key_fold_stats(self._h, a.ctypes.data), self._h)
+        return {"folded_steps": int(a[0]), "prep_launches": int(a[1])}
 
     def neighbor_rows(self, first: int = 0, count: int | None = None):
         """(counts, offsets, ids): the neighbour sets of the particles [first, first + count) from

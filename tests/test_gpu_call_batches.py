@@ -1,0 +1,226 @@
+"""Lean batches up to a call's last (csrc/mph_kernels.h replay_plan): a call can
+only be observed after it returns, so of the whole 8-step batches of one mph_step(n) only the last
+ends in a step that stores the output-only fields; the batches before it come from an 8-step graph
+whose steps are all lazy (graph8t).  And the key fold (step_keys): inside a
+graph, pass B moves and wraps the particles and leaves the next step's cell keys, slots and
+histogram, so only the graph's first step launches k_prep.  Nothing a caller can read may change:
+every comparison here is bitwise, mph_step(n) in one call against n x mph_step(1), over
+parity.CHUNK_FIELDS and both virial fields.
+
+n = 16 is graph8t + graph8 (15 lazy steps), n = 29 is 2 x graph8t + graph8 + 4 x graph1t + graph1
+(23 + 4), n = 40 is 4 x graph8t + graph8 (39).  The cases: the 12,000-particle tank of
+test_gpu_idle_walls.py (a partial last wave, idle walls, a moving fluid block), also under the
+work-balanced XCD map; box3d_jit (off the lattice: the shell pairs the lean search leaves out);
+seam3d (periodic faces); movwall3d (rigid wall motion across Time 0.2); rolling3d; turek2d (the
+inlet profile; its elastic plate keeps the fold off) and turek2d_fluid, the same channel with fluid
+in the plate's place, which takes the inlet profile through the fold; dam2d; box3d_st (surface
+tension: pass A never lean); gate3d (structures: fold off, plan on).
+"""
+import numpy as np
+import pytest
+
+from parity import CHUNK_FIELDS
+from particlemethod_fsi_amd import MphSolver, cases
+from particlemethod_fsi_amd.mphio import Cuboid
+
+pytestmark = pytest.mark.gpu
+
+VIRIAL = ["VirialStressAtParticle", "VirialPressureAtParticle"]
+CALLS = (16, 29, 40)
+CASES = ["tank", "box3d_jit", "seam3d", "movwall3d", "rolling3d", "turek2d", "turek2d_fluid", "dam2d", "box3d_st",
+         "gate3d"]
+STRUCTURES = {"turek2d", "gate3d"}   # cases with structure particles: the fold stays off
+
+
+def tank():
+    """The tank of test_gpu_idle_walls.py: 12,000 particles, 10,800 of them walls, the outer half of
+    the fluid block started at 0.8 m/s along +x."""
+    dx = 0.001
+    c = cases.Case("idle_tank", 3, "dam", dx, (-0.01, 0.0, -0.01), (0.045, 0.055, 0.03), [
+        Cuboid(1, (0.0, 0.003, 0.0), (0.010, 0.015, 0.010), dx),
+        Cuboid(4, (0.0, 0.0, 0.0), (0.030, 0.003, 0.016), dx),
+        Cuboid(4, (0.030, 0.0, 0.0), (0.033, 0.030, 0.016), dx),
+        Cuboid(4, (-0.003, 0.0, 0.0), (0.0, 0.030, 0.016), dx),
+        Cuboid(4, (-0.003, 0.0, -0.003), (0.033, 0.030, 0.0), dx),
+        Cuboid(4, (-0.003, 0.0, 0.016), (0.033, 0.030, 0.019), dx),
+    ])
+    cfg, parts = c.build()
+    assert parts.n == 12000
+    parts.velocity[(parts.property < 2) & (parts.position[:, 0] > 0.005)] = (0.8, 0.0, 0.0)
+    return cfg, parts
+
+
+def turek_fluid():
+    """turek2d with fluid where its elastic plate is: no structure particle, so the fold is on and the
+    per-step inlet profile (move_and_wrap) runs in pass B's tail."""
+    t = cases.get("turek2d")
+    cuboids = [Cuboid(1, c.lower, c.upper, c.space) if c.type == 2 else c for c in t.cuboids]
+    return cases.Case("turek2d_fluid", 2, "turek_hron", t.spacing, t.lower, t.upper, cuboids).build()
+
+
+def snapshot(s):
+    out = {f: s.get(f) for f in CHUNK_FIELDS}
+    s.compute_virial()
+    out.update({f: s.get(f) for f in VIRIAL})
+    return out
+
+
+def counters(s):
+    lean = s.lean_step_stats()
+    fold = s.key_fold_stats()
+    return {"lazy": s.idle_wall_stats()["lazy_steps"], "lean_search": lean["search_steps"],
+            "lean_pass_a": lean["pass_a_steps"], "folded": fold["folded_steps"], "prep": fold["prep_launches"]}
+
+
+ZERO = {"lazy": 0, "lean_search": 0, "lean_pass_a": 0, "folded": 0}
+
+
+def one_call(cfg, parts, n, monitors=False):
+    with MphSolver(cfg, parts) as s:
+        if monitors:
+            s.monitor(stride=1, capacity=64)
+        s.step(n)
+        return snapshot(s), counters(s)
+
+
+def assert_same(a, b, context):
+    for f in a:
+        assert np.array_equal(a[f], b[f], equal_nan=True), (context, f)
+
+
+_built, _single = {}, {}
+
+
+def build(case):
+    if case not in _built:
+        _built[case] = tank() if case == "tank" else turek_fluid() if case == "turek2d_fluid" else \
+            cases.get(case).build()
+    return _built[case]
+
+
+def single_steps(case):
+    """40 x mph_step(1) on `case`, every step full: the snapshots after 16, 29 and 40 steps.  Computed
+    once per case and shared, never changed."""
+    if case not in _single:
+        snaps = {}
+        with MphSolver(*build(case)) as s:
+            for k in range(1, max(CALLS) + 1):
+                s.step(1)
+                if k in CALLS:
+                    snaps[k] = snapshot(s)
+            assert counters(s) == dict(ZERO, prep=max(CALLS))
+        _single[case] = snaps
+    return _single[case]
+
+
+def lazy_steps(n):
+    """Every step of one mph_step(n) is lazy but the last of the last whole batch and the call's last."""
+    return n - 1 - (1 if n >= 8 and n % 8 else 0)
+
+
+def folded_steps(n):
+    """Seven of every 8-step graph's steps leave the next one's keys; a single-step graph folds nothing."""
+    return 7 * (n // 8)
+
+
+@pytest.mark.parametrize("n", CALLS)
+@pytest.mark.parametrize("case", CASES)
+def test_one_call_equals_single_steps(case, n):
+    snap, c = one_call(*build(case), n)
+    print(case, n, c)
+    assert c["lazy"] == lazy_steps(n), c
+    assert c["folded"] == (0 if case in STRUCTURES else folded_steps(n)) and c["prep"] == n - c["folded"], c
+    assert_same(snap, single_steps(case)[n], (case, n))
+
+
+@pytest.mark.parametrize("n", CALLS)
+def test_balanced_xcd_map(n, monkeypatch):
+    """The tank with the work-balanced XCD map of the passes forced on: a full step's map is now as
+    old as the previous call's end (list_block falls back to the equal ranges where a range does
+    not fit)."""
+    monkeypatch.setenv("MPH_XCD_BAL_MIN", "0")
+    snap, c = one_call(*build("tank"), n)
+    monkeypatch.delenv("MPH_XCD_BAL_MIN")
+    assert c["lazy"] == lazy_steps(n) and c["folded"] == folded_steps(n), c
+    assert_same(snap, single_steps("tank")[n], ("tank, MPH_XCD_BAL_MIN=0", n))
+
+
+def test_counters():
+    """step(40) on the tank: 39 lazy steps, all of them lean, 35 folded, 5 k_prep launches; step(13): 7 +
+    4 lazy as before, 7 folded; step(8) and step(9): 7 and 7.  Structures (gate3d): none folded."""
+    cfg, parts = build("tank")
+    assert one_call(cfg, parts, 40)[1] == {"lazy": 39, "lean_search": 39, "lean_pass_a": 39, "folded": 35, "prep": 5}
+    assert one_call(cfg, parts, 13)[1] == {"lazy": 11, "lean_search": 11, "lean_pass_a": 11, "folded": 7, "prep": 6}
+    for n in (8, 9):
+        c = one_call(cfg, parts, n)[1]
+        assert c["lazy"] == 7 and c["folded"] == 7, (n, c)
+    c = one_call(*build("gate3d"), 40)[1]
+    assert c["lazy"] == 39 and c["folded"] == 0 and c["prep"] == 40, c
+
+
+def test_two_calls_store_twice():
+    """Calls of 16 and 24 steps: each ends in a storing step of its own (15 + 23 lazy steps), and a
+    reader between them sees the 16th step's outputs."""
+    with MphSolver(*build("tank")) as s:
+        s.step(16)
+        mid = snapshot(s)
+        s.step(24)
+        c = counters(s)
+        end = snapshot(s)
+    assert c["lazy"] == 15 + 23, c
+    assert_same(mid, single_steps("tank")[16], "first call")
+    assert_same(end, single_steps("tank")[40], "second call")
+
+
+def test_monitors_keep_every_step_full():
+    """With monitors no step is lazy; the batches before a call's last still store no output-only field."""
+    snap, c = one_call(*build("tank"), 40, monitors=True)
+    assert c == dict(ZERO, prep=40), c
+    assert_same(snap, single_steps("tank")[40], "monitors")
+
+
+def test_step_paths_fold_alike():
+    """Nine steps phase-timed and nine profiled (one direct-launch batch each, folded like a graph)
+    against nine single steps, on the off-lattice box."""
+    cfg, parts = build("box3d_jit")
+    snaps = []
+    for way in ("single", "phase", "profile"):
+        with MphSolver(cfg, parts) as s:
+            if way == "single":
+                for _ in range(9):
+                    s.step(1)
+            elif way == "phase":
+                s.phase_timing(True)
+                s.step(9)
+            else:
+                s.profile(9)
+            c = counters(s)
+            snaps.append(snapshot(s))
+        assert c["folded"] == {"single": 0, "phase": 7, "profile": 8}[way], (way, c)
+    assert_same(snaps[1], snaps[0], "phase-timed")
+    assert_same(snaps[2], snaps[0], "profiled")
+
+
+def test_fold_on_equals_off(monkeypatch):
+    """MPH_KEY_FOLD=0 at creation: no step folded, every step opens with k_prep, the lazy counts and
+    the bits of the default."""
+    monkeypatch.setenv("MPH_KEY_FOLD", "0")
+    off, c = one_call(*build("tank"), 40)
+    off_seam, c_seam = one_call(*build("seam3d"), 29)
+    monkeypatch.delenv("MPH_KEY_FOLD")
+    assert c == {"lazy": 39, "lean_search": 39, "lean_pass_a": 39, "folded": 0, "prep": 40}, c
+    assert c_seam["folded"] == 0 and c_seam["lazy"] == lazy_steps(29), c_seam
+    assert_same(off, single_steps("tank")[40], "MPH_KEY_FOLD=0")
+    assert_same(off_seam, single_steps("seam3d")[29], "MPH_KEY_FOLD=0, seam3d")
+
+
+def test_on_equals_off(monkeypatch):
+    """MPH_LEAN_CALLS=0 at creation: every whole batch ends in a storing step (35 lazy steps of 40, 7 + 7
+    + 4 of 29), the same bits."""
+    monkeypatch.setenv("MPH_LEAN_CALLS", "0")
+    off40, c40 = one_call(*build("tank"), 40)
+    off29, c29 = one_call(*build("tank"), 29)
+    monkeypatch.delenv("MPH_LEAN_CALLS")
+    assert c40["lazy"] == 35 and c29["lazy"] == 7 * 3 + 4, (c40, c29)
+    assert_same(off40, single_steps("tank")[40], "MPH_LEAN_CALLS=0, 40")
+    assert_same(off29, single_steps("tank")[29], "MPH_LEAN_CALLS=0, 29")
