@@ -32,11 +32,10 @@ struct MphCtx {
     double time = 0.0;           // host mirror of Time (same additions as the device)
     bool stepped = false;
     hipStream_t stream = nullptr;
-    hipGraphExec_t graph1 = nullptr, graph8 = nullptr;
-    hipGraphExec_t graph1t = nullptr;   // one step without the output-only stores (single context)
-    // eight steps without them: every whole batch of a call but its last (replay_plan); captured
-    // only where lean_calls (a single context, MPH_LEAN_CALLS not 0 at creation: ctx_fill_launch)
-    hipGraphExec_t graph8t = nullptr;
+    // the step graphs by kind (mph_kernels.h kSeqs).  The two without the output-only stores belong
+    // to a single context alone, and kSeq8t -- every whole batch of a call but its last
+    // (replay_plan) -- only where lean_calls (MPH_LEAN_CALLS not 0 at creation: ctx_fill_launch)
+    hipGraphExec_t graph[mph::kSeqKinds] = {};
     bool lean_calls = false;
     // step batching (mph_set_step_batching): single mph_step calls accumulate into 8-step graphs;
     // `pending` steps are accepted but not launched yet, `unchecked`: batches launched whose error
@@ -150,16 +149,15 @@ inline void ctx_stepped(MphCtx* c, int nsteps, bool a_current)
     if (a_current) c->a_current = true;
 }
 
-// `steps` steps captured from the context's stream into an uploaded graph (so the first launch costs
-// what later ones do): enqueue(k) puts step k on the stream and returns MPH_OK or the status that
-// ends the capture, whose graph is then destroyed.
+// A sequence of steps captured from the context's stream into an uploaded graph (so the first launch
+// costs what later ones do): enqueue() puts the steps on the stream and returns MPH_OK or the status
+// that ends the capture, whose graph is then destroyed.
 template <typename Enqueue>
-int ctx_capture(MphCtx* c, int steps, hipGraphExec_t* out, Enqueue enqueue)
+int ctx_capture(MphCtx* c, hipGraphExec_t* out, Enqueue enqueue)
 {
     hipGraph_t g = nullptr;
     MPH_HIP_OK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    int rc = MPH_OK;
-    for (int k = 0; k < steps && rc == MPH_OK; ++k) rc = enqueue(k);
+    const int rc = enqueue();
     const hipError_t e = hipStreamEndCapture(c->stream, &g);
     if (rc != MPH_OK) {
         if (g) (void)hipGraphDestroy(g);
@@ -173,10 +171,10 @@ int ctx_capture(MphCtx* c, int steps, hipGraphExec_t* out, Enqueue enqueue)
     return MPH_OK;
 }
 
-// n steps replayed from the captured graphs in the order of replay_plan (mph_kernels.h): graph8t (no
-// output-only stores) for every whole batch but the last where the context has it, graph8 for the
-// last, then single steps -- graph1t for all but the last where the context has it, graph1 for the
-// last, so the outputs are stored on the call's last step; a slab context has graph8 and graph1 only
+// n steps replayed from the captured graphs in the order of replay_plan (mph_kernels.h): kSeq8t (no
+// output-only stores) for every whole batch but the last where the context has it, kSeq8 for the
+// last, then single steps -- kSeq1t for all but the last where the context has it, kSeq1 for the
+// last, so the outputs are stored on the call's last step; a slab context has kSeq8 and kSeq1 only
 int ctx_replay(MphCtx* c, int n);
 
 // Step batching: launch the steps accepted but not launched and read the error flags of everything
@@ -231,10 +229,9 @@ struct EventProfiler final : Profiler {
     }
 };
 
-// one step of a single context on L's stream (mph_step.hip); last: the batch's last step; ev: the
-// phase events; k of `steps` enqueued together, next_last: step k + 1 is a last one (the key fold)
-void enqueue_step(const Launch& L, bool last, hipEvent_t* ev = nullptr, int k = 0, int steps = 1,
-                  bool next_last = true);
+// the steps of one sequence of a single context on L's stream (mph_step.hip); ev: phase timing's
+// events, three per step, else null
+void enqueue_steps(const Launch& L, StepSeq seq, hipEvent_t* ev = nullptr);
 
 void ctx_set_global_error(const std::string& msg);   // mph_last_error(NULL)
 // ids/n_glob: slab-local creation (the arrays hold n of n_glob particles, original indices ids)

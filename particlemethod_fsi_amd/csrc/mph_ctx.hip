@@ -84,21 +84,19 @@ int ctx_status(MphCtx* c)
 int drop_graphs(MphCtx* c)
 {
     MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
-    for (hipGraphExec_t* g : {&c->graph1, &c->graph1t, &c->graph8, &c->graph8t})
-        if (*g) {
-            MPH_HIP_OK(c, hipGraphExecDestroy(*g));
-            *g = nullptr;
+    for (hipGraphExec_t& g : c->graph)
+        if (g) {
+            MPH_HIP_OK(c, hipGraphExecDestroy(g));
+            g = nullptr;
         }
     return MPH_OK;
 }
 
 int ctx_replay(MphCtx* c, int n)
 {
-    const ReplayPlan p = replay_plan(n, c->graph8t != nullptr, c->graph1t != nullptr);
-    for (int k = 0; k < p.batch8t; ++k) MPH_HIP_OK(c, hipGraphLaunch(c->graph8t, c->stream));
-    for (int k = 0; k < p.batch8; ++k) MPH_HIP_OK(c, hipGraphLaunch(c->graph8, c->stream));
-    for (int k = 0; k < p.single1t; ++k) MPH_HIP_OK(c, hipGraphLaunch(c->graph1t, c->stream));
-    for (int k = 0; k < p.single1; ++k) MPH_HIP_OK(c, hipGraphLaunch(c->graph1, c->stream));
+    const ReplayPlan p = replay_plan(n, c->graph[kSeq8t] != nullptr, c->graph[kSeq1t] != nullptr);
+    for (int kind = 0; kind < kSeqKinds; ++kind)
+        for (int k = 0; k < p.count[kind]; ++k) MPH_HIP_OK(c, hipGraphLaunch(c->graph[kind], c->stream));
     return MPH_OK;
 }
 
@@ -109,19 +107,19 @@ void ctx_fill_launch(MphCtx* c)
     // MPH_LIST_FULL=1: the lists keep every neighbour within the search radius, like the reference's
     // Neighbor[] (mph_neighbor_rows needs them); else only those the passes' sums can take
     if (env_int("MPH_LIST_FULL", 0) == 1) c->P.rlf = 3.0e38f;
-    // MPH_LAZY_WALLS=0: no lazy wall steps (step_launch), every step searches and sums every wall
+    // MPH_LAZY_WALLS=0: no lazy wall steps (seq_step), every step searches and sums every wall
     // wave; slab contexts never take them (a halo wall may have a fluid neighbour on the next rank)
     c->lazy_walls = !c->dist && env_int("MPH_LAZY_WALLS", 1) != 0;
-    // MPH_LEAN_STEPS=0: the lazy steps launch the kernels of the full steps' arithmetic (step_launch);
+    // MPH_LEAN_STEPS=0: the lazy steps launch the kernels of the full steps' arithmetic (seq_step);
     // the lean search also needs the list radius below the search radius' FP32 band (lean_search_ok:
     // not with MPH_LIST_FULL=1)
     L.lean_ok = env_int("MPH_LEAN_STEPS", 1) != 0;
     L.lean_search = L.lean_ok && lean_search_ok(c->P);
     // MPH_LEAN_CALLS=0: every whole batch of a call ends in a step that stores the output-only fields
-    // (no graph8t, replay_plan), not only the call's last; slab contexts never take the lean batches
+    // (no kSeq8t graph, replay_plan), not only the call's last; slab contexts never take the lean batches
     c->lean_calls = !c->dist && env_int("MPH_LEAN_CALLS", 1) != 0;
     // MPH_KEY_FOLD=0: every step opens with k_prep, no pass B leaves the next step's cell keys
-    // (step_keys); slab contexts never fold
+    // (seq_step); slab contexts never fold
     L.key_fold = !c->dist && env_int("MPH_KEY_FOLD", 1) != 0;
     L.P = &c->P;
     L.stream = c->stream;
@@ -164,10 +162,8 @@ void mph_destroy(MphCtx* c)
     if (c->hs_pin) (void)hipHostFree(c->hs_pin);
     if (c->ev_status) (void)hipEventDestroy(c->ev_status);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->graph1) (void)hipGraphExecDestroy(c->graph1);
-    if (c->graph1t) (void)hipGraphExecDestroy(c->graph1t);
-    if (c->graph8) (void)hipGraphExecDestroy(c->graph8);
-    if (c->graph8t) (void)hipGraphExecDestroy(c->graph8t);
+    for (hipGraphExec_t g : c->graph)
+        if (g) (void)hipGraphExecDestroy(g);
     for (auto* v : {&c->ev8, &c->ev_vir})
         for (hipEvent_t e : *v) (void)hipEventDestroy(e);
     if (c->dist) dist_free(c);

@@ -1,8 +1,8 @@
 // mph_device.h -- device helpers and the host-side launcher shared by the kernel translation units
 // (mph_sort.hip, mph_search.hip, mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip,
 // mph_sample.hip): the reference's exact periodic arithmetic, the cell grid's indexing, buffer-
-// descriptor loads, the type predicates, wave-level helpers, a particle's wall motion and wrap, the
-// stencil around a point, and launch / blocks / by_dim.  A helper used by one unit alone stays in that
+// descriptor loads, the type predicates, wave-level helpers, a particle's wall motion and wrap, the prep tail, the
+// stencil around a point, and launch / blocks / by_dim / by_flag.  A helper used by one unit alone stays in that
 // unit; the neighbour lists' layout is mph_list.h.
 #pragma once
 
@@ -281,6 +281,51 @@ __device__ __forceinline__ void move_and_wrap(const DevParams& P, const DevState
     B.z[p] = z;
 }
 
+// ---------------------------------------------------------------------------- prep tail -----
+// What opens a step's sort from a particle's moved and wrapped position, shared by k_prep and by the
+// KEYS tail of the previous step's pass B: one body, so the two leave the
+// same bits.
+
+// The non-finite flag, the cell key (stored to *key and returned), the coarse map's mark and the face
+// bits (occ).  cmap: a lazy wall step's coarse map (mph_params.h kCoarseShift), else null; a non-wall
+// particle marks its coarse cell -- a plain store of the same byte by every marker, no atomic (the
+// search reads the map, pass A clears it).  not_wall() is asked only with the map set.
+template <typename NotWall>
+__device__ __forceinline__ int prep_cell(const DevParams& P, const DevState* st, double x, double y, double z,
+                                         int* key, unsigned char* cmap, NotWall not_wall, int& occ)
+{
+    if (!isfinite(x + y + z)) atomicOr(const_cast<int*>(&st->overflow), 4);   // MPH_ERR_NONFINITE
+    const int cx = cell_axis(x, P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
+    const int cy = cell_axis(y, P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
+    const int cz = P.dim == 3 ? cell_axis(z, P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
+    const int k = cell_index(P, cx, cy, cz);   // (cell_id)
+    *key = k;
+    if (cmap && not_wall())
+        cmap[coarse_index(P, cx >> kCoarseShift, cy >> kCoarseShift, cz >> kCoarseShift)] = 1;
+    occ = seam_bits(P, x, y, z);
+    return k;
+}
+
+// The particles arrive in the previous cell order, so consecutive lanes often share a cell: one
+// histogram atomic per run of equal keys; returns the lane's slot in its cell (run base + rank in the
+// run).  Every lane of the wave takes part in the shuffles; the lanes past n (live false) come with
+// k = -1 - lane, so they form runs of their own, and their result is not a slot.
+__device__ __forceinline__ int prep_slot(int k, bool live, int* __restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const int kprev = __shfl_up(k, 1, 64);
+    const bool head = lane == 0 || kprev != k;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+    const int hl = 63 - __clzll(heads & upto);
+    const unsigned long long above = heads & ~upto;
+    const int next = above ? __ffsll((long long)above) - 1 : 64;
+    int base = 0;
+    if (live && head) base = atomicAdd(&cnt[k], next - lane);
+    base = __shfl(base, hl, 64);
+    return base + (lane - hl);
+}
+
 // entry p of a sort input C: its set (C or the VSrc's V) and index there; mig: a kept migrant
 // (its id is read negated)
 __device__ __forceinline__ int vsrc_entry(const VSrc& vs, const Soa& C, int p, Soa& S, bool& mig)
@@ -406,6 +451,14 @@ static void by_dim(int dim, F&& f)
 {
     if (dim == 3) f(Int<3>{});
     else f(Int<2>{});
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a kernel's template flag from a step's form
+template <typename F>
+static void by_flag(bool on, F&& f)
+{
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 }  // namespace mph

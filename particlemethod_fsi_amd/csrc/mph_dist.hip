@@ -489,8 +489,11 @@ bool early_at(const MphCtx* c, int k, int steps, int out)
 
 int dist_capture(MphCtx* c, int steps, hipGraphExec_t* out)
 {
-    return ctx_capture(c, steps, out, [&](int k) {
-        return dist_enqueue_step(c, nullptr, early_at(c, k, steps, 0), early_at(c, k, steps, 1));
+    return ctx_capture(c, out, [&] {
+        int rc = MPH_OK;
+        for (int k = 0; k < steps && rc == MPH_OK; ++k)
+            rc = dist_enqueue_step(c, nullptr, early_at(c, k, steps, 0), early_at(c, k, steps, 1));
+        return rc;
     });
 }
 
@@ -515,8 +518,8 @@ int dist_step_batch(MphCtx* c, int nsteps, Profiler* prof)
     // refuses (an RCCL build without graph support) falls back to the same steps as direct
     // launches, reported by mph_dist_info
     if (D.graphs && !prof &&
-        ((!c->graph1 && dist_capture(c, 1, &c->graph1) != MPH_OK) ||
-         (!c->graph8 && dist_capture(c, 8, &c->graph8) != MPH_OK))) {
+        ((!c->graph[kSeq1] && dist_capture(c, 1, &c->graph[kSeq1]) != MPH_OK) ||
+         (!c->graph[kSeq8] && dist_capture(c, 8, &c->graph[kSeq8]) != MPH_OK))) {
         (void)hipGetLastError();
         D.graphs = false;
         c->err.clear();

@@ -2,7 +2,7 @@
 // hot path, the one host-visible interface of the kernel units (mph_sort.hip, mph_search.hip,
 // mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip, mph_sample.hip), used by the context's
 // host units (mph_ctx.h) and the slab layer's (mph_dist.h).  It also decides a step's form
-// (step_launch): plain host C++, so a host compiler can include this header and test it.
+// (seq_step): plain host C++, so a host compiler can include this header and test it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -110,7 +110,7 @@ struct MonitorDev {
 };
 
 // A step's form: which variant of its kernels a step launches.  Decided by
-// step_launch below and nowhere else; all false in the context's own Launch, in the slab steps and
+// seq_step below and nowhere else; all false in the context's own Launch, in the slab steps and
 // in every launch outside a step.
 struct StepForm {
     // a lazy wall step (mph_params.h kCoarseShift): k_prep marks the coarse map, the search skips the
@@ -119,7 +119,7 @@ struct StepForm {
     // lean steps: a lazy step whose search accepts only the pairs it stores
     // and counts no NeighborCount / whose pass A leaves out the DensityA and GravityCenter sums
     bool lean_search = false, lean_pass_a = false;
-    // the key fold (step_keys below): keys_done, the previous step's pass B has moved and wrapped the
+    // the key fold (seq_step below): keys_done, the previous step's pass B has moved and wrapped the
     // particles and left this step's cell keys, slots and histogram, so the sort launches no k_prep;
     // keys_next, this step's pass B does that for the next step
     bool keys_done = false, keys_next = false;
@@ -154,11 +154,11 @@ struct Launch {
     // lean steps, the context's capabilities (set at creation, ctx_fill_launch): lean_ok, it takes
     // them (MPH_LEAN_STEPS); lean_search, and its radii let the search (lean_search_ok)
     bool lean_ok = false, lean_search = false;
-    // the key fold, the context's choice (MPH_KEY_FOLD, ctx_fill_launch); step_keys has the rest
+    // the key fold, the context's choice (MPH_KEY_FOLD, ctx_fill_launch); seq_step has the rest
     bool key_fold = false;
     // keys_next: the coarse map the next step's search reads -- set where that step is lazy, else null
     unsigned char* cmap_next = nullptr;
-    StepForm form;   // this step's (step_launch, step_keys)
+    StepForm form;   // this step's (seq_step)
     // pass A products (A order): pressure values, gravity centre (GC, PressureA), sums
     double *pres = nullptr, *gx = nullptr, *gy = nullptr, *gz = nullptr, *pa = nullptr;
     double *dens_a = nullptr, *vstrain = nullptr, *divp = nullptr;
@@ -181,67 +181,85 @@ inline Launch trim_outputs(Launch L)
     L.force = L.acc = nullptr;
     return L;
 }
+// whether a step's Launch is an untrimmed one (Force is allocated at every creation)
+inline bool stores_outputs(const Launch& S) { return S.force != nullptr; }
 
-// The Launch of one step of a single context, from the context's: the outputs trimmed unless the
-// step is the `last` of its batch, and the step's form.
-// Lazy wall steps take the output rule one kernel further up.  On a step that is not `last`, a wall
-// walks no list in pass B, so what the search and pass A compute for a wall particle whose
-// neighbours are all walls -- its list, PressureP, the pass-B record, fpart -- has no reader; the
-// batch's last step computes all of it again.  Off (every step full) without the map (slab mode,
-// MPH_LAZY_WALLS=0) and while the monitor kernels run, which read the walls' pressure on every step.
-// A lean step is a lazy step that also leaves out what it would compute only to drop it: the search
-// where the context's radii allow (Launch.lean_search), pass A where GravityCenter is not stored
-// (DensityA never is on a lazy step).
-inline Launch step_launch(const Launch& L, bool last)
-{
-    Launch S = last ? L : trim_outputs(L);
-    S.form.lazy = !last && L.cmap && !L.mon;
-    S.form.lean_search = S.form.lazy && L.lean_ok && L.lean_search;
-    S.form.lean_pass_a = S.form.lazy && L.lean_ok && !L.P->surface;
-    return S;
-}
+// Steps enqueued together with nothing between them (a captured graph, a phase-timed or profiled
+// batch): their number and whether the last one stores the output-only fields.
+struct StepSeq {
+    int steps = 1;
+    bool store_last = true;
+};
+// The four kinds a context replays, in replay_plan's launch order; the profiler's batch of n steps is
+// StepSeq{n, true}.
+enum SeqKind { kSeq8t = 0, kSeq8, kSeq1t, kSeq1, kSeqKinds };
+constexpr StepSeq kSeqs[kSeqKinds] = {{8, false}, {8, true}, {1, false}, {1, true}};
 
 // The key fold.  A step opens with k_prep: wall motion, periodic wrap, cell
 // key, histogram -- all of it from what the previous step's pass B had in registers when it stored
 // them.  Where nothing can come between the two, pass B does k_prep's work before its stores
 // (k_pass_b<.., KEYS>) and the next step's sort starts at the scan.  Nothing comes between them
-// inside one enqueued sequence of steps (a captured graph, a phase-timed or profiled batch): k is the
-// step's index there, `steps` their number, next_last whether step k + 1 stores the output-only
-// fields.  Never across the sequence's end (the state a caller reads is the unmoved one), never with
-// structure particles (the elastic substeps write the set after pass B), monitors (they read the
-// unmoved set) or a slab context (vsrc).  S: the step's Launch from step_launch; L: the context's.
+// inside one sequence.  Never across the sequence's end (the state a caller reads is the unmoved
+// one), never with structure particles (the elastic substeps write the set after pass B), monitors
+// (they read the unmoved set) or a slab context (vsrc).
 inline bool key_fold_ok(const Launch& L)
 {
     return L.key_fold && L.P->n_struct == 0 && !L.mon && !L.vsrc.idx;
 }
-inline Launch step_keys(Launch S, const Launch& L, int k, int steps, bool next_last)
+
+// The Launch of step k of a sequence of a single context, from the context's: the outputs trimmed
+// unless the step is the storing last one, and the step's form -- decided here and nowhere else.
+// Lazy wall steps take the output rule one kernel further up.  On a step that does not store, a wall
+// walks no list in pass B, so what the search and pass A compute for a wall particle whose
+// neighbours are all walls -- its list, PressureP, the pass-B record, fpart -- has no reader; the
+// next storing step computes all of it again.  Off (every step full) without the map (slab mode,
+// MPH_LAZY_WALLS=0) and while the monitor kernels run, which read the walls' pressure on every step.
+// A lean step is a lazy step that also leaves out what it would compute only to drop it: the search
+// where the context's radii allow (Launch.lean_search), pass A where GravityCenter is not stored
+// (DensityA never is on a lazy step).
+// The key fold: a step's keys come from the step before it in the sequence and it leaves the keys of
+// the step after it, with the coarse map where that step is lazy (cmap_next).
+inline Launch seq_step(const Launch& L, StepSeq seq, int k)
 {
-    const bool ok = key_fold_ok(L);
-    S.form.keys_done = ok && k > 0;
-    S.form.keys_next = ok && k + 1 < steps;
-    S.cmap_next = S.form.keys_next && step_launch(L, next_last).form.lazy ? L.cmap : nullptr;
+    const auto stores = [&](int j) { return seq.store_last && j == seq.steps - 1; };
+    const auto lazy = [&](int j) { return !stores(j) && L.cmap && !L.mon; };
+    Launch S = stores(k) ? L : trim_outputs(L);
+    S.form.lazy = lazy(k);
+    S.form.lean_search = S.form.lazy && L.lean_ok && L.lean_search;
+    S.form.lean_pass_a = S.form.lazy && L.lean_ok && !L.P->surface;
+    S.form.keys_done = key_fold_ok(L) && k > 0;
+    S.form.keys_next = key_fold_ok(L) && k + 1 < seq.steps;
+    S.cmap_next = S.form.keys_next && lazy(k + 1) ? L.cmap : nullptr;
     return S;
 }
 
-// How n steps of one call are cut into batches, launched in this order:
-// batch8t whole batches of eight steps none of which stores the output-only fields, batch8 of eight
-// whose last step stores them, single1t single steps that store none, single1 that do.  A call can
-// only be observed after it returns, so only its last step needs them: with `lean8` (the context has
-// the all-lean 8-step graph) every whole batch but the last is a batch8t, and with `lean1` every
-// step of the remainder but the last is a single1t.  Without either, every batch and every single
-// step ends in a storing step of its own (a slab context's sequence).  Plain host C++, no HIP call.
+// What the launchers read off a step's Launch instead of deriving it again: the coarse map a lazy
+// step's kernels take (null on every other launch), and whether a launch over the lazy step's
+// balanced XCD map (list_grid's lazy grid, the sort's split 2, the search's xcd_sfrac).
+inline unsigned char* lazy_cmap(const Launch& L) { return L.form.lazy ? L.cmap : nullptr; }
+inline bool xcd_bal(const Launch& L) { return L.P->n >= L.xcd_bal_min; }
+inline bool lazy_bal(const Launch& L) { return L.form.lazy && xcd_bal(L); }
+
+// How n steps of one call are cut into sequences: the count of each kind,
+// launched in the kinds' order -- whole batches of eight steps none of which stores the output-only
+// fields, batches of eight whose last step stores them, single steps that store none, single steps
+// that do.  A call can only be observed after it returns, so only its last step needs them: with
+// `lean8` (the context has the all-lean 8-step graph) every whole batch but the last is a kSeq8t, and
+// with `lean1` every step of the remainder but the last is a kSeq1t.  Without either, every batch and
+// every single step ends in a storing step of its own (a slab context's sequence).  Plain host C++,
+// no HIP call.
 struct ReplayPlan {
-    int batch8t = 0, batch8 = 0, single1t = 0, single1 = 0;
+    int count[kSeqKinds] = {0, 0, 0, 0};
 };
 inline ReplayPlan replay_plan(int n, bool lean8, bool lean1)
 {
     ReplayPlan p;
     if (n <= 0) return p;
     const int whole = n / 8, rest = n % 8;
-    p.batch8t = lean8 && whole >= 2 ? whole - 1 : 0;
-    p.batch8 = whole - p.batch8t;
-    p.single1t = lean1 && rest > 1 ? rest - 1 : 0;
-    p.single1 = rest - p.single1t;
+    p.count[kSeq8t] = lean8 && whole >= 2 ? whole - 1 : 0;
+    p.count[kSeq8] = whole - p.count[kSeq8t];
+    p.count[kSeq1t] = lean1 && rest > 1 ? rest - 1 : 0;
+    p.count[kSeq1] = rest - p.count[kSeq1t];
     return p;
 }
 

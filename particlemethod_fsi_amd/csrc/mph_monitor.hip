@@ -1,6 +1,6 @@
 // mph_monitor.hip -- per-step monitors (include/mph_gpu.h mph_monitor_*): sums, extrema, tracked
 // particles and pressure probes of the state a step leaves, reduced on the device into one record
-// per sampled step of a ring buffer.  Launched at the end of every step (enqueue_step) while
+// per sampled step of a ring buffer.  Launched at the end of every step (enqueue_steps) while
 // monitors are on, so a sample is taken by whichever path runs the step (captured graphs, direct
 // launches) and the host reads the ring without breaking a batch.
 //

@@ -279,7 +279,7 @@ struct DevState {
     // form, and those whose pass A did, since the creation -- each bumped by block 0 of its kernel
     // (mph_lean_step_stats).  Behind every older member, whose offsets the other kernels keep.
     unsigned long long lean_search_steps, lean_pass_a_steps;
-    // the key fold (mph_kernels.h step_keys), counted the same way since the creation: the steps whose
+    // the key fold (mph_kernels.h seq_step), counted the same way since the creation: the steps whose
     // pass B left the next step's cell keys (bumped by block 0 of k_pass_b's KEYS form), and the
     // steps that opened with a k_prep launch (by k_place) -- mph_key_fold_stats
     unsigned long long key_fold_steps, prep_steps;

@@ -421,9 +421,9 @@ struct KeyOut {
 // ViscosityV (2478-2522) for non-structure i; InterfaceForce (2439-2472) for structure i; then
 // Gravity (2917-2936), Acceleration/kick (2938-2956) and Convection/drift (1892-1907).  The sums
 // start from pass A's fpart (P_i half of the pressure force + viscous force).
-// KEYS (the key fold, mph_kernels.h step_keys; single contexts without structure particles): the
+// KEYS (the key fold, mph_kernels.h seq_step; single contexts without structure particles): the
 // kernel ends with the next step's k_prep on the values it is about to store -- the same
-// move_and_wrap, cell_axis and cell_index, so the same bits -- and leaves key, slot, the cell
+// move_and_wrap, prep_cell and prep_slot (mph_device.h), so the same bits -- and leaves key, slot, the cell
 // histogram, the non-finite flag, the face bits and (cmap set: the next step is lazy) the coarse
 // map.  This step's k_place has advanced Time, WallCenter and seam_step, its k_scan_down has
 // re-zeroed cnt and its pass A has cleared the map, so the tail sees what that k_prep would.  The
@@ -542,28 +542,11 @@ __global__ __launch_bounds__(MPH_LB) MPH_PB_ATTR void k_pass_b(DevParams P, cons
             B.id[i] = A.id[i];
             double x = xo0, y = xo1, z = xo2;
             move_and_wrap(P, st, B, i, x, y, z);   // (reads the type just stored; stores the position)
-            if (!isfinite(x + y + z)) atomicOr(const_cast<int*>(&st->overflow), 4);   // MPH_ERR_NONFINITE
-            const int cx = cell_axis(x, P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
-            const int cy = cell_axis(y, P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
-            const int cz = P.dim == 3 ? cell_axis(z, P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
-            k = cell_index(P, cx, cy, cz);
-            K.key[i] = k;
-            if (K.cmap && !dev_is_wall(ti))
-                K.cmap[coarse_index(P, cx >> kCoarseShift, cy >> kCoarseShift, cz >> kCoarseShift)] = 1;
-            occ = seam_bits(P, x, y, z);
+            k = prep_cell(P, st, x, y, z, &K.key[i], K.cmap, [&] { return !dev_is_wall(ti); }, occ);
         }
-        // one histogram atomic per run of equal keys (k_prep has the derivation)
-        const int kprev = __shfl_up(k, 1, 64);
-        const bool head = lane == 0 || kprev != k;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
-        const int hl = 63 - __clzll(heads & upto);
-        const unsigned long long above = heads & ~upto;
-        const int next = above ? __ffsll((long long)above) - 1 : 64;
-        int base = 0;
-        if (live && head) base = atomicAdd(&K.cnt[k], next - lane);
-        base = __shfl(base, hl, 64);
-        if (live) K.slot[i] = base + (lane - hl);
+        // one histogram atomic per run of equal keys (prep_slot)
+        const int s = prep_slot(k, live, K.cnt);
+        if (live) K.slot[i] = s;
         // the wave's face bits: one device atomic, only for bits the next step's word does not hold
         if (__ballot(occ != 0)) {
 #pragma unroll
@@ -693,18 +676,15 @@ void launch_pass_a(const Launch& L)
 {
     const DevParams& P = *L.P;
     if (P.n == 0) return;
-    // a lean step stores neither GravityCenter / PressureA nor the diagnostics (step_launch) and
+    // a lean step stores neither GravityCenter / PressureA nor the diagnostics (seq_step) and
     // leaves their sums out
-    const bool lazy = L.form.lazy;
-    auto go = [&](auto LEAN) {
+    by_flag(L.form.lean_pass_a, [&](auto LEAN) {
         by_dim(P.dim, [&](auto D) {
             launch(L.prof, "pass_a", L.stream, k_pass_a<decltype(D)::value, decltype(LEAN)::value>,
-                   dim3(list_grid(P.n, lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T, L.A, L.nbr, L.ncount,
-                   L.lhdr, L.lgap, pass_a_out(L), L.st, lazy ? L.cmap : nullptr, L.cmap_bytes);
+                   dim3(list_grid(P.n, lazy_bal(L))), dim3(MPH_LB), P, L.T, L.A, L.nbr, L.ncount, L.lhdr, L.lgap,
+                   pass_a_out(L), L.st, lazy_cmap(L), L.cmap_bytes);
         });
-    };
-    if (L.form.lean_pass_a) go(std::true_type{});
-    else go(std::false_type{});
+    });
 }
 
 // calculateNeighbor + the pass-A sums
@@ -738,24 +718,24 @@ void launch_pass_b(const Launch& L, int phase)
         std::fprintf(stderr, "mph: launch_pass_b with surface tension needs GravityCenter/PressureA\n");
         std::abort();
     }
-    // the key fold (step_keys): never on a step that stores Force, with structure particles, in a
+    // the key fold (seq_step): never on a step that stores Force, with structure particles, in a
     // slab's phases or on a slab's set
     const bool keys = L.form.keys_next;
     if (keys && (L.force || P.n_struct > 0 || phase || P.slab_axis >= 0 || P.n_dev)) {
         std::fprintf(stderr, "mph: launch_pass_b: the key fold on a step that cannot take it\n");
         std::abort();
     }
-    auto go = [&](auto SURF, auto KEYS) {
-        by_dim(P.dim, [&](auto D) {
-            launch(L.prof, phase == 2 ? "pass_b_face" : "pass_b", L.stream,
-                   k_pass_b<decltype(SURF)::value, decltype(D)::value, decltype(KEYS)::value>,
-                   dim3(list_grid(P.n, L.form.lazy && P.n >= L.xcd_bal_min)), dim3(MPH_LB), P, L.T, L.A,
-                   L.rec, L.fpart, L.gx, L.gy, L.gz, L.pa, L.nbr, L.ncount, L.lhdr, L.lgap, L.force, L.acc, L.B, phase,
-                   L.wface, struct_hook(L), L.st, keys ? KeyOut{L.key, L.slot, L.cnt, L.cmap_next} : KeyOut{});
+    by_flag(P.surface, [&](auto SURF) {
+        by_flag(keys, [&](auto KEYS) {
+            by_dim(P.dim, [&](auto D) {
+                launch(L.prof, phase == 2 ? "pass_b_face" : "pass_b", L.stream,
+                       k_pass_b<decltype(SURF)::value, decltype(D)::value, decltype(KEYS)::value>,
+                       dim3(list_grid(P.n, lazy_bal(L))), dim3(MPH_LB), P, L.T, L.A, L.rec, L.fpart, L.gx, L.gy, L.gz,
+                       L.pa, L.nbr, L.ncount, L.lhdr, L.lgap, L.force, L.acc, L.B, phase, L.wface, struct_hook(L),
+                       L.st, keys ? KeyOut{L.key, L.slot, L.cnt, L.cmap_next} : KeyOut{});
+            });
         });
-    };
-    if (P.surface) keys ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
-    else keys ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
+    });
 }
 
 void launch_virial(const Launch& L, const Soa& X, double* vir, double* vpres)

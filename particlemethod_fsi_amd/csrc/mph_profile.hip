@@ -28,7 +28,7 @@ int mph_profile_steps(MphCtx* c, int nsteps, double* avg_ms, int* launches, char
     } else {
         Launch L = c->L;
         L.prof = &prof;
-        for (int k = 0; k < nsteps; ++k) enqueue_step(L, k == nsteps - 1, nullptr, k, nsteps, k + 1 == nsteps - 1);
+        enqueue_steps(L, StepSeq{nsteps, true});
         MPH_HIP_OK(c, hipGetLastError());
         MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
         ctx_stepped(c, nsteps, true);
@@ -207,12 +207,31 @@ int mph_list_layout(MphCtx* c, long long out[6])
     return MPH_OK;
 }
 
-int mph_idle_wall_stats(MphCtx* c, long long out[2])
+// the counter readers' entry: the context entered and its stream drained, so the counters at the tail
+// of DevState are those of every step launched
+static int counters_enter(MphCtx* c, const long long* out)
 {
     if (!out) return MPH_ERR_ARG;
     MPH_CK(ctx_enter(c));
     MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
-    // the tail of DevState: the lazy steps, then the idle waves per run of the waves
+    return MPH_OK;
+}
+
+// two adjacent unsigned long long counters of DevState, the first at byte offset `first`, in one copy
+static int counter_pair(MphCtx* c, size_t first, long long out[2])
+{
+    MPH_CK(counters_enter(c, out));
+    unsigned long long v[2] = {0, 0};
+    MPH_HIP_OK(c, hipMemcpy(v, reinterpret_cast<const char*>(c->L.st) + first, sizeof(v), hipMemcpyDeviceToHost));
+    out[0] = (long long)v[0];
+    out[1] = (long long)v[1];
+    return MPH_OK;
+}
+
+int mph_idle_wall_stats(MphCtx* c, long long out[2])
+{
+    MPH_CK(counters_enter(c, out));
+    // the lazy steps, then the idle waves per run of the waves
     unsigned long long steps = 0;
     std::vector<unsigned> seg(kXcdSegs);
     const char* st = reinterpret_cast<const char*>(c->L.st);
@@ -228,32 +247,16 @@ int mph_idle_wall_stats(MphCtx* c, long long out[2])
 
 int mph_lean_step_stats(MphCtx* c, long long out[2])
 {
-    if (!out) return MPH_ERR_ARG;
-    MPH_CK(ctx_enter(c));
-    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
-    unsigned long long steps[2] = {0, 0};   // lean_search_steps, lean_pass_a_steps
-    static_assert(offsetof(DevState, lean_pass_a_steps) == offsetof(DevState, lean_search_steps) + sizeof(steps[0]),
+    static_assert(offsetof(DevState, lean_pass_a_steps) == offsetof(DevState, lean_search_steps) + sizeof(long long),
                   "the two counters are read in one copy");
-    MPH_HIP_OK(c, hipMemcpy(steps, reinterpret_cast<const char*>(c->L.st) + offsetof(DevState, lean_search_steps),
-                            sizeof(steps), hipMemcpyDeviceToHost));
-    out[0] = (long long)steps[0];
-    out[1] = (long long)steps[1];
-    return MPH_OK;
+    return counter_pair(c, offsetof(DevState, lean_search_steps), out);
 }
 
 int mph_key_fold_stats(MphCtx* c, long long out[2])
 {
-    if (!out) return MPH_ERR_ARG;
-    MPH_CK(ctx_enter(c));
-    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
-    unsigned long long steps[2] = {0, 0};   // key_fold_steps, prep_steps
-    static_assert(offsetof(DevState, prep_steps) == offsetof(DevState, key_fold_steps) + sizeof(steps[0]),
+    static_assert(offsetof(DevState, prep_steps) == offsetof(DevState, key_fold_steps) + sizeof(long long),
                   "the two counters are read in one copy");
-    MPH_HIP_OK(c, hipMemcpy(steps, reinterpret_cast<const char*>(c->L.st) + offsetof(DevState, key_fold_steps),
-                            sizeof(steps), hipMemcpyDeviceToHost));
-    out[0] = (long long)steps[0];
-    out[1] = (long long)steps[1];
-    return MPH_OK;
+    return counter_pair(c, offsetof(DevState, key_fold_steps), out);
 }
 
 int mph_neighbor_rows(MphCtx* c, int first, int count, int* counts, int* ids, long long ids_cap)

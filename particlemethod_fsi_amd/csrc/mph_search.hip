@@ -683,26 +683,22 @@ void launch_neighbors(const Launch& L)
 {
     const DevParams& P = *L.P;
     if (P.n == 0) return;
-    const int bal = P.n >= L.xcd_bal_min;
-    const bool lazy = L.form.lazy;
     // a lean step's search (lean_search_ok is asked again here for a caller that changed rlf after
     // the context was filled, as virial_full_lists does)
-    const bool lean = L.form.lean_search && lean_search_ok(P);
+    const bool lean = L.form.lazy && L.form.lean_search && lean_search_ok(P);
     by_dim(P.dim, [&](auto D) {
         constexpr int DIM = decltype(D)::value;
         auto go = [&](auto PERM) {
-            if (lean)
-                launch(L.prof, "neighbors", L.stream, k_neighbors<DIM, decltype(PERM)::value, true, true>,
-                       dim3(bal ? list_grid(P.n, true) : blocks(P.n, MPH_LB)), dim3(MPH_LB), P, L.A, L.start, L.nbr,
-                       L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, bal, L.cmap);
-            else if (lazy)
-                launch(L.prof, "neighbors", L.stream, k_neighbors<DIM, decltype(PERM)::value, true>,
-                       dim3(bal ? list_grid(P.n, true) : blocks(P.n, MPH_LB)), dim3(MPH_LB), P, L.A, L.start, L.nbr,
-                       L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, bal, L.cmap);
-            else
-                launch(L.prof, "neighbors", L.stream, k_neighbors<DIM, decltype(PERM)::value, false>,
-                       dim3(blocks(P.n, MPH_LB)), dim3(MPH_LB), P, L.A, L.start, L.nbr, L.ncount, L.nbcount, L.lhdr,
-                       L.lgap, L.st, L.wface, bal, nullptr);
+            by_flag(L.form.lazy, [&](auto LAZY) {
+                by_flag(lean, [&](auto LEAN) {
+                    if constexpr (decltype(LAZY)::value || !decltype(LEAN)::value)   // (only a lazy step is lean)
+                        launch(L.prof, "neighbors", L.stream,
+                               k_neighbors<DIM, decltype(PERM)::value, decltype(LAZY)::value, decltype(LEAN)::value>,
+                               dim3(lazy_bal(L) ? list_grid(P.n, true) : blocks(P.n, MPH_LB)), dim3(MPH_LB), P, L.A,
+                               L.start, L.nbr, L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, (int)xcd_bal(L),
+                               lazy_cmap(L));
+                });
+            });
         };
         if constexpr (DIM == 3) {   // (the 2-D grid has the one cell order)
             switch (P.perm) {

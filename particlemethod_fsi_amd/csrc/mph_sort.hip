@@ -81,39 +81,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
     bool mig = false;
     const int b = p < n ? vsrc_entry(vs, C, p, B, mig) : p;
     {
-        // The particles arrive in the previous cell order, so consecutive lanes often share a
-        // cell: one histogram atomic per run of equal keys (slot = run base + rank in the run).
-        // Every lane of the wave takes part in the shuffles; lanes past n form runs of their own.
+        // the lanes past n stay for the run detection (prep_slot), with keys of their own
         const bool live = p < n;
-        int k = -1 - (int)(threadIdx.x & 63);
+        const int lane = threadIdx.x & 63;
+        int k = -1 - lane;
         int occ = 0;
         if (live) {
             double x = B.x[b], y = B.y[b], z = B.z[b];
             if (mode == 1) move_and_wrap(P, st, B, b, x, y, z);
-            if (!isfinite(x + y + z)) atomicOr(const_cast<int*>(&st->overflow), 4);   // MPH_ERR_NONFINITE
-            const int cx = cell_axis(x, P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
-            const int cy = cell_axis(y, P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
-            const int cz = P.dim == 3 ? cell_axis(z, P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
-            k = cell_index(P, cx, cy, cz);   // (cell_id)
-            key[p] = k;
-            // a lazy wall step (cmap set): a non-wall particle marks its coarse cell -- a plain store
-            // of the same byte by every marker, no atomic (the search reads the map, pass A clears it)
-            if (cmap && !dev_is_wall(B.type[b]))
-                cmap[coarse_index(P, cx >> kCoarseShift, cy >> kCoarseShift, cz >> kCoarseShift)] = 1;
-            occ = seam_bits(P, x, y, z);
+            // (the type is loaded only with the map set)
+            k = prep_cell(P, st, x, y, z, &key[p], cmap, [&] { return !dev_is_wall(B.type[b]); }, occ);
         }
-        const int lane = threadIdx.x & 63;
-        const int kprev = __shfl_up(k, 1, 64);
-        const bool head = lane == 0 || kprev != k;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
-        const int hl = 63 - __clzll(heads & upto);
-        const unsigned long long above = heads & ~upto;
-        const int next = above ? __ffsll((long long)above) - 1 : 64;
-        int base = 0;
-        if (live && head) base = atomicAdd(&cnt[k], next - lane);
-        base = __shfl(base, hl, 64);
-        if (live) slot[p] = base + (lane - hl);
+        const int s = prep_slot(k, live, cnt);
+        if (live) slot[p] = s;
         // the block's face bits: OR-ed in LDS, then one device atomic per block, only for bits the
         // step's word does not hold yet (few blocks: the particles near a periodic face)
         __shared__ int s_occ;
@@ -372,13 +352,13 @@ void launch_sort(const Launch& L, int mode)
     const int n = P.n;
     if (n == 0) return;
     // the passes' XCD split (list_grid, k_rank_scatter): 0 none, 1 a full step's, 2 a lazy step's
-    const int split = n >= L.xcd_bal_min ? (L.form.lazy ? 2 : 1) : 0;
+    const int split = lazy_bal(L) ? 2 : xcd_bal(L);
     const dim3 g(blocks(n, 256)), b(256);
-    // keys_done (step_keys): the previous step's pass B has done k_prep's work
+    // keys_done (seq_step): the previous step's pass B has done k_prep's work
     const bool prep = !(mode == 1 && L.form.keys_done);
     if (prep)
         launch(L.prof, "prep", L.stream, k_prep, g, b, P, L.st, L.B, L.key, L.slot, L.cnt, mode, L.vsrc,
-               L.form.lazy ? L.cmap : nullptr);
+               lazy_cmap(L));
     launch_scan(L.cnt, P.ncell, L.bsum, L.start, n, P.n_dev, L.stream, L.prof);
     launch(L.prof, "place", L.stream, k_place, g, b, P, L.st, L.key, L.slot, L.start, L.tmp, mode,
            (int)(prep && mode == 1));

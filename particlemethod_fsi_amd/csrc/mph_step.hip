@@ -1,4 +1,4 @@
-// mph_step.hip -- the step sequencer of a single context: one step's launches (enqueue_step), the
+// mph_step.hip -- the step sequencer of a single context: a sequence's launches (enqueue_steps), the
 // captured step graphs and their replay, step batching, mph_step, phase timing.
 #include <hip/hip_runtime.h>
 
@@ -10,7 +10,7 @@ using namespace mph;
 
 namespace mph {
 
-// One step: its Launch (step_launch: the outputs it stores and its form, decided there and nowhere
+// One step: its Launch (seq_step: the outputs it stores and its form, decided there and nowhere
 // else) goes to the sort, the search and the two passes.  The elastic substeps and the monitors take
 // the context's own: the last substep zeroes the Force of the clamped slots on every step
 // (k_struct_velocity), and neither reads a trimmed field or the form otherwise.  The virial
@@ -18,12 +18,9 @@ namespace mph {
 // ev (phase timing, else null): three events recorded on the stream at the step's phase
 // boundaries -- before the sort, after the search (neighbour search = sort + search, as the
 // reference's calculateNeighbor holds its own cell sort), after the elastic substeps.
-// k, steps, next_last: the step's place in the sequence it is enqueued with (a graph, a phase-timed or
-// profiled batch) and whether the step after it is a last one, for the key fold (step_keys).
-void enqueue_step(const Launch& L, bool last, hipEvent_t* ev, int k, int steps, bool next_last)
+static void enqueue_step(const Launch& L, const Launch& S, hipEvent_t* ev)
 {
     if (ev) (void)hipEventRecord(ev[0], L.stream);
-    const Launch S = step_keys(step_launch(L, last), L, k, steps, next_last);
     launch_sort(S, 1);
     if (ev) {   // phase timing: the boundary between the search and pass A
         launch_neighbors(S);
@@ -33,30 +30,28 @@ void enqueue_step(const Launch& L, bool last, hipEvent_t* ev, int k, int steps, 
         launch_search_pass_a(S);
     }
     launch_pass_b(S);
-    launch_structure(L, last);
+    launch_structure(L, stores_outputs(S));
     if (ev) (void)hipEventRecord(ev[2], L.stream);
     if (L.mon) launch_monitor(L, *L.mon);   // monitors on: this step's sample (mph_monitor.hip)
 }
 
-// store_last = false: no step of the graph stores the output-only fields (graph1t, the steps of a
-// remainder before its last one; graph8t, the whole batches of a call before its last one)
-static int capture(MphCtx* c, int steps, hipGraphExec_t* out, bool store_last = true)
+void enqueue_steps(const Launch& L, StepSeq seq, hipEvent_t* ev)
 {
-    return ctx_capture(c, steps, out, [&](int k) {
-        enqueue_step(c->L, store_last && k == steps - 1, nullptr, k, steps, store_last && k + 1 == steps - 1);
-        return MPH_OK;
-    });
+    for (int k = 0; k < seq.steps; ++k) enqueue_step(L, seq_step(L, seq, k), ev ? ev + 3 * k : nullptr);
 }
 
 // The step graphs, captured at the first mph_step whatever its count: a caller that warms up with
 // fewer than 8 steps (the driver's bench: 5) would otherwise capture and upload the 8-step graph
-// inside its first long run.
+// inside its first long run.  kSeq8t only where the context takes the lean batches.
 static int capture_graphs(MphCtx* c)
 {
-    if (!c->graph1) MPH_CK(capture(c, 1, &c->graph1));
-    if (!c->graph1t) MPH_CK(capture(c, 1, &c->graph1t, false));
-    if (!c->graph8) MPH_CK(capture(c, 8, &c->graph8));
-    if (c->lean_calls && !c->graph8t) MPH_CK(capture(c, 8, &c->graph8t, false));
+    for (int kind = 0; kind < kSeqKinds; ++kind) {
+        if (c->graph[kind] || (kind == kSeq8t && !c->lean_calls)) continue;
+        MPH_CK(ctx_capture(c, &c->graph[kind], [&] {
+            enqueue_steps(c->L, kSeqs[kind]);
+            return MPH_OK;
+        }));
+    }
     return MPH_OK;
 }
 
@@ -144,14 +139,11 @@ int mph_step(MphCtx* c, int nsteps)
         // launches with the phase events (HIP cannot time events recorded inside a captured graph),
         // read after every batch
         const ReplayPlan p = replay_plan(nsteps, c->lean_calls, true);
-        const int batches[4][3] = {{p.batch8t, 8, 0}, {p.batch8, 8, 1}, {p.single1t, 1, 0}, {p.single1, 1, 1}};
-        for (const auto& [count, b, store_last] : batches)
-            for (int r = 0; r < count; ++r) {
-                for (int k = 0; k < b; ++k)
-                    enqueue_step(c->L, store_last && k == b - 1, c->ev8.data() + 3 * k, k, b,
-                                 store_last && k + 1 == b - 1);
+        for (int kind = 0; kind < kSeqKinds; ++kind)
+            for (int r = 0; r < p.count[kind]; ++r) {
+                enqueue_steps(c->L, kSeqs[kind], c->ev8.data());
                 MPH_HIP_OK(c, hipGetLastError());
-                MPH_CK(accumulate_phases(c, c->ev8, b));
+                MPH_CK(accumulate_phases(c, c->ev8, kSeqs[kind].steps));
             }
     } else {
         MPH_CK(capture_graphs(c));

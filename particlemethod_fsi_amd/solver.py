@@ -645,35 +645,33 @@ class MphSolver:
         keys = ["waves", "waves_jumped", "jumps", "max_jumps", "gap_rows", "max_rows"]
         return {k: int(v) for k, v in zip(keys, a)}
 
+    def _counter_pair(self, entry: str, keys) -> dict:
+        """Two step counters of the device state through `entry`; zeros from a library built before it."""
+        a = np.zeros(2, np.int64)
+        if hasattr(self._L, entry):
+            _check(getattr(self._L, entry)(self._h, a.ctypes.data), self._h)
+        return {k: int(v) for k, v in zip(keys, a)}
+
     def idle_wall_stats(self) -> dict:
         """Lazy wall steps since the creation (mph_idle_wall_stats): the wall waves the search skipped
         ("idle_wave_steps") over the steps that store no output-only field ("lazy_steps"); both 0
         in slab mode, with monitors, with MPH_LAZY_WALLS=0 at creation, or from a library built
         before the entry point."""
-        a = np.zeros(2, np.int64)
-        if hasattr(self._L, "mph_idle_wall_stats"):
-            _check(self._L.mph_idle_wall_stats(self._h, a.ctypes.data), self._h)
-        return {"idle_wave_steps": int(a[0]), "lazy_steps": int(a[1])}
+        return self._counter_pair("mph_idle_wall_stats", ("idle_wave_steps", "lazy_steps"))
 
     def lean_step_stats(self) -> dict:
         """Lean steps since the creation (mph_lean_step_stats): the lazy steps whose search ran its
         lean form ("search_steps") and those whose pass A did ("pass_a_steps"); both 0 wherever no
         step is lazy, with MPH_LEAN_STEPS=0 at creation, or from a library built before the entry
         point."""
-        a = np.zeros(2, np.int64)
-        if hasattr(self._L, "mph_lean_step_stats"):
-            _check(self._L.mph_lean_step_stats(self._h, a.ctypes.data), self._h)
-        return {"search_steps": int(a[0]), "pass_a_steps": int(a[1])}
+        return self._counter_pair("mph_lean_step_stats", ("search_steps", "pass_a_steps"))
 
     def key_fold_stats(self) -> dict:
         """The key fold since the creation (mph_key_fold_stats): the steps whose pass B left the next
         step's cell keys ("folded_steps") and the steps that opened with a k_prep launch
         ("prep_launches"); the first 0 with structure particles, monitors, in slab mode or with
         MPH_KEY_FOLD=0 at creation, both 0 from a library built before the entry point."""
-        a = np.zeros(2, dtype=np.int64)
-        if hasattr(self._L, "mph_key_fold_stats"):
-            _check(self._L.mph_key_fold_stats(self._h, a.ctypes.data), self._h)
-        return {"folded_steps": int(a[0]), "prep_launches": int(a[1])}
+        return self._counter_pair("mph_key_fold_stats", ("folded_steps", "prep_launches"))
 
     def neighbor_rows(self, first: int = 0, count: int | None = None):
         """(counts, offsets, ids): the neighbour sets of the particles [first, first + count) from

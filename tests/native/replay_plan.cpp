@@ -1,6 +1,6 @@
 // replay_plan.cpp -- how a call's steps are cut into batches (csrc/mph_kernels.h replay_plan; DESIGN.md
 // section 3.1) for n = 1 ... 80 with and without the all-lean 8-step graph and the lean single step,
-// and the key fold's two fields of a step's form (step_keys; section 3.2) over every combination of
+// and the key fold's two fields of a step's form (seq_step; section 3.2) over every combination of
 // the step's place in its sequence, structures, monitors, a slab's set and the toggle.  The rules are
 // written out below as this program's own and never taken from the code under test.  Built and run
 // by tests/test_replay_plan.py with the host compiler; needs no GPU.
@@ -29,12 +29,18 @@ void expect(bool ok, const char* what, int a, int b, int c)
 std::vector<int> steps_of(const ReplayPlan& p)
 {
     std::vector<int> s;
-    for (int k = 0; k < p.batch8t; ++k) s.insert(s.end(), {0, 0, 0, 0, 0, 0, 0, 0});
-    for (int k = 0; k < p.batch8; ++k) s.insert(s.end(), {0, 0, 0, 0, 0, 0, 0, 1});
-    for (int k = 0; k < p.single1t; ++k) s.push_back(0);
-    for (int k = 0; k < p.single1; ++k) s.push_back(1);
+    for (int k = 0; k < p.count[kSeq8t]; ++k) s.insert(s.end(), {0, 0, 0, 0, 0, 0, 0, 0});
+    for (int k = 0; k < p.count[kSeq8]; ++k) s.insert(s.end(), {0, 0, 0, 0, 0, 0, 0, 1});
+    for (int k = 0; k < p.count[kSeq1t]; ++k) s.push_back(0);
+    for (int k = 0; k < p.count[kSeq1]; ++k) s.push_back(1);
     return s;
 }
+
+// the plan's four counts under the names of the rules below
+struct Counts {
+    int batch8t, batch8, single1t, single1;
+};
+Counts counts_of(const ReplayPlan& q) { return {q.count[kSeq8t], q.count[kSeq8], q.count[kSeq1t], q.count[kSeq1]}; }
 
 // The rules.  The sequence before the lean batches: graph8 while 8 or more steps are left, then
 // single steps -- all but the last without the stores where the context has the lean single step.
@@ -49,8 +55,9 @@ std::vector<int> before(int n, bool lean1)
 
 void check_plan(int n, bool lean8, bool lean1)
 {
-    const ReplayPlan p = replay_plan(n, lean8, lean1);
-    const std::vector<int> s = steps_of(p);
+    const ReplayPlan plan = replay_plan(n, lean8, lean1);
+    const Counts p = counts_of(plan);
+    const std::vector<int> s = steps_of(plan);
     expect((int)s.size() == n, "the step total", n, lean8, lean1);
     expect(!s.empty() && s.back() == 1, "the call's last step stores", n, lean8, lean1);
     expect(p.batch8t >= 0 && p.batch8 >= 0 && p.single1t >= 0 && p.single1 >= 0, "a negative count", n, lean8, lean1);
@@ -92,8 +99,10 @@ void check_fold(int bits)
     MonitorDev mon;
     int idx = 0;
     unsigned char map = 0;
+    double4 force;
     Launch L;
     L.P = &P;
+    L.force = &force;
     L.key_fold = c.toggle;
     L.mon = c.monitors ? &mon : nullptr;
     L.vsrc.idx = c.slab ? &idx : nullptr;
@@ -108,8 +117,7 @@ void check_fold(int bits)
         bool prev_next = false;   // keys_next of the step before; false before a sequence's first
         for (int k = 0; k < steps; ++k) {
             const bool last = store_last && k == steps - 1, next_last = store_last && k + 1 == steps - 1;
-            const Launch base = step_launch(L, last);
-            const Launch S = step_keys(base, L, k, steps, next_last);
+            const Launch S = seq_step(L, StepSeq{steps, store_last}, k);
             expect(S.form.keys_done == prev_next, "keys_done of step k + 1 <=> keys_next of step k", bits, steps, k);
             expect(S.form.keys_next == (fold_on(c) && k + 1 < steps), "keys_next", bits, steps, k);
             expect(!(k == steps - 1 && S.form.keys_next), "keys_next across a sequence's end", bits, steps, k);
@@ -120,10 +128,12 @@ void check_fold(int bits)
             const bool next_lazy = S.form.keys_next && !next_last && c.lazy_walls && !c.monitors;
             expect(S.cmap_next == (next_lazy ? &map : nullptr), "cmap_next", bits, steps, k);
             // nothing else of the step's Launch changes
-            expect(S.form.lazy == base.form.lazy && S.form.lean_search == base.form.lean_search &&
-                       S.form.lean_pass_a == base.form.lean_pass_a && S.force == base.force && S.cmap == base.cmap &&
-                       S.P == base.P && S.mon == base.mon,
-                   "step_keys changed another field", bits, steps, k);
+            // the rest of the step's Launch is what the step alone would have: lazy unless it stores (the
+            // map allocated, no monitors), never lean here (L.lean_ok is off), Force on the storing step
+            expect(S.form.lazy == (!last && c.lazy_walls && !c.monitors) && !S.form.lean_search &&
+                       !S.form.lean_pass_a && S.force == (last ? &force : nullptr) && S.cmap == L.cmap && S.P == L.P &&
+                       S.mon == L.mon,
+                   "the fold changed another field", bits, steps, k);
             prev_next = S.form.keys_next;
         }
     }
@@ -136,12 +146,18 @@ int main()
     for (int n = 1; n <= 80; ++n)
         for (int g = 0; g < 4; ++g) check_plan(n, (g & 1) != 0, (g & 2) != 0);
     // the calls the GPU tests pin
-    const ReplayPlan p40 = replay_plan(40, true, true), p16 = replay_plan(16, true, true), p13 = replay_plan(13, true, true);
+    const Counts p40 = counts_of(replay_plan(40, true, true)), p16 = counts_of(replay_plan(16, true, true)),
+                 p13 = counts_of(replay_plan(13, true, true));
     expect(p40.batch8t == 4 && p40.batch8 == 1 && p40.single1t == 0 && p40.single1 == 0, "mph_step(40)", 40, 0, 0);
     expect(p16.batch8t == 1 && p16.batch8 == 1 && p16.single1t == 0 && p16.single1 == 0, "mph_step(16)", 16, 0, 0);
     expect(p13.batch8t == 0 && p13.batch8 == 1 && p13.single1t == 4 && p13.single1 == 1, "mph_step(13)", 13, 0, 0);
-    const ReplayPlan z = replay_plan(0, true, true);
+    const Counts z = counts_of(replay_plan(0, true, true));
     expect(z.batch8t + z.batch8 + z.single1t + z.single1 == 0, "no step, no launch", 0, 0, 0);
+    // the four kinds are the sequences steps_of writes out, in the plan's launch order
+    const int kinds[4][2] = {{8, 0}, {8, 1}, {1, 0}, {1, 1}};
+    for (int kind = 0; kind < 4; ++kind)
+        expect(kSeqKinds == 4 && kSeqs[kind].steps == kinds[kind][0] && kSeqs[kind].store_last == (kinds[kind][1] != 0),
+               "the four kinds", kind, 0, 0);
     for (int bits = 0; bits < 32; ++bits) check_fold(bits);
     if (failures) return 1;
     std::printf("replay_plan ok\n");

@@ -1,5 +1,5 @@
-// step_form.cpp -- a step's form and the outputs it stores (csrc/mph_kernels.h step_launch,
-// trim_outputs) over all 64 combinations of: the batch's last step or not,
+// step_form.cpp -- a step's form and the outputs it stores (csrc/mph_kernels.h seq_step,
+// trim_outputs) over all 64 combinations of: a sequence's storing last step or not,
 // surface tension, the coarse map allocated, monitors on, MPH_LEAN_STEPS, the context's lean-search
 // capability.  The rules are written out below as this program's own table and never taken from the
 // code under test.  Built and run by tests/test_step_form.py with the host compiler; needs no GPU.
@@ -115,7 +115,8 @@ int main()
         const Launch L = context_launch(c, &P, &mon);
         expect(!L.form.lazy && !L.form.lean_search && !L.form.lean_pass_a, bits, "the context's own form is all false");
 
-        const Launch S = step_launch(L, c.last);
+        // a sequence of one step, storing or not: the step alone, with nothing to fold
+        const Launch S = seq_step(L, StepSeq{1, c.last}, 0);
         expect(S.form.lazy == want_lazy(c), bits, "form.lazy");
         expect(S.form.lean_search == want_lean_search(c), bits, "form.lean_search");
         expect(S.form.lean_pass_a == want_lean_pass_a(c), bits, "form.lean_pass_a");
@@ -124,6 +125,10 @@ int main()
             expect(t.want_null(c) ? got == nullptr : (got != nullptr && got == t.get(L)), bits, t.name);
         }
         expect(untrimmed_same(S, L), bits, "an untrimmed field changed");
+        expect(!S.form.keys_done && !S.form.keys_next && !S.cmap_next, bits, "a single step folds nothing");
+        // what the launchers read: the map on a lazy step alone, a stored Force on a storing step alone
+        expect(lazy_cmap(S) == (want_lazy(c) ? L.cmap : nullptr), bits, "lazy_cmap");
+        expect(stores_outputs(S) == c.last, bits, "stores_outputs");
         lazy += S.form.lazy;
         lean_s += S.form.lean_search;
         lean_a += S.form.lean_pass_a;

@@ -194,6 +194,79 @@ CHUNK_FIELDS = ["Position", "Velocity", "Force", "Acceleration", "GravityCenter"
                 "PressureA", "DensityA", "VolStrainP", "DivergenceP", "NeighborCount", "Kappa",
                 "DeformGradient", "Strain", "Stress"]
 
+# ---- the step variants' bitwise comparisons (test_gpu_idle_walls, _lean_steps, _step_paths,
+# _call_batches): what a caller can read after a step, compared bit for bit between two ways to run it
+VIRIAL = ["VirialStressAtParticle", "VirialPressureAtParticle"]
+
+
+def snapshot(s):
+    """CHUNK_FIELDS (NeighborCount is one of them) and both virial fields of the solver's state."""
+    out = {f: s.get(f) for f in CHUNK_FIELDS}
+    s.compute_virial()
+    out.update({f: s.get(f) for f in VIRIAL})
+    return out
+
+
+def assert_same(a, b, context):
+    """Two snapshots, or two dicts {steps done: snapshot}, hold the same fields with the same bits."""
+    assert sorted(a) == sorted(b), (context, sorted(a), sorted(b))
+    for k in a:
+        if isinstance(a[k], dict):
+            assert_same(a[k], b[k], (context, k))
+        else:
+            assert np.array_equal(a[k], b[k], equal_nan=True), (context, k)
+
+
+def step_counters(s):
+    """The five step counters since the creation: lazy steps, lean searches, lean pass A's, steps whose
+    pass B left the next one's keys, k_prep launches."""
+    lean, fold = s.lean_step_stats(), s.key_fold_stats()
+    return {"lazy": s.idle_wall_stats()["lazy_steps"], "lean_search": lean["search_steps"],
+            "lean_pass_a": lean["pass_a_steps"], "folded": fold["folded_steps"], "prep": fold["prep_launches"]}
+
+
+def run_calls(cfg, parts, calls, snap_at=(), monitors=0):
+    """One context stepped by mph_step(k) for k in `calls`, with a monitor ring of `monitors` samples
+    where that is not 0: ({steps done: snapshot} at the step counts of `snap_at`, step_counters after
+    every call, the idle wall waves counted after every call, the monitor samples or None)."""
+    from particlemethod_fsi_amd import MphSolver
+    snaps, counters, idle = {}, [], []
+    with MphSolver(cfg, parts) as s:
+        if monitors:
+            s.monitor(stride=1, capacity=monitors)
+        done = 0
+        for k in calls:
+            s.step(k)
+            done += k
+            counters.append(step_counters(s))
+            idle.append(s.idle_wall_stats()["idle_wave_steps"])
+            if done in snap_at:
+                snaps[done] = snapshot(s)
+        samples = s.monitor_read()[0] if monitors else None
+    return snaps, counters, idle, samples
+
+
+def tank():
+    """A 3-D dam tank of 30 x 30 x 16 dx with three-layer walls on the floor, on both x sides and on both
+    z sides, and a fluid block of 10 x 12 x 10 dx in the corner x = z = 0 -- 12,000 particles, 10,800 of
+    them walls -- the outer half of the block (x > 5 dx) started at 0.8 m/s along +x
+    (test_gpu_idle_walls.py has the reasons)."""
+    from particlemethod_fsi_amd import cases
+    from particlemethod_fsi_amd.mphio import Cuboid
+    dx = 0.001
+    c = cases.Case("idle_tank", 3, "dam", dx, (-0.01, 0.0, -0.01), (0.045, 0.055, 0.03), [
+        Cuboid(1, (0.0, 0.003, 0.0), (0.010, 0.015, 0.010), dx),
+        Cuboid(4, (0.0, 0.0, 0.0), (0.030, 0.003, 0.016), dx),
+        Cuboid(4, (0.030, 0.0, 0.0), (0.033, 0.030, 0.016), dx),
+        Cuboid(4, (-0.003, 0.0, 0.0), (0.0, 0.030, 0.016), dx),
+        Cuboid(4, (-0.003, 0.0, -0.003), (0.033, 0.030, 0.0), dx),
+        Cuboid(4, (-0.003, 0.0, 0.016), (0.033, 0.030, 0.019), dx),
+    ])
+    cfg, parts = c.build()
+    assert parts.n == 12000
+    parts.velocity[(parts.property < 2) & (parts.position[:, 0] > 0.005)] = (0.8, 0.0, 0.0)
+    return cfg, parts
+
 
 def check_structure_init_equals_host_build(case, monkeypatch):
     """The structure lists built on the device against the host build: see

@@ -1,14 +1,14 @@
 """Lean batches up to a call's last (csrc/mph_kernels.h replay_plan): a call can
 only be observed after it returns, so of the whole 8-step batches of one mph_step(n) only the last
 ends in a step that stores the output-only fields; the batches before it come from an 8-step graph
-whose steps are all lazy (graph8t).  And the key fold (step_keys): inside a
+whose steps are all lazy (kSeq8t).  And the key fold (seq_step): inside a
 graph, pass B moves and wraps the particles and leaves the next step's cell keys, slots and
 histogram, so only the graph's first step launches k_prep.  Nothing a caller can read may change:
 every comparison here is bitwise, mph_step(n) in one call against n x mph_step(1), over
 parity.CHUNK_FIELDS and both virial fields.
 
-n = 16 is graph8t + graph8 (15 lazy steps), n = 29 is 2 x graph8t + graph8 + 4 x graph1t + graph1
-(23 + 4), n = 40 is 4 x graph8t + graph8 (39).  The cases: the 12,000-particle tank of
+n = 16 is kSeq8t + kSeq8 (15 lazy steps), n = 29 is 2 x kSeq8t + kSeq8 + 4 x kSeq1t + kSeq1
+(23 + 4), n = 40 is 4 x kSeq8t + kSeq8 (39).  The cases: the 12,000-particle tank of
 test_gpu_idle_walls.py (a partial last wave, idle walls, a moving fluid block), also under the
 work-balanced XCD map; box3d_jit (off the lattice: the shell pairs the lean search leaves out);
 seam3d (periodic faces); movwall3d (rigid wall motion across Time 0.2); rolling3d; turek2d (the
@@ -16,38 +16,18 @@ inlet profile; its elastic plate keeps the fold off) and turek2d_fluid, the same
 in the plate's place, which takes the inlet profile through the fold; dam2d; box3d_st (surface
 tension: pass A never lean); gate3d (structures: fold off, plan on).
 """
-import numpy as np
 import pytest
 
-from parity import CHUNK_FIELDS
+from parity import assert_same, run_calls, snapshot, step_counters as counters, tank
 from particlemethod_fsi_amd import MphSolver, cases
 from particlemethod_fsi_amd.mphio import Cuboid
 
 pytestmark = pytest.mark.gpu
 
-VIRIAL = ["VirialStressAtParticle", "VirialPressureAtParticle"]
 CALLS = (16, 29, 40)
 CASES = ["tank", "box3d_jit", "seam3d", "movwall3d", "rolling3d", "turek2d", "turek2d_fluid", "dam2d", "box3d_st",
          "gate3d"]
 STRUCTURES = {"turek2d", "gate3d"}   # cases with structure particles: the fold stays off
-
-
-def tank():
-    """The tank of test_gpu_idle_walls.py: 12,000 particles, 10,800 of them walls, the outer half of
-    the fluid block started at 0.8 m/s along +x."""
-    dx = 0.001
-    c = cases.Case("idle_tank", 3, "dam", dx, (-0.01, 0.0, -0.01), (0.045, 0.055, 0.03), [
-        Cuboid(1, (0.0, 0.003, 0.0), (0.010, 0.015, 0.010), dx),
-        Cuboid(4, (0.0, 0.0, 0.0), (0.030, 0.003, 0.016), dx),
-        Cuboid(4, (0.030, 0.0, 0.0), (0.033, 0.030, 0.016), dx),
-        Cuboid(4, (-0.003, 0.0, 0.0), (0.0, 0.030, 0.016), dx),
-        Cuboid(4, (-0.003, 0.0, -0.003), (0.033, 0.030, 0.0), dx),
-        Cuboid(4, (-0.003, 0.0, 0.016), (0.033, 0.030, 0.019), dx),
-    ])
-    cfg, parts = c.build()
-    assert parts.n == 12000
-    parts.velocity[(parts.property < 2) & (parts.position[:, 0] > 0.005)] = (0.8, 0.0, 0.0)
-    return cfg, parts
 
 
 def turek_fluid():
@@ -58,34 +38,12 @@ def turek_fluid():
     return cases.Case("turek2d_fluid", 2, "turek_hron", t.spacing, t.lower, t.upper, cuboids).build()
 
 
-def snapshot(s):
-    out = {f: s.get(f) for f in CHUNK_FIELDS}
-    s.compute_virial()
-    out.update({f: s.get(f) for f in VIRIAL})
-    return out
-
-
-def counters(s):
-    lean = s.lean_step_stats()
-    fold = s.key_fold_stats()
-    return {"lazy": s.idle_wall_stats()["lazy_steps"], "lean_search": lean["search_steps"],
-            "lean_pass_a": lean["pass_a_steps"], "folded": fold["folded_steps"], "prep": fold["prep_launches"]}
-
-
 ZERO = {"lazy": 0, "lean_search": 0, "lean_pass_a": 0, "folded": 0}
 
 
 def one_call(cfg, parts, n, monitors=False):
-    with MphSolver(cfg, parts) as s:
-        if monitors:
-            s.monitor(stride=1, capacity=64)
-        s.step(n)
-        return snapshot(s), counters(s)
-
-
-def assert_same(a, b, context):
-    for f in a:
-        assert np.array_equal(a[f], b[f], equal_nan=True), (context, f)
+    snaps, c, _, _ = run_calls(cfg, parts, [n], {n}, 64 if monitors else 0)
+    return snaps[n], c[0]
 
 
 _built, _single = {}, {}

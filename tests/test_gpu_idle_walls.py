@@ -18,62 +18,19 @@ coarse cell of the map (3.5 dx), so whole waves of the floor ahead of the toe st
 import numpy as np
 import pytest
 
-from parity import CHUNK_FIELDS
-from particlemethod_fsi_amd import MphSolver, cases
-from particlemethod_fsi_amd.mphio import Cuboid
+from parity import assert_same, run_calls, tank
+from particlemethod_fsi_amd import cases
 
 pytestmark = pytest.mark.gpu
 
-VIRIAL = ["VirialStressAtParticle", "VirialPressureAtParticle"]
 STEPS = 64
 
 
-def tank():
-    dx = 0.001
-    c = cases.Case("idle_tank", 3, "dam", dx, (-0.01, 0.0, -0.01), (0.045, 0.055, 0.03), [
-        Cuboid(1, (0.0, 0.003, 0.0), (0.010, 0.015, 0.010), dx),
-        Cuboid(4, (0.0, 0.0, 0.0), (0.030, 0.003, 0.016), dx),
-        Cuboid(4, (0.030, 0.0, 0.0), (0.033, 0.030, 0.016), dx),
-        Cuboid(4, (-0.003, 0.0, 0.0), (0.0, 0.030, 0.016), dx),
-        Cuboid(4, (-0.003, 0.0, -0.003), (0.033, 0.030, 0.0), dx),
-        Cuboid(4, (-0.003, 0.0, 0.016), (0.033, 0.030, 0.019), dx),
-    ])
-    cfg, parts = c.build()
-    assert parts.n == 12000
-    parts.velocity[(parts.property < 2) & (parts.position[:, 0] > 0.005)] = (0.8, 0.0, 0.0)
-    return cfg, parts
-
-
-def snapshot(s):
-    out = {f: s.get(f) for f in CHUNK_FIELDS}
-    s.compute_virial()
-    out.update({f: s.get(f) for f in VIRIAL})
-    return out
-
-
 def run(cfg, parts, calls, snap_at, monitors=False):
-    """One context stepped by mph_step(k) for k in `calls`: {steps done: snapshot} at the step
-    counts of `snap_at`, the idle-wall counters after every call, the monitor samples."""
-    snaps, counters = {}, []
-    with MphSolver(cfg, parts) as s:
-        if monitors:
-            s.monitor(stride=1, capacity=256)
-        done = 0
-        for k in calls:
-            s.step(k)
-            done += k
-            counters.append(s.idle_wall_stats())
-            if done in snap_at:
-                snaps[done] = snapshot(s)
-        samples = s.monitor_read()[0] if monitors else None
-    return snaps, counters, samples
-
-
-def assert_same(a, b, context):
-    assert sorted(a) == sorted(b), (context, sorted(a), sorted(b))
-    for k in a:
-        for f in a[k]:
-            assert np.array_equal(a[k][f], b[k][f], equal_nan=True), (context, k, f)
+    """parity.run_calls as this file reads it: the snapshots, the idle-wall counters after every call
+    as mph_idle_wall_stats gives them, the monitor samples."""
+    snaps, counters, idle, samples = run_calls(cfg, parts, calls, snap_at, 256 if monitors else 0)
+    return snaps, [{"idle_wave_steps": i, "lazy_steps": c["lazy"]} for i, c in zip(idle, counters)], samples
 
 
 EVERY8 = set(range(8, STEPS + 1, 8))

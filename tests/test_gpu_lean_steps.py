@@ -9,48 +9,22 @@ shell MaxRadius < r <= MaxRadius + MARGIN (2.5 to 2.6 dx) holds pairs -- 9.6 % o
 2.6 dx, counted with a k-d tree on the case's positions (51.8 against 57.3 neighbours per
 particle); box3d, channel3d and seam3d have none.  test_shell_is_populated asserts it on the device.
 """
-import numpy as np
 import pytest
 
-from parity import CHUNK_FIELDS
+from parity import assert_same, run_calls
 from particlemethod_fsi_amd import MphSolver, cases
 
 pytestmark = pytest.mark.gpu
 
-VIRIAL = ["VirialStressAtParticle", "VirialPressureAtParticle"]
 ZERO = {"search_steps": 0, "pass_a_steps": 0}
 
 
-def snapshot(s):
-    out = {f: s.get(f) for f in CHUNK_FIELDS}   # (NeighborCount is one of them)
-    s.compute_virial()
-    out.update({f: s.get(f) for f in VIRIAL})
-    return out
-
-
 def run(cfg, parts, calls, snap_at, monitors=False):
-    """One context stepped by mph_step(k) for k in `calls`: {steps done: snapshot} at the step counts
-    of `snap_at`, and the lean and lazy counters after every call."""
-    snaps, lean, lazy = {}, [], []
-    with MphSolver(cfg, parts) as s:
-        if monitors:
-            s.monitor(stride=1, capacity=64)
-        done = 0
-        for k in calls:
-            s.step(k)
-            done += k
-            lean.append(s.lean_step_stats())
-            lazy.append(s.idle_wall_stats()["lazy_steps"])
-            if done in snap_at:
-                snaps[done] = snapshot(s)
-    return snaps, lean, lazy
-
-
-def assert_same(a, b, context):
-    assert sorted(a) == sorted(b), (context, sorted(a), sorted(b))
-    for k in a:
-        for f in a[k]:
-            assert np.array_equal(a[k][f], b[k][f], equal_nan=True), (context, k, f)
+    """parity.run_calls as this file reads it: the snapshots, and the lean counters (as
+    mph_lean_step_stats gives them) and the lazy steps after every call."""
+    snaps, counters, _, _ = run_calls(cfg, parts, calls, snap_at, 64 if monitors else 0)
+    lean = [{"search_steps": c["lean_search"], "pass_a_steps": c["lean_pass_a"]} for c in counters]
+    return snaps, lean, [c["lazy"] for c in counters]
 
 
 @pytest.fixture(scope="module")

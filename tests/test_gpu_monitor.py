@@ -153,12 +153,12 @@ def _gate_monitor(s, parts):
 def test_batch_shapes_give_the_same_samples():
     cfg, parts = cases.get("gate3d_jit").build()
     out = []
-    with MphSolver(cfg, parts) as s:        # 29 single steps (graph1)
+    with MphSolver(cfg, parts) as s:        # 29 single steps (kSeq1)
         _gate_monitor(s, parts)
         for _ in range(29):
             s.step(1)
         out.append(s.monitor_read())
-    with MphSolver(cfg, parts) as s:        # graph8 x 3, graph1t x 4, graph1
+    with MphSolver(cfg, parts) as s:        # kSeq8 x 3, kSeq1t x 4, kSeq1
         _gate_monitor(s, parts)
         s.step(24)
         s.step(5)

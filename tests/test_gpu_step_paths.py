@@ -1,7 +1,7 @@
-"""The ways a step reaches the device (csrc/mph_step.hip enqueue_step): replayed
+"""The ways a step reaches the device (csrc/mph_step.hip enqueue_steps): replayed
 from the captured graphs, launched directly with the phase events (mph_phase_timing), launched directly
 under the per-kernel profiler (mph_profile_steps).  All of them take a step's form from the one
-function (mph_kernels.h step_launch), so nine steps give the same bits whichever way they run, with
+function (mph_kernels.h seq_step), so nine steps give the same bits whichever way they run, with
 lazy and lean steps among them -- the monitors, which the other direct-launch comparison
 (test_batch_shapes_give_the_same_samples) turns on, make every step full.
 
@@ -10,29 +10,14 @@ followed by one full step (mph_step(9), with or without phase timing); eight of 
 which stores the outputs on its last step only.  With surface tension (box3d_st) pass B reads
 GravityCenter and PressureA on every step, so pass A is never lean.
 """
-import numpy as np
 import pytest
 
-from parity import CHUNK_FIELDS
+from parity import assert_same, snapshot, step_counters
 from particlemethod_fsi_amd import MphSolver, cases
 
 pytestmark = pytest.mark.gpu
 
 STEPS = 9
-VIRIAL = ["VirialStressAtParticle", "VirialPressureAtParticle"]
-
-
-def snapshot(s):
-    out = {f: s.get(f) for f in CHUNK_FIELDS}
-    s.compute_virial()
-    out.update({f: s.get(f) for f in VIRIAL})
-    return out
-
-
-def assert_same(a, b, context):
-    assert sorted(a) == sorted(b), (context, sorted(a), sorted(b))
-    for f in a:
-        assert np.array_equal(a[f], b[f], equal_nan=True), (context, f)
 
 
 def single_steps(s):
@@ -56,8 +41,8 @@ def profiled(s):
 def run(cfg, parts, way):
     with MphSolver(cfg, parts) as s:
         way(s)
-        lean, lazy = s.lean_step_stats(), s.idle_wall_stats()["lazy_steps"]
-        return snapshot(s), (lean["search_steps"], lean["pass_a_steps"], lazy)
+        c = step_counters(s)
+        return snapshot(s), (c["lean_search"], c["lean_pass_a"], c["lazy"])
 
 
 # case -> [(way, (lean search steps, lean pass A steps, lazy steps))]; the first way is the reference

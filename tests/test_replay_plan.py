@@ -1,4 +1,4 @@
-"""A call's batches and the key fold's form (csrc/mph_kernels.h replay_plan, step_keys; DESIGN.md
+"""A call's batches and the key fold's form (csrc/mph_kernels.h replay_plan, seq_step; DESIGN.md
 sections 3.1 and 3.2), CPU only: a stand-alone program (tests/native/replay_plan.cpp) walks the plan
 for n = 1 ... 80 with and without the all-lean 8-step graph and the lean single step -- the step
 total, which steps store the output-only fields, the count of lean batches, the sequence below 16

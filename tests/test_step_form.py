@@ -1,4 +1,4 @@
-"""A step's form (csrc/mph_kernels.h step_launch, trim_outputs), CPU only: a
+"""A step's form (csrc/mph_kernels.h seq_step, trim_outputs), CPU only: a
 stand-alone program (tests/native/step_form.cpp) walks the 64 combinations of last step, surface
 tension, coarse map, monitors, MPH_LEAN_STEPS and the lean-search capability and checks the three
 fields of the form, the nullness of the nine trimmed outputs and that every other field of the Launch

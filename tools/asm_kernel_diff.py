@@ -2,7 +2,8 @@
 r"""Per-kernel comparison of two sets of gfx950 assembly listings (hipcc --cuda-device-only -S):
 did moving code between translation units change any kernel?
 
-    asm_kernel_diff.py --old OLD.s [OLD.s ...] --new NEW.s [NEW.s ...] [--show] [--rename RE REPL ...]
+    asm_kernel_diff.py --old OLD.s [OLD.s ...] --new NEW.s [NEW.s ...] [--show] [--opcodes]
+                       [--rename RE REPL ...]
 
 Each listing is split at its kernel symbols (the .amdhsa_kernel names).  A kernel is its instruction
 stream (from its label to .Lfunc_end) and its descriptor (.amdhsa_* lines, and the .set lines the
@@ -13,9 +14,12 @@ masked.  Prints SAME or DIFF per kernel, and ONLY-OLD / ONLY-NEW for a kernel of
 unless every kernel is SAME.  --show adds a unified diff of every DIFF.  --rename RE REPL (repeatable)
 rewrites the new listings' text with re.sub before they are split, for a template that gained a
 parameter: `--rename 'k_pass_aILi(\d)ELb0EE' 'k_pass_aILi\1EE'` gives k_pass_a<D, false> the name
-k_pass_a<D> had.  CPU only.
+k_pass_a<D> had.  --opcodes splits the DIFFs: a kernel whose descriptor is identical and whose
+instruction streams hold the same mnemonics the same number of times (the compiler ordered them or
+named their registers differently) is REORDER, which does not fail the run.  CPU only.
 """
 import argparse
+import collections
 import difflib
 import re
 import sys
@@ -80,11 +84,18 @@ def figures(desc):
                                                   d.get("private_seg_size", "?"))
 
 
+def opcodes(body):
+    """the multiset of a stream's instruction mnemonics (labels and directives left out)"""
+    return collections.Counter(l.split()[0] for l in body if not l.endswith(":") and not l.startswith("."))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
     ap.add_argument("--show", action="store_true", help="print a unified diff of every DIFF")
+    ap.add_argument("--opcodes", action="store_true",
+                    help="report a DIFF with an identical descriptor and mnemonic multiset as REORDER (passes)")
     ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("RE", "REPL"),
                     help="re.sub applied to the new listings' text")
     a = ap.parse_args()
@@ -98,20 +109,22 @@ def main():
         side.append(ks)
     old, new = side
     bad = 0
-    count = {"SAME": 0, "DIFF": 0, "ONLY-OLD": 0, "ONLY-NEW": 0}
+    count = {"SAME": 0, "REORDER": 0, "DIFF": 0, "ONLY-OLD": 0, "ONLY-NEW": 0}
     for sym in sorted(set(old) | set(new)):
         if sym not in new or sym not in old:
             verdict = "ONLY-OLD" if sym in old else "ONLY-NEW"
             bad += 1
         elif old[sym] == new[sym]:
             verdict = "SAME"
+        elif a.opcodes and old[sym][1] == new[sym][1] and opcodes(old[sym][0]) == opcodes(new[sym][0]):
+            verdict = "REORDER"
         else:
             verdict = "DIFF"
             bad += 1
         count[verdict] += 1
         k = new.get(sym) or old[sym]
         print("%-8s %s  [%d lines, %s]" % (verdict, sym, len(k[0]), figures(k[1])))
-        if a.show and verdict == "DIFF":
+        if a.show and verdict in ("DIFF", "REORDER"):
             for part in (0, 1):
                 sys.stdout.writelines(l + "\n" for l in difflib.unified_diff(old[sym][part], new[sym][part],
                                                                              "old", "new", lineterm="", n=2))
