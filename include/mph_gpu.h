@@ -237,7 +237,7 @@ int mph_step(MphCtx* ctx, int nsteps);
  * Steps still pending run, and the error flags of everything launched are read, at the next
  * flush point: mph_synchronize, mph_get, mph_set, every writer, mph_compute_virial,
  * mph_neighbor_stats, mph_profile_steps, mph_phase_timing, mph_monitor_configure, mph_monitor_read,
- * mph_sample_grid, turning batching off, mph_destroy; so
+ * mph_sample_grid, mph_gauge_configure, mph_gauge_grid, turning batching off, mph_destroy; so
  * every field read after a step is that step's, bit for bit as without batching.  A launched
  * batch's error is also reported by a later mph_step once its flags have landed (no wait).
  * Errors therefore surface up to two batches late, or at the next flush point.  Off by default. */
@@ -357,7 +357,8 @@ typedef struct MphMonitorConfig {
  * next step.  MPH_ERR_ARG: stride or capacity < 1, a count over its maximum, a track index outside
  * [0, n), a probe radius below 0 or over the stencil's reach.  MPH_ERR_UNSUPPORTED: slab mode.   */
 int mph_monitor_configure(MphCtx* ctx, const MphMonitorConfig* cfg);
-/* Doubles per sample: MPH_MONITOR_HEAD + 6 ntrack + 2 nprobe; 0 with monitors off.              */
+/* Doubles per sample: MPH_MONITOR_HEAD + 6 ntrack + 2 nprobe (+ MPH_GAUGE_CHANNELS ngauge after
+ * mph_gauge_configure); 0 with monitors off.                                                    */
 int mph_monitor_sample_doubles(const MphCtx* ctx);
 /* Copy the unread samples, oldest first and at most max_samples, to out ([k][sample doubles]) and
  * return how many.  The ring keeps the newest `capacity` samples: *lost (may be NULL) receives how
@@ -416,6 +417,61 @@ int mph_sample_grid_timed(MphCtx* ctx, const MphSampleGrid* g, double* out, doub
  * and Spacing of *g, Float64 point arrays Count, WSum, PressureP and Velocity (3 components) in raw
  * appended data (UInt64 headers), the doubles as sampled.                                         */
 int mph_write_vti_arrays(const char* path, const MphSampleGrid* g, const double* out);
+
+/* ---- free-surface gauges ---------------------------------------------------------------------- */
+
+/* The water level H(t) at gauge stations, inside the per-step monitors, and as an elevation map on
+ * demand.  A gauge is a straight line parallel to coordinate axis `axis` through a point whose
+ * coordinate along that axis is ignored (2-D: its z too, and the axis is 0 or 1).  Its particles are
+ * the fluid particles (types 0, 1) of the last step's sorted set -- the wrapped positions before
+ * that step's motion, the ones PressureP was computed at, as for the probes -- whose distance r from
+ * the line is below the radius h: r the minimum-image distance over the dim - 1 other axes, from
+ * the gauge point wrapped into the periodic domain like a particle, r = sqrt(q0 q0 [+ q1 q1]) with
+ * the lower axis first, FP64, no contraction.  Per gauge MPH_GAUGE_CHANNELS doubles
+ * (MphGaugeChannel): COUNT of these particles; TOP, their largest coordinate along the axis (-inf
+ * with none; spray counts); BOTTOM, the smallest (+inf with none); WET, the number of distinct
+ * occupied bins along the axis (0 with none), a particle's bin being
+ *     min(max((int)floor((x - domain_min[axis]) / particle_spacing), 0), nbins - 1),
+ *     nbins = (int)ceil((domain_max[axis] - domain_min[axis]) / particle_spacing)
+ * (FP64, IEEE division): WET * particle_spacing is the wetted length a wire gauge reads, whatever
+ * droplets fly above the surface.  All four are order-independent, hence bit-exact functions of the
+ * state, the gauge and the radius: the same in any batch shape, beside any other gauges, from the
+ * monitors or from the map.  nbins must be <= MPH_GAUGE_MAX_BINS.                               */
+#define MPH_GAUGE_MAX            64
+#define MPH_GAUGE_CHANNELS       4
+#define MPH_GAUGE_MAX_BINS       8192
+#define MPH_GAUGE_GRID_MAX_LINES (1 << 20)
+typedef enum MphGaugeChannel { MPH_GAUGE_COUNT = 0, MPH_GAUGE_TOP = 1, MPH_GAUGE_BOTTOM = 2, MPH_GAUGE_WET = 3 } MphGaugeChannel;
+
+typedef struct MphGaugeConfig {      /* 24 bytes: axis 0, ngauge 4, points 8, radius 16 */
+    int axis;              /* 0, 1, 2 (2-D: 0, 1); -1: the axis of the largest |gravity| component
+                              (ties: the lowest axis; zero gravity: MPH_ERR_ARG) */
+    int ngauge;            /* 0..MPH_GAUGE_MAX */
+    const double* points;  /* [ngauge][3] */
+    double radius;         /* 0: RadiusRatioP * dx; must be <= MaxRadius + MARGIN (the cell stencil's reach) */
+} MphGaugeConfig;
+/* Set the gauges of the monitors that are on (cfg == NULL or ngauge == 0: none).  A reconfiguration
+ * like mph_monitor_configure: a flush point, the ring is emptied, STEP counts from this call, the
+ * step graphs are captured again at the next step.  A sample is then head, tracked rows, probes and
+ * {COUNT, TOP, BOTTOM, WET} per gauge: mph_monitor_sample_doubles returns MPH_MONITOR_HEAD +
+ * 6 ntrack + 2 nprobe + MPH_GAUGE_CHANNELS ngauge.  mph_monitor_configure replaces the whole
+ * configuration: after it there are no gauges.  MPH_ERR_ARG: monitors off, a count over the maximum,
+ * a bad axis, a radius below 0 or over the stencil's reach, too many bins.  MPH_ERR_UNSUPPORTED: slab
+ * mode.                                                                                           */
+int mph_gauge_configure(MphCtx* ctx, const MphGaugeConfig* cfg);
+
+typedef struct MphGaugeGrid {        /* 72 bytes: origin 0, spacing 24, count 48, axis 60, radius 64 */
+    double origin[3]; double spacing[3]; int count[3]; int axis; double radius;
+} MphGaugeGrid;
+/* The elevation map on demand: the record of every line of a lattice.  Line (i, j, k) passes through
+ * origin + (i spacing[0], j spacing[1], k spacing[2]) (each product and sum rounded, no contraction;
+ * lines outside the domain wrap); count[axis] must be 1, and count[2] in 2-D; at most
+ * MPH_GAUGE_GRID_MAX_LINES lines; a spacing must be > 0 where its count is above 1.  The axis and
+ * radius rules are mph_gauge_configure's.  out is [count[2]][count[1]][count[0]][MPH_GAUGE_CHANNELS],
+ * i fastest.  A flush point, legal where mph_sample_grid is (MPH_ERR_ARG before the first step and
+ * after mph_set, MPH_ERR_UNSUPPORTED in slab mode); it changes no state and touches no step graph.  A
+ * context without particles gives {0, -inf, +inf, 0} for every line.                              */
+int mph_gauge_grid(MphCtx* ctx, const MphGaugeGrid* g, double* out);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

@@ -74,8 +74,9 @@ struct MphCtx {
     size_t mon_ring_cap = 0;     // doubles the ring allocation holds
     int *mon_sorted = nullptr, *mon_map = nullptr;
     double* mon_probes = nullptr;
+    double* mon_gauges = nullptr;   // the gauge points (mph_gauge_configure), allocated at its first call
     long long mon_read = 0;
-    // lattice sampling (mph_sample_grid): the device result buffer (allocated at the first call,
+    // lattice sampling and the elevation map (mph_sample_grid, mph_gauge_grid): the device result buffer (allocated at the first call,
     // regrown when a larger lattice arrives) and whether the sorted set A and pres are the current
     // state's -- a step has run since creation and no mph_set since
     double* sample_out = nullptr;

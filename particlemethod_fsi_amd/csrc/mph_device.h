@@ -1,6 +1,6 @@
 // mph_device.h -- device helpers and the host-side launcher shared by the kernel translation units
 // (mph_sort.hip, mph_search.hip, mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip,
-// mph_sample.hip): the reference's exact periodic arithmetic, the cell grid's indexing, buffer-
+// mph_sample.hip, mph_gauge.hip): the reference's exact periodic arithmetic, the cell grid's indexing, buffer-
 // descriptor loads, the type predicates, wave-level helpers, a particle's wall motion and wrap, the prep tail, the
 // stencil around a point, and launch / blocks / by_dim / by_flag.  A helper used by one unit alone stays in that
 // unit; the neighbour lists' layout is mph_list.h.
@@ -348,6 +348,14 @@ __device__ __forceinline__ double4 struct_disp(const DevParams& P, double4 x, do
     return make_double4(image_exact<false>(x.x - x0.x, P.dw[0], P.hw[0], P.w075[0]),
                         image_exact<false>(x.y - x0.y, P.dw[1], P.hw[1], P.w075[1]),
                         image_exact<false>(x.z - x0.z, P.dw[2], P.hw[2], P.w075[2]), 0.0);
+}
+
+// The monitor kernels (mph_monitor.hip, mph_gauge.hip): is this step (the one the counters do not
+// count yet) a sampled one?
+__device__ __forceinline__ bool mon_sampled(const MonitorDev& M, long long& step)
+{
+    step = M.counters[0] + 1;
+    return step % M.stride == 0;
 }
 
 // ------------------------------------------------------------------------ point stencil -----

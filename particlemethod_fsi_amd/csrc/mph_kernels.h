@@ -1,6 +1,6 @@
 // mph_kernels.h -- launch interface of the hand-written HIP/CDNA4 (gfx950) kernels of the MPH explicit
 // hot path, the one host-visible interface of the kernel units (mph_sort.hip, mph_search.hip,
-// mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip, mph_sample.hip), used by the context's
+// mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip, mph_sample.hip, mph_gauge.hip), used by the context's
 // host units (mph_ctx.h) and the slab layer's (mph_dist.h).  It also decides a step's form
 // (seq_step): plain host C++, so a host compiler can include this header and test it.
 #pragma once
@@ -107,6 +107,13 @@ struct MonitorDev {
     const int* track_sorted = nullptr; // the distinct tracked ids ascending, padded with INT_MAX to 64
     const int* track_map = nullptr;    // tracked entry k -> its row of trk
     const double* probes = nullptr;    // [nprobe][3]
+    // free-surface gauges (mph_gauge.hip, mph_gauge_configure), behind every older member: a
+    // default-constructed MonitorDev is a configuration without gauges
+    int ngauge = 0, gauge_axis = 0;
+    int gauge_nbins = 1;               // bins of particle_spacing along gauge_axis (<= MPH_GAUGE_MAX_BINS)
+    double gauge_h = 0.0;              // radius
+    const double* gauges = nullptr;    // [ngauge][3]
+    double* gau = nullptr;             // {COUNT, TOP, BOTTOM, WET} per gauge
 };
 
 // A step's form: which variant of its kernels a step launches.  Decided by
@@ -274,6 +281,17 @@ struct SampleDev {
     double h;        // radius
 };
 
+// The elevation map (mph_gauge.hip, mph_gauge_grid): the lattice of lines with the resolved axis, bin
+// count and radius, passed to the kernel by value.
+struct GaugeGridDev {
+    double origin[3], spacing[3];
+    int count[3];
+    int nlines;      // count[0] count[1] count[2] (<= MPH_GAUGE_GRID_MAX_LINES)
+    int axis, nbins;
+    int waves;       // lines (waves) per block: 1 or 4
+    double h;        // radius
+};
+
 // One time step of the reference (main.cpp:597-686) is mapped onto these launches:
 //
 //   k_prep           calculateWall (3031-3071) + calculatePeriodicBoundary (3322-3333) + cell key
@@ -311,6 +329,10 @@ struct SampleDev {
 
 int monitor_blocks(int n);   // blocks (partial records) of k_monitor_partial
 void launch_monitor(const Launch& L, const MonitorDev& M);
+// the gauges' records of a sampled step into M.gau (launch_monitor calls it; M.ngauge > 0, L.P->n > 0)
+void launch_monitor_gauge(const Launch& L, const MonitorDev& M);
+// the four channels of every line into out ([nz][ny][nx][4], device); L.P->n > 0
+void launch_gauge_grid(const Launch& L, const GaugeGridDev& G, double* out);
 // fills G.tile / G.tiles from G.count / G.spacing (run_axis: the contiguous cell axis); returns the
 // number of tiles (waves)
 long long sample_tiling(SampleDev& G, int run_axis);

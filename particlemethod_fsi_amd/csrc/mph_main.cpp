@@ -114,6 +114,7 @@ struct MonitorCsv {
     int stride = 1, width = 0;
     std::vector<int> track;
     std::vector<double> probes;
+    std::vector<double> gauges;   // MPH_MONITOR_GAUGES: the gauge points, three numbers each
     std::vector<double> buf;
 };
 
@@ -144,6 +145,8 @@ static void monitor_header(const MonitorCsv& m)
     for (int i : m.track)
         for (int k = 0; k < 6; ++k) std::fprintf(m.f, ",p%d_%s", i, row[k]);
     for (size_t q = 0; q < m.probes.size() / 3; ++q) std::fprintf(m.f, ",probe%zu_value,probe%zu_count", q, q);
+    for (size_t q = 0; q < m.gauges.size() / 3; ++q)
+        std::fprintf(m.f, ",gauge%zu_count,gauge%zu_top,gauge%zu_bottom,gauge%zu_wet", q, q, q, q);
     std::fprintf(m.f, "\n");
 }
 
@@ -404,6 +407,11 @@ int main(int argc, char** argv)
         for (double v : parse_numbers(std::getenv("MPH_MONITOR_TRACK"))) mon.track.push_back((int)v);
         mon.probes = parse_numbers(std::getenv("MPH_MONITOR_PROBES"));
         if (mon.probes.size() % 3 != 0) die(nullptr, MPH_ERR_ARG, "MPH_MONITOR_PROBES (x,y,z;x,y,z;...)");
+        // free-surface gauges beside the monitors (include/mph_gpu.h mph_gauge_configure): lines
+        // through these points along MPH_MONITOR_GAUGE_AXIS (default -1: gravity's) of radius
+        // MPH_MONITOR_GAUGE_RADIUS (default 0: RadiusRatioP dx)
+        mon.gauges = parse_numbers(std::getenv("MPH_MONITOR_GAUGES"));
+        if (mon.gauges.size() % 3 != 0) die(nullptr, MPH_ERR_ARG, "MPH_MONITOR_GAUGES (x,y,z;x,y,z;...)");
         // the ring holds the samples of the longest batch the loop below issues: a batch ends at the
         // next .prof or .vtk output step or at EndTime
         const double span = std::fmin(std::fmin(cfg.output_interval, cfg.vtk_output_interval), cfg.end_time - cfg.time);
@@ -417,6 +425,15 @@ int main(int argc, char** argv)
         mc.probes = mon.probes.data();
         rc = mph_monitor_configure(ctx, &mc);
         if (rc) die(ctx, rc, "mph_monitor_configure");
+        if (!mon.gauges.empty()) {
+            MphGaugeConfig gc{};
+            gc.axis = std::getenv("MPH_MONITOR_GAUGE_AXIS") ? std::atoi(std::getenv("MPH_MONITOR_GAUGE_AXIS")) : -1;
+            gc.ngauge = (int)(mon.gauges.size() / 3);
+            gc.points = mon.gauges.data();
+            gc.radius = std::getenv("MPH_MONITOR_GAUGE_RADIUS") ? std::atof(std::getenv("MPH_MONITOR_GAUGE_RADIUS")) : 0.0;
+            rc = mph_gauge_configure(ctx, &gc);
+            if (rc) die(ctx, rc, "mph_gauge_configure");
+        }
         mon.width = mph_monitor_sample_doubles(ctx);
         mon.buf.resize((size_t)mc.capacity * mon.width);
         mon.f = std::fopen(mp, "w");

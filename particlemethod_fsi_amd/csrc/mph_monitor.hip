@@ -4,7 +4,8 @@
 // monitors are on, so a sample is taken by whichever path runs the step (captured graphs, direct
 // launches) and the host reads the ring without breaking a batch.
 //
-// Three plain launches per step (the probe kernel only with probes) and no floating-point atomics:
+// Three plain launches per step (the probe kernel only with probes; with gauges a fourth, the gauge
+// kernel of mph_gauge.hip, before the final one) and no floating-point atomics:
 // every block of k_monitor_partial owns a fixed range of particles and stores one partial record;
 // k_monitor_final adds the records in a fixed order.  A sample is therefore a function of the state
 // alone, bit for bit, in any batch shape.
@@ -99,13 +100,6 @@ __device__ __forceinline__ double mon_block_reduce(double (&sum)[kMonSums], doub
         for (int w = 1; w < kMonWaves; ++w) v = mon_combine(k, v, red[w][k]);
     }
     return v;
-}
-
-// is this step (the one the counters do not count yet) a sampled one?
-__device__ __forceinline__ bool mon_sampled(const MonitorDev& M, long long& step)
-{
-    step = M.counters[0] + 1;
-    return step % M.stride == 0;
 }
 
 // One partial record per block over its kMonBlock particles of the integrated set B (in the sorted
@@ -316,6 +310,9 @@ __global__ __launch_bounds__(kMonFinalThreads) void k_monitor_final(MonitorDev M
             out[MPH_MONITOR_HEAD + 6 * M.ntrack + 2 * tid] = M.prb[2 * tid];
             out[MPH_MONITOR_HEAD + 6 * M.ntrack + 2 * tid + 1] = M.prb[2 * tid + 1];
         }
+        // the gauges' records (k_monitor_gauge, mph_gauge.hip) behind the probes
+        if (tid < MPH_GAUGE_CHANNELS * M.ngauge)
+            out[MPH_MONITOR_HEAD + 6 * M.ntrack + 2 * M.nprobe + tid] = M.gau[tid];
     }
     __syncthreads();   // every thread has read the counters
     if (tid == 0) {
@@ -337,6 +334,7 @@ void launch_monitor(const Launch& L, const MonitorDev& M)
             launch(L.prof, "monitor_probe", L.stream, k_monitor_probe<decltype(D)::value>, dim3(M.nprobe), dim3(64),
                    P, M, n, L.A, L.start, L.pres);
         });
+    if (M.ngauge > 0) launch_monitor_gauge(L, M);
     launch(L.prof, "monitor_final", L.stream, k_monitor_final, dim3(1), dim3(kMonFinalThreads), M, nb, L.st);
 }
 

@@ -1,5 +1,6 @@
 // mph_observe.hip -- the host half of what observes a run without downloading its fields: the
-// per-step monitors (kernels: mph_monitor.hip) and the lattice sampling (kernel: mph_sample.hip).
+// per-step monitors (kernels: mph_monitor.hip), the free-surface gauges (kernels: mph_gauge.hip) and
+// the lattice sampling (kernel: mph_sample.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,8 +11,59 @@
 #include <vector>
 
 #include "mph_ctx.h"
+#include "mph_env.h"
 
 using namespace mph;
+
+// A monitor configuration's ring: `capacity` samples of `width` doubles (the allocation regrown when
+// too small), emptied -- the counters zeroed, so STEP counts from here -- and nothing read yet.
+static int monitor_ring(MphCtx* c, int capacity, int width)
+{
+    MonitorDev& D = c->mon;
+    const size_t need = (size_t)capacity * width;
+    if (need > c->mon_ring_cap) {
+        ctx_dfree(c, D.ring);
+        D.ring = nullptr;
+        c->mon_ring_cap = 0;
+        MPH_CK(ctx_dalloc(c, &D.ring, need));
+        c->mon_ring_cap = need;
+    }
+    MPH_HIP_OK(c, hipMemset(D.counters, 0, 2 * sizeof(long long)));
+    D.capacity = capacity;
+    D.width = width;
+    c->mon_read = 0;
+    return MPH_OK;
+}
+
+// What the gauges of mph_gauge_configure and the lines of mph_gauge_grid share: the axis (-1: the
+// largest |gravity| component's), the radius (0: RadiusP) and the bins along the axis.
+static int gauge_resolve(MphCtx* c, int axis, double radius, int* ax, double* h, int* nbins)
+{
+    const int dim = c->cfg.dim;
+    if (axis == -1) {
+        double best = 0.0;
+        for (int d = 0; d < dim; ++d)
+            if (std::fabs(c->cfg.gravity[d]) > best) {
+                best = std::fabs(c->cfg.gravity[d]);
+                axis = d;
+            }
+        if (axis < 0) return ctx_fail(c, MPH_ERR_ARG, "gauges: axis -1 needs a gravity component");
+    }
+    if (axis < 0 || axis >= dim)
+        return ctx_fail(c, MPH_ERR_ARG, "gauges: axis " + std::to_string(axis) + " outside 0.." + std::to_string(dim - 1));
+    const double reach = c->h.max_radius + 0.1 * c->h.dx;   // MaxRadius + MARGIN (make_dev_params)
+    if (!(radius >= 0.0) || radius > reach)
+        return ctx_fail(c, MPH_ERR_ARG, "gauges: radius outside [0, MaxRadius + MARGIN = " + std::to_string(reach) + "]");
+    const double bins = std::ceil((c->cfg.domain_max[axis] - c->cfg.domain_min[axis]) / c->cfg.particle_spacing);
+    if (!(bins >= 1.0) || bins > (double)MPH_GAUGE_MAX_BINS)
+        return ctx_fail(c, MPH_ERR_ARG, "gauges: the domain has " + std::to_string(bins) + " bins of particle_spacing along axis " +
+                                            std::to_string(axis) + ", outside 1..MPH_GAUGE_MAX_BINS = " +
+                                            std::to_string(MPH_GAUGE_MAX_BINS));
+    *ax = axis;
+    *h = radius > 0.0 ? radius : c->h.rp;
+    *nbins = (int)bins;
+    return MPH_OK;
+}
 
 extern "C" {
 
@@ -55,15 +107,9 @@ int mph_monitor_configure(MphCtx* c, const MphMonitorConfig* m)
         D.track_map = c->mon_map;
         D.probes = c->mon_probes;
     }
-    const int width = MPH_MONITOR_HEAD + 6 * m->ntrack + 2 * m->nprobe;
-    const size_t need = (size_t)m->capacity * width;
-    if (need > c->mon_ring_cap) {
-        ctx_dfree(c, D.ring);
-        D.ring = nullptr;
-        c->mon_ring_cap = 0;
-        MPH_CK(ctx_dalloc(c, &D.ring, need));
-        c->mon_ring_cap = need;
-    }
+    // (the whole configuration is replaced: no gauges until the next mph_gauge_configure)
+    MPH_CK(monitor_ring(c, m->capacity, MPH_MONITOR_HEAD + 6 * m->ntrack + 2 * m->nprobe));
+    D.ngauge = 0;
     // the distinct tracked ids ascending (the kernel's search), and each entry's row among them
     std::vector<int> sorted(m->track, m->track + m->ntrack);
     std::sort(sorted.begin(), sorted.end());
@@ -77,16 +123,12 @@ int mph_monitor_configure(MphCtx* c, const MphMonitorConfig* m)
     MPH_HIP_OK(c, hipMemcpy(c->mon_sorted, sorted.data(), sizeof(int) * sorted.size(), hipMemcpyHostToDevice));
     MPH_HIP_OK(c, hipMemcpy(c->mon_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
     MPH_HIP_OK(c, hipMemcpy(c->mon_probes, probes.data(), sizeof(double) * probes.size(), hipMemcpyHostToDevice));
-    MPH_HIP_OK(c, hipMemset(D.counters, 0, 2 * sizeof(long long)));
     MPH_HIP_OK(c, hipMemset(D.trk, 0, sizeof(double) * 6 * MPH_MONITOR_MAX_TRACK));
     MPH_HIP_OK(c, hipMemset(D.prb, 0, sizeof(double) * 2 * MPH_MONITOR_MAX_PROBES));
     D.stride = m->stride;
-    D.capacity = m->capacity;
     D.ntrack = m->ntrack;
     D.nprobe = m->nprobe;
-    D.width = width;
     D.probe_h = m->probe_radius > 0.0 ? m->probe_radius : c->h.rp;
-    c->mon_read = 0;
     c->mon_on = true;
     c->L.mon = &c->mon;
     return MPH_OK;
@@ -119,6 +161,93 @@ long long mph_monitor_read(MphCtx* c, double* out, long long max_samples, long l
     }
     c->mon_read = first + k;
     return k;
+}
+
+// ---- free-surface gauges (kernels: mph_gauge.hip) -----------------------------------------------
+
+int mph_gauge_configure(MphCtx* c, const MphGaugeConfig* g)
+{
+    if (!c) return MPH_ERR_ARG;
+    MPH_CK(ctx_flush(c));
+    if (c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "gauges are not available in slab mode (a line spans the ranks)");
+    if (!c->mon_on) return ctx_fail(c, MPH_ERR_ARG, "gauges: the monitors are off (mph_monitor_configure first)");
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    const int ngauge = g ? g->ngauge : 0;
+    if (ngauge < 0 || ngauge > MPH_GAUGE_MAX || (ngauge > 0 && !g->points))
+        return ctx_fail(c, MPH_ERR_ARG, "gauges: 0.." + std::to_string(MPH_GAUGE_MAX) + " gauges");
+    int axis = 0, nbins = 1;
+    double h = 0.0;
+    if (ngauge > 0) MPH_CK(gauge_resolve(c, g->axis, g->radius, &axis, &h, &nbins));
+    MPH_CK(drop_graphs(c));
+    MonitorDev& D = c->mon;
+    if (!D.gau) {   // once, for the maximum
+        MPH_CK(ctx_dalloc(c, &c->mon_gauges, 3 * (size_t)MPH_GAUGE_MAX));
+        MPH_CK(ctx_dalloc(c, &D.gau, (size_t)MPH_GAUGE_CHANNELS * MPH_GAUGE_MAX));
+        D.gauges = c->mon_gauges;
+    }
+    MPH_CK(monitor_ring(c, D.capacity, MPH_MONITOR_HEAD + 6 * D.ntrack + 2 * D.nprobe + MPH_GAUGE_CHANNELS * ngauge));
+    std::vector<double> points(3 * (size_t)MPH_GAUGE_MAX, 0.0);
+    if (ngauge > 0) std::copy(g->points, g->points + 3 * (size_t)ngauge, points.begin());
+    MPH_HIP_OK(c, hipMemcpy(c->mon_gauges, points.data(), sizeof(double) * points.size(), hipMemcpyHostToDevice));
+    MPH_HIP_OK(c, hipMemset(D.gau, 0, sizeof(double) * MPH_GAUGE_CHANNELS * MPH_GAUGE_MAX));
+    D.ngauge = ngauge;
+    D.gauge_axis = axis;
+    D.gauge_nbins = nbins;
+    D.gauge_h = h;
+    return MPH_OK;
+}
+
+int mph_gauge_grid(MphCtx* c, const MphGaugeGrid* g, double* out)
+{
+    if (!c || !g || !out) return MPH_ERR_ARG;
+    MPH_CK(ctx_flush(c));
+    if (c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "gauge grid: not available in slab mode (a line spans the ranks)");
+    long long lines = 1;
+    for (int d = 0; d < 3; ++d) {
+        if (g->count[d] < 1 || !std::isfinite(g->spacing[d]) || !std::isfinite(g->origin[d]) ||
+            (g->count[d] > 1 && !(g->spacing[d] > 0.0)))
+            return ctx_fail(c, MPH_ERR_ARG, "gauge grid: counts must be >= 1, the origin finite and a spacing > 0 where its count is above 1");
+        lines *= g->count[d];   // (at most 2^20 before each factor below 2^31)
+        if (lines > MPH_GAUGE_GRID_MAX_LINES)
+            return ctx_fail(c, MPH_ERR_ARG, "gauge grid: more than MPH_GAUGE_GRID_MAX_LINES = " +
+                                                std::to_string(MPH_GAUGE_GRID_MAX_LINES) + " lines");
+    }
+    GaugeGridDev G{};
+    MPH_CK(gauge_resolve(c, g->axis, g->radius, &G.axis, &G.h, &G.nbins));
+    if (g->count[G.axis] != 1) return ctx_fail(c, MPH_ERR_ARG, "gauge grid: the count along the lines' axis must be 1");
+    if (c->cfg.dim == 2 && g->count[2] != 1) return ctx_fail(c, MPH_ERR_ARG, "gauge grid: count[2] must be 1 in 2-D");
+    const size_t need = (size_t)lines * MPH_GAUGE_CHANNELS;
+    if (c->n == 0) {
+        const double empty[MPH_GAUGE_CHANNELS] = {0.0, -INFINITY, INFINITY, 0.0};
+        for (size_t k = 0; k < need; ++k) out[k] = empty[k % MPH_GAUGE_CHANNELS];
+        return MPH_OK;
+    }
+    if (!c->a_current)
+        return ctx_fail(c, MPH_ERR_ARG, "gauge grid: run a step first (none since creation or since the last mph_set)");
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    if (need > c->sample_cap) {
+        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+        ctx_dfree(c, c->sample_out);
+        c->sample_out = nullptr;
+        c->sample_cap = 0;
+        MPH_CK(ctx_dalloc(c, &c->sample_out, need));
+        c->sample_cap = need;
+    }
+    for (int d = 0; d < 3; ++d) {
+        G.origin[d] = g->origin[d];
+        G.spacing[d] = g->spacing[d];
+        G.count[d] = g->count[d];
+    }
+    G.nlines = (int)lines;
+    // four lines to a 256-thread block, as measured; 1: one line per block (A/B)
+    G.waves = env_int("MPH_GAUGE_GRID_WAVES", 4) == 1 ? 1 : 4;
+    launch_gauge_grid(c->L, G, c->sample_out);
+    MPH_HIP_OK(c, hipGetLastError());
+    MPH_HIP_OK(c, hipMemcpyAsync(out, c->sample_out, sizeof(double) * need, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    return MPH_OK;
 }
 
 // ---- lattice sampling (kernel: mph_sample.hip) --------------------------------------------------

@@ -60,7 +60,7 @@ EXPORTED_SYMBOLS = [
     "mph_set_step_batching", "mph_neighbor_rows", "mph_dist_overlap", "mph_list_layout",
     "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
     "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
-    "mph_lean_step_stats", "mph_key_fold_stats",
+    "mph_lean_step_stats", "mph_key_fold_stats", "mph_gauge_configure", "mph_gauge_grid",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -106,6 +106,25 @@ def _sample_grid(origin, spacing, count, radius=0.0, classes=0) -> MphSampleGrid
     return g
 
 
+class MphGaugeConfig(ctypes.Structure):
+    """include/mph_gpu.h MphGaugeConfig."""
+    _fields_ = [("axis", ctypes.c_int), ("ngauge", ctypes.c_int), ("points", ctypes.c_void_p),
+                ("radius", ctypes.c_double)]
+
+
+class MphGaugeGrid(ctypes.Structure):
+    """include/mph_gpu.h MphGaugeGrid."""
+    _fields_ = [("origin", ctypes.c_double * 3), ("spacing", ctypes.c_double * 3), ("count", ctypes.c_int * 3),
+                ("axis", ctypes.c_int), ("radius", ctypes.c_double)]
+
+
+# MphGaugeChannel (include/mph_gpu.h): name -> index into a gauge's (a line's) record
+GAUGE_CHANNELS = {"COUNT": 0, "TOP": 1, "BOTTOM": 2, "WET": 3}
+GAUGE_MAX = 64
+GAUGE_MAX_BINS = 8192
+GAUGE_GRID_MAX_LINES = 1 << 20
+
+
 # MphMonitorSlot (include/mph_gpu.h): name -> index into a sample's head
 MONITOR_HEAD = 32
 MONITOR_MAX_TRACK = 64
@@ -131,6 +150,17 @@ def monitor_split(row: np.ndarray, ntrack: int, nprobe: int):
                          % (ntrack, nprobe, b + 2 * nprobe, row.shape[-1]))
     return (row[..., :a], row[..., a:b].reshape(lead + (ntrack, 6)),
             row[..., b:].reshape(lead + (nprobe, 2)))
+
+
+def monitor_gauges(row: np.ndarray, ntrack: int, nprobe: int, ngauge: int):
+    """The gauge tail of one sample (or of [k, width] samples) of a configuration with gauges
+    (mph_gauge_configure) -> [.., ngauge, 4] rows {COUNT, TOP, BOTTOM, WET} (GAUGE_CHANNELS)."""
+    row = np.asarray(row)
+    b = MONITOR_HEAD + 6 * ntrack + 2 * nprobe
+    if row.shape[-1] != b + len(GAUGE_CHANNELS) * ngauge:
+        raise ValueError("a sample of %d tracked particles, %d probes and %d gauges has %d doubles, not %d"
+                         % (ntrack, nprobe, ngauge, b + len(GAUGE_CHANNELS) * ngauge, row.shape[-1]))
+    return row[..., b:].reshape(row.shape[:-1] + (ngauge, len(GAUGE_CHANNELS)))
 
 
 class MphError(RuntimeError):
@@ -224,13 +254,15 @@ def load_library() -> ctypes.CDLL:
         "mph_idle_wall_stats": (ip, [vp, vp]),
         "mph_lean_step_stats": (ip, [vp, vp]),
         "mph_key_fold_stats": (ip, [vp, vp]),
+        "mph_gauge_configure": (ip, [vp, ctypes.POINTER(MphGaugeConfig)]),
+        "mph_gauge_grid": (ip, [vp, ctypes.POINTER(MphGaugeGrid), vp]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
                 "mph_dist_overlap", "mph_profile_graphs", "mph_list_stats", "mph_list_layout",
                 "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
                 "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
-                "mph_lean_step_stats", "mph_key_fold_stats"}
+                "mph_lean_step_stats", "mph_key_fold_stats", "mph_gauge_configure", "mph_gauge_grid"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -561,11 +593,16 @@ class MphSolver:
         return {"neighbor_ms": float(a[0]), "explicit_ms": float(a[1]), "virial_ms": float(a[2])}
 
     # -- monitors ---------------------------------------------------------------------------------
-    def monitor(self, stride=1, capacity: int = 4096, track=(), probes=(), probe_radius: float = 0.0):
+    def monitor(self, stride=1, capacity: int = 4096, track=(), probes=(), probe_radius: float = 0.0,
+                gauges=(), gauge_axis: int = -1, gauge_radius: float = 0.0):
         """mph_monitor_configure: from the next step on, every `stride`-th step leaves a sample
         (MONITOR_SLOTS, then the tracked particles `track` (original indices), then the pressure
         probes `probes` ([k][3] points)) in a device ring of `capacity` samples, computed inside the
-        step graphs -- stepping stays batched, monitor_read() fetches.  monitor(None): off."""
+        step graphs -- stepping stays batched, monitor_read() fetches.  monitor(None): off.
+        gauges: free-surface gauges ([k][3] points, mph_gauge_configure), lines along `gauge_axis`
+        (-1: gravity's) of radius `gauge_radius` (0: RadiusRatioP dx); each adds {COUNT, TOP, BOTTOM,
+        WET} (GAUGE_CHANNELS) behind the probes, read with monitor_gauges()."""
+        self._mon_gauges = 0
         if stride is None:
             _check(self._L.mph_monitor_configure(self._h, None), self._h)
             self._mon_shape = None
@@ -577,6 +614,11 @@ class MphSolver:
         _check(self._L.mph_monitor_configure(self._h, ctypes.byref(m)), self._h)
         self._mon_shape = (len(tr), len(pr))
         self._mon_cap = int(capacity)
+        ga = np.ascontiguousarray(gauges, np.float64).reshape(-1, 3)
+        if len(ga):
+            g = MphGaugeConfig(int(gauge_axis), len(ga), ga.ctypes.data, float(gauge_radius))
+            _check(self._L.mph_gauge_configure(self._h, ctypes.byref(g)), self._h)
+            self._mon_gauges = len(ga)
 
     def monitor_read(self, max_samples: int | None = None):
         """(samples [k, width], lost): the unread samples, oldest first, and how many unread ones the
@@ -593,7 +635,30 @@ class MphSolver:
     def monitor_split(self, rows: np.ndarray):
         """monitor_split(rows, ...) with this solver's tracked-particle and probe counts."""
         nt, npr = self._mon_shape
-        return monitor_split(rows, nt, npr)
+        rows = np.asarray(rows)
+        return monitor_split(rows[..., :rows.shape[-1] - len(GAUGE_CHANNELS) * self._mon_gauges], nt, npr)
+
+    def monitor_gauges(self, rows: np.ndarray):
+        """monitor_gauges(rows, ...) with this solver's counts: the gauges' records [.., ngauge, 4]."""
+        nt, npr = self._mon_shape
+        return monitor_gauges(rows, nt, npr, self._mon_gauges)
+
+    # -- elevation map ----------------------------------------------------------------------------
+    def gauge_grid(self, origin, spacing, count, axis: int = -1, radius: float = 0.0):
+        """mph_gauge_grid: the gauge record of every line of a lattice of count = (nx, ny, nz) lines
+        along `axis` (-1: gravity's; count[axis] must be 1) through origin + (i sx, j sy, k sz) ->
+        array of shape (nz, ny, nx, 4), the channels GAUGE_CHANNELS (COUNT, TOP, BOTTOM, WET) over the
+        fluid particles within `radius` (0: RadiusRatioP dx) of each line.  Needs a step since
+        creation / the last set(); a flush point."""
+        g = MphGaugeGrid()
+        for d in range(3):
+            g.origin[d], g.spacing[d], g.count[d] = float(origin[d]), float(spacing[d]), int(count[d])
+        g.axis, g.radius = int(axis), float(radius)
+        shape = (max(int(count[2]), 0), max(int(count[1]), 0), max(int(count[0]), 0), len(GAUGE_CHANNELS))
+        n = shape[0] * shape[1] * shape[2]
+        out = np.zeros(shape if 0 < n <= GAUGE_GRID_MAX_LINES else (1, 1, 1, len(GAUGE_CHANNELS)))
+        _check(self._L.mph_gauge_grid(self._h, ctypes.byref(g), out.ctypes.data), self._h)
+        return out
 
     # -- lattice sampling -------------------------------------------------------------------------
     def sample_grid(self, origin, spacing, count, radius: float = 0.0, classes: int = 0, timed: bool = False,
