@@ -596,7 +596,9 @@ int mph_list_stats(MphCtx* ctx, double* mean, int* max);
  * verification: out6 = {waves (tiles of 64 particles), waves that made at least one row jump,
  * row jumps in all, the most jumps of one wave, gap rows in all (the rows the lanes skipped at
  * their jumps), the most rows of one lane (entries + gaps)}.  Read-only, reduced on the host.
- * Single contexts only (MPH_ERR_UNSUPPORTED in slab mode).  ABI 5.                             */
+ * A wave with 16-bit rows (mph_list_format_stats) jumps at every stencil group end; only its jumps
+ * that left a gap in some lane are counted, as a wave with 32-bit rows makes no other.
+ * Single contexts only (MPH_ERR_UNSUPPORTED in slab mode).  ABI 5.                              */
 int mph_list_layout(MphCtx* ctx, long long out6[6]);
 /* Lazy wall steps, for verification: out2 = {idle wave-steps, lazy steps} since the
  * creation.  A lazy step is a step that stores no output-only field (every step of an 8-step batch
@@ -620,6 +622,16 @@ int mph_lean_step_stats(MphCtx* ctx, long long out2[2]);
  * without MPH_KEY_FOLD=0; elsewhere the first stays 0 and the second counts every step.  A flush
  * point.  Additive: no change of MPH_ABI_VERSION.                                               */
 int mph_key_fold_stats(MphCtx* ctx, long long out2[2]);
+/* The formats of the neighbour lists, for verification: out3 = {waves whose rows are
+ * 16-bit ones, waves with 32-bit rows, waves among the latter that began in the 16-bit format and
+ * started over} of the last search.  A 3-D interior wave takes the 16-bit rows when the candidates
+ * of each of its stencil groups lie within 8191 indices; none does in 2-D, in slab mode or with
+ * MPH_LIST16=0 at creation.  A flush point.  Additive: no change of MPH_ABI_VERSION.            */
+int mph_list_format_stats(MphCtx* ctx, long long out3[3]);
+/* Of the waves with 32-bit rows of the last search, those that are interior 3-D waves turned away
+ * by the span limit alone (the others are waves at periodic faces, idle wall waves, ghosts,
+ * restarted waves): *out.  A flush point.  Additive: no change of MPH_ABI_VERSION.               */
+int mph_list_span_misses(MphCtx* ctx, long long* out);
 /* The neighbour lists of calculateNeighbor themselves (main.cpp:1764-1772: Neighbor[i][k] = j for
  * k < 512), for verification: the sets of the `count` particles [first, first + count) (original
  * order) from the last search, each row as ascending original indices (the reference's rows are in

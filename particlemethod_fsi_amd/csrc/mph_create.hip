@@ -199,6 +199,7 @@ static int init_alloc(MphCtx* c, const CreateArgs& a)
     MPH_CK(ctx_dalloc(c, &c->L.nbcount, cap));
     // the lists' row jumps: a header word per wave, a word of gap starts per lane (whole tiles)
     MPH_CK(ctx_dalloc(c, &c->L.lhdr, ntile)); MPH_CK(ctx_dalloc(c, &c->L.lgap, ntile * kTile));
+    MPH_CK(ctx_dalloc(c, &c->L.lbase, ntile * kBaseInts));
     for (double** p : {&c->L.pres, &c->L.gx, &c->L.gy, &c->L.gz, &c->L.pa}) MPH_CK(ctx_dalloc(c, p, cap));
     for (double4** p : {&c->L.force, &c->L.acc, &c->L.fpart, &c->L.rec}) MPH_CK(ctx_dalloc(c, p, cap));
     for (double** p : {&c->L.dens_a, &c->L.vstrain, &c->L.divp}) MPH_CK(ctx_dalloc(c, p, cap));

@@ -121,6 +121,14 @@ void ctx_fill_launch(MphCtx* c)
     // MPH_KEY_FOLD=0: every step opens with k_prep, no pass B leaves the next step's cell keys
     // (seq_step); slab contexts never fold
     L.key_fold = !c->dist && env_int("MPH_KEY_FOLD", 1) != 0;
+    // MPH_LIST16=0: every wave keeps the 32-bit list rows; else the 3-D interior waves whose group
+    // spans allow take the 16-bit ones (mph_params.h kOff16Bits).  MPH_LIST16_SPAN (tests): a lower
+    // span limit, so that small cases mix the formats.  Slab contexts keep the wide rows.
+    c->P.list16_span = 0;
+    if (!c->dist && c->P.dim == 3 && env_int("MPH_LIST16", 1) != 0) {
+        const int span = env_is("MPH_LIST16_SPAN", "") ? kList16Span : env_int("MPH_LIST16_SPAN", kList16Span);
+        c->P.list16_span = span < 0 ? 0 : (span > kList16Span ? kList16Span : span);
+    }
     L.P = &c->P;
     L.stream = c->stream;
     // work-balanced XCD map of the passes from this many particles (MPH_XCD_BAL_MIN: tests force it

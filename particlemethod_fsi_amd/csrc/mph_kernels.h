@@ -149,6 +149,8 @@ struct Launch {
     // the row jumps of the lists (mph_list.h RowMask): one header word per wave, one word of gap
     // starts per particle; ncount counts rows, gaps included
     unsigned long long *lhdr = nullptr, *lgap = nullptr;
+    // the group bases of the waves with 16-bit rows (mph_params.h kOff16Bits): kBaseInts per wave
+    int* lbase = nullptr;
     int* wface = nullptr;         // slab mode: face-wavefront flags written by pass B (early send)
     VSrc vsrc;                    // slab mode: where the sort finds the kept entries of its input
     // fewest particles for the work-balanced XCD map of the passes (split in k_rank_scatter);

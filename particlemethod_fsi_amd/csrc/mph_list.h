@@ -101,15 +101,7 @@ __device__ __forceinline__ void add_wave_work(int* seg, int cnt, int i, int n, i
 }
 
 __device__ __forceinline__ int nbr_entry(int j, int type) { return j | (type << kTypeShift); }
-// The search's per-lane counter (scan_candidates_lds): lane x 4 in bits 0-7, the row of the next
-// stored entry in bits 8-17 (the stored entries so far plus the gaps of the row jumps; up to 1023,
-// so a lane that keeps all 512 entries the reference allows does not carry into the total) and
-// every accepted neighbour from bit 18.  The next list slot's byte offset in the wave's ELL tile is
-// soff & kSoffMask; a row past the tile's kTileRows (only an overflowing lane, > 512 entries, the
-// step's MPH_ERR_NEIGHBOR_OVERFLOW) is dropped by the tile's buffer descriptor.
-constexpr int kListKeep = 256 + (1 << 18), kListTotal = 1 << 18, kSoffMask = 0x3FFFF;
-__device__ __forceinline__ int soff_total(int soff) { return (int)((unsigned)soff >> 18); }
-__device__ __forceinline__ int soff_stored(int soff) { return (soff >> 8) & 0x3FF; }
+// (the search's per-lane store counter and its constants per format: mph_params.h soff_*)
 
 __device__ __forceinline__ const int* ell_row(const int* nbr, int i)
 {
@@ -147,6 +139,46 @@ __device__ __forceinline__ void nbr_at(const NbrList& L, int k, int& j, int& t)
     j = e & kIndexMask;
     t = e >> kTypeShift;
 }
+// the same of a short wave (16-bit rows): the entry's offset from its group's base, and its type
+__device__ __forceinline__ void nbr_at16(const NbrList& L, int k, int& off, int& t)
+{
+    using gcchar = const __attribute__((address_space(1))) char;
+    using gcshort = const __attribute__((address_space(1))) unsigned short;
+    const unsigned e = *(gcshort*)((gcchar*)L.tile + ((unsigned)ell_slot(k, L.lane) << 1));
+    off = entry16_off(e);
+    t = entry16_type(e);
+}
+
+// A short wave's list loop keeps the stencil group of its (wave-uniform) row as scalars: the group,
+// the row its successor starts on (header byte g; none after the last) and the group's base scaled
+// to the loop's gather stride, re-read from the wave's bases where the row passes a group start --
+// kMaxJumps times per wave, a compare and a branch on the other rows.
+struct GroupWalk {
+    const int* base;   // the wave's kBaseInts bases
+    unsigned long long hdr;
+    int stride;        // bytes per gathered record
+    GroupCursor cur;   // (mph_params.h)
+    unsigned sb;       // base[cur.g] * stride
+    int j0;            // base[cur.g]
+    __device__ __forceinline__ void load()
+    {
+        j0 = __builtin_amdgcn_readfirstlane(base[cur.g]);
+        sb = (unsigned)j0 * (unsigned)stride;
+    }
+    __device__ __forceinline__ void init(const int* lbase, int i, unsigned long long h, int st)
+    {
+        base = lbase + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * kBaseInts;
+        hdr = h;
+        stride = st;
+        cur.init(h);
+        load();
+    }
+    // on to row k (k wave-uniform, never below an earlier call's)
+    __device__ __forceinline__ void seek(int k)
+    {
+        if (cur.seek(hdr, k)) load();
+    }
+};
 
 // Aligned rows (mph_params.h kAlignRows).  A wave's jumps are recorded in two places: the wave's
 // header word lhdr[tile] (byte k < kMaxJumps: the row the lanes moved on to at jump k; byte 7: the
@@ -171,7 +203,7 @@ __device__ __forceinline__ RowMask row_mask(unsigned long long hdr, const unsign
     RowMask m;
     m.lo = ~bits_from(end);
     m.hi = ~bits_from(end - 64);
-    const int J = jump_count(hdr);
+    const int J = gap_count(hdr);
     if (J) {   // wave-uniform
         const unsigned long long g = lgap[i];
         for (int k = 0; k < J; ++k) {

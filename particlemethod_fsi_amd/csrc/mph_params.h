@@ -69,6 +69,17 @@ constexpr int kTypeShift = 28;
 // memory access (no cache lookup)
 constexpr unsigned kGatherOob = 0xFFFFFFC0u;
 constexpr int kIndexMask = (1 << kTypeShift) - 1;
+// 16-bit list rows: a 3-D interior wave whose candidates of every stencil
+// group (the kGroups columns of one slowest-axis offset) lie within kList16Span indices of a wave-
+// uniform base stores its entries as (index - base[group]) | type << kOff16Bits in rows of 64
+// uint16 (128 bytes, the first half of its tile); its kBaseInts bases live in a per-wave array
+// beside the header words.
+constexpr int kOff16Bits = 13;
+constexpr int kOff16Mask = (1 << kOff16Bits) - 1;
+constexpr int kList16Span = kOff16Mask;
+constexpr int kBaseInts = 8;   // kGroups bases and one spare int per wave
+static_assert(MPH_TYPE_COUNT <= (1 << (16 - kOff16Bits)), "a 16-bit list entry has 3 type bits");
+static_assert(2 * MPH_R + 1 < kBaseInts, "one base per stencil group");
 constexpr int kPad = 8;         // extra elements behind every per-particle array (vector over-reads)
 
 inline bool is_fluid(int t) { return t >= 0 && t < 2; }   // main.cpp:69-70
@@ -121,6 +132,10 @@ struct DevParams {
     // both ends of that axis (DevState.seam_occ) or on the slab axis (seam_always bit)
     double sinner_lo[3], sinner_hi[3];
     int seam_always;
+    // 16-bit list rows (kOff16Bits below): the widest index span of a stencil group's candidates a
+    // wave may have and still take them; 0: every wave keeps the 32-bit rows (MPH_LIST16=0, 2-D,
+    // slab contexts).  (In the padding behind seam_always: every other member keeps its offset.)
+    int list16_span;
     double dmin[3], dw[3], hw[3], w075[3];   // domain min / width / half width / 0.75 width
     double corg[3];    // origin of the GPU cell grid (dmin, or the slab window's lower edge)
     double ginv[3];    // 1 / GPU cell width per axis
@@ -170,6 +185,9 @@ struct DevParams {
 static_assert(offsetof(DevParams, rl_trimf) == offsetof(DevParams, rlf) + sizeof(float) &&
               offsetof(DevParams, rl_trimf) + sizeof(float) == sizeof(DevParams),
               "rl_trimf fills the tail padding behind rlf: the size is the one without it");
+static_assert(offsetof(DevParams, list16_span) == offsetof(DevParams, seam_always) + sizeof(int) &&
+              offsetof(DevParams, dmin) == offsetof(DevParams, list16_span) + sizeof(int),
+              "list16_span fills the padding behind seam_always");
 
 // Derived uniforms of DevParams (same expressions the kernels used, so the same bits).
 inline void set_uniforms(DevParams& P)
@@ -296,9 +314,71 @@ constexpr size_t kStateHead = offsetof(DevState, seg_work);
 // The lists' row jumps (kAlignRows above; mph_list.h RowMask), decoded alike by the kernels and
 // the host readers: byte 7 of a wave's header word is its jump count J; gap k < J of a lane is the
 // rows [byte k of the lane's gap word, byte k of the header).
-MPH_HD inline int jump_count(unsigned long long hdr) { return (int)(hdr >> 56); }
+// The bits of byte 7 above the count are the wave's flags: kHdrShort, its rows are 16-bit ones (then
+// J = kMaxJumps: every group end is a jump, so header byte g - 1 is the first row of group g);
+// kHdrNoGap, none of a short wave's lanes has a gap (its rows are plain, no mask needed);
+// Byte kHdrRestartByte (no jump's) is 1 in a wide wave that began in the 16-bit format and started over.
+constexpr unsigned kHdrShort = 0x80, kHdrNoGap = 0x40;
+constexpr int kHdrRestartByte = 6;
+// (the same byte is kHdrSpanMiss in an interior wave that stayed wide because a group's span
+// passed DevParams.list16_span)
+constexpr unsigned kHdrSpanMiss = 2;
+MPH_HD inline int jump_count(unsigned long long hdr) { return (int)(hdr >> 56) & 7; }
+MPH_HD inline bool hdr_short(unsigned long long hdr) { return ((hdr >> 56) & kHdrShort) != 0; }
+MPH_HD inline bool hdr_restarted(unsigned long long hdr) { return ((hdr >> (8 * kHdrRestartByte)) & 1) != 0; }
+MPH_HD inline bool hdr_span_miss(unsigned long long hdr) { return ((hdr >> (8 * kHdrRestartByte)) & kHdrSpanMiss) != 0; }
+// the jumps that may have left a gap in a lane (what a row mask is built from)
+MPH_HD inline int gap_count(unsigned long long hdr) { return ((hdr >> 56) & kHdrNoGap) ? 0 : jump_count(hdr); }
 MPH_HD inline int gap_begin(unsigned long long gap, int k) { return (int)((gap >> (8 * k)) & 0xff); }
 MPH_HD inline int gap_end(unsigned long long hdr, int k) { return (int)((hdr >> (8 * k)) & 0xff); }
+
+// A 16-bit entry and its parts; the stencil group of row k of a short wave (header byte g - 1 is
+// the first row of group g; equal bytes: empty groups).
+MPH_HD inline unsigned entry16(int off, int type) { return (unsigned)off | ((unsigned)type << kOff16Bits); }
+MPH_HD inline int entry16_off(unsigned e) { return (int)(e & kOff16Mask); }
+MPH_HD inline int entry16_type(unsigned e) { return (int)(e >> kOff16Bits); }
+MPH_HD inline int row_group(unsigned long long hdr, int k)
+{
+    int g = 0;
+    while (g < kMaxJumps && k >= gap_end(hdr, g)) ++g;
+    return g;
+}
+// The same for rows visited in ascending order (the passes' list loops): the group of the last row
+// asked for and the row its successor starts on (none after the last group).
+struct GroupCursor {
+    int g, nxt;
+    MPH_HD void init(unsigned long long hdr)
+    {
+        g = 0;
+        nxt = gap_end(hdr, 0);
+    }
+    // moves on to row k's group; true when the group changed
+    MPH_HD bool seek(unsigned long long hdr, int k)
+    {
+        bool moved = false;
+        while (k >= nxt) {
+            ++g;
+            nxt = g < kMaxJumps ? gap_end(hdr, g) : 0x7fffffff;
+            moved = true;
+        }
+        return moved;
+    }
+};
+
+// The search's per-lane store counter (mph_search.hip scan_candidates_lds), per format (s16: rows of
+// 64 uint16): the lane's byte offset inside a row in the low bits (lane x 4 in bits 0-7, or lane x 2
+// in bits 0-6), above it the row of the next stored entry -- the stored entries so far plus the
+// gaps of the row jumps, up to 1023 (or 2047), so a lane that keeps all 512 entries the reference
+// allows does not carry into the total -- and every accepted neighbour from bit 18.  The next list
+// slot's byte offset in the wave's ELL tile is soff & kSoffMask; a row past the tile's kTileRows
+// (only an overflowing lane, > 512 entries, the step's MPH_ERR_NEIGHBOR_OVERFLOW) is dropped by
+// the tile's buffer descriptor, which spans kTileRows rows of the wave's format.
+constexpr int kListTotal = 1 << 18, kSoffMask = 0x3FFFF;
+MPH_HD constexpr int soff_row_shift(bool s16) { return s16 ? 7 : 8; }
+MPH_HD constexpr int soff_first(bool s16, int lane) { return lane << (s16 ? 1 : 2); }
+MPH_HD constexpr int soff_keep(bool s16) { return (1 << soff_row_shift(s16)) + kListTotal; }
+MPH_HD constexpr int soff_total(int soff) { return (int)((unsigned)soff >> 18); }
+MPH_HD constexpr int soff_stored(bool s16, int soff) { return (soff & kSoffMask) >> soff_row_shift(s16); }
 
 // Pass A's single-cutoff form (pass_a_term<.., true>) when RadiusA = RadiusP = RadiusV (RadiusG =
 // RadiusA, main.cpp:1195-1198), as in every BASELINE config.

@@ -173,13 +173,30 @@ __device__ __forceinline__ void pass_a_finish(const DevParams& P, const DevTable
 // it (a gap of its row jumps, or past its end) gathers nothing and is not summed.
 // The batch of U rows from k0: the entries' loads first, then which rows hold entries (bits_of(),
 // from the lane's mask in LDS or registers) -- so the loads are in flight while the bits are formed
-template <int U, typename Bits>
+// S16 (a short wave, mph_params.h kOff16Bits): jj is the entry's offset from its group's base and
+// sb[u] row k0 + u's base scaled to the gather stride (GroupWalk; scalars), j0[u] the base itself
+template <int U, bool S16, typename Bits>
 __device__ __forceinline__ void list_batch(const NbrList& NL, Bits bits_of, int k0, int end,
-                                           bool (&ok)[U], int (&jj)[U], int (&TT)[U])
+                                           bool (&ok)[U], int (&jj)[U], int (&TT)[U], GroupWalk& W,
+                                           unsigned (&sb)[U], int (&j0)[U])
 {
     int e[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) nbr_at(NL, k0 + u < end ? k0 + u : end - 1, e[u], TT[u]);
+    for (int u = 0; u < U; ++u) {
+        if constexpr (S16) nbr_at16(NL, k0 + u < end ? k0 + u : end - 1, e[u], TT[u]);
+        else nbr_at(NL, k0 + u < end ? k0 + u : end - 1, e[u], TT[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if constexpr (S16) {
+            W.seek(k0 + u);
+            sb[u] = W.sb;
+            j0[u] = W.j0;
+        } else {
+            sb[u] = 0u;
+            j0[u] = 0;
+        }
+    }
     const unsigned bits = bits_of();
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -188,12 +205,12 @@ __device__ __forceinline__ void list_batch(const NbrList& NL, Bits bits_of, int 
     }
 }
 
-template <bool FAST, int DIM, bool EQR, bool LEAN, int U = MPH_UA>
+template <bool FAST, int DIM, bool EQR, bool LEAN, bool S16 = false, int U = MPH_UA>
 __device__ __forceinline__ void pass_a_loop(const DevParams& P, const double* s_ratio, const double* s_mu,
                                             const Soa& A,
                                             NbrList NL, bool plain, const unsigned* lm, int end, int ti,
                                             bool solid, double xi, double yi, double zi, double vxi, double vyi,
-                                            double vzi, PassA& o)
+                                            double vzi, PassA& o, GroupWalk W = GroupWalk{})
 {
     const __amdgpu_buffer_rsrc_t p6r = sized_rsrc(A.p6, (unsigned)P.n * 48u);
     for (int k0 = 0; k0 < end; k0 += U) {
@@ -201,13 +218,16 @@ __device__ __forceinline__ void pass_a_loop(const DevParams& P, const double* s_
         double X[U], Y[U], Z[U], VX[U], VY[U], VZ[U];
         int TT[U];
         bool ok[U];
-        list_batch<U>(NL, [&] { return plain ? bit_range(0, end - k0) : row_bits_lds(lm, k0, end); }, k0, end,
-                      ok, jj, TT);
+        unsigned sb[U];
+        int j0[U];
+        list_batch<U, S16>(NL, [&] { return plain ? bit_range(0, end - k0) : row_bits_lds(lm, k0, end); }, k0, end,
+                           ok, jj, TT, W, sb, j0);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             // a row without an entry of the lane (a gap, or past its end) reads past the buffer:
             // zeros, no cache lookup
-            const unsigned off = ok[u] ? (unsigned)jj[u] * 48u : kGatherOob;
+            // (S16: the offset within the group times the stride plus the group's scaled base, a scalar)
+            const unsigned off = ok[u] ? (S16 ? (unsigned)jj[u] * 48u + sb[u] : (unsigned)jj[u] * 48u) : kGatherOob;
             const double2 a = buf_ld16(p6r, off), b = buf_ld16(p6r, off + 16u), c = buf_ld16(p6r, off + 32u);
             X[u] = a.x; Y[u] = a.y; Z[u] = b.x;
             VX[u] = b.y; VY[u] = c.x; VZ[u] = c.y;
@@ -244,7 +264,8 @@ __global__ __launch_bounds__(MPH_LB) MPH_PA_ATTR void k_pass_a(DevParams P, cons
                                                 const unsigned long long* __restrict__ lhdr,
                                                 const unsigned long long* __restrict__ lgap, PassAOut pout,
                                                 const DevState* __restrict__ st,
-                                                unsigned char* __restrict__ cmap, int cmap_bytes)
+                                                unsigned char* __restrict__ cmap, int cmap_bytes,
+                                                const int* __restrict__ lbase)
 {
     const int n = dev_n(P);
     // counted like the lazy steps in the search (one writer; st is written by no other kernel of
@@ -290,14 +311,24 @@ __global__ __launch_bounds__(MPH_LB) MPH_PA_ATTR void k_pass_a(DevParams P, cons
     unsigned* lm = &s_mask[threadIdx.x >> 6][(threadIdx.x & 63) * kMaskWords];
     // a wave without jumps (plain rows: on the lattice, in 2-D) needs no mask, only its lanes' ends
     const unsigned long long hdr = wave_hdr(lhdr, i);
-    const bool plain = (hdr >> 56) == 0;
+    const bool plain = gap_count(hdr) == 0;
     if (!plain) mask_to_lds(lm, row_mask(hdr, lgap, i, end));   // (each lane reads back only its own)
     const NbrList NL = nbr_list(nbr, i);
     PassA o;
     // wave-uniform: equal radii (every BASELINE config) take the single-cutoff form of the sums in
     // the interior waves; waves at a periodic face keep the general form
     const bool eqr = pass_a_equal_radii(P);
-    if (fast && eqr)
+    // a short wave (interior, 3-D): the same loops over its 16-bit rows
+    if (DIM == 3 && hdr_short(hdr)) {
+        GroupWalk W;
+        W.init(lbase, i, hdr, 48);
+        if (eqr)
+            pass_a_loop<true, DIM, true, LEAN, true>(P, s_ratio, s_mu, A, NL, plain, lm, end, ti, solid, xi, yi, zi, vxi,
+                                                     vyi, vzi, o, W);
+        else
+            pass_a_loop<true, DIM, false, LEAN, true>(P, s_ratio, s_mu, A, NL, plain, lm, end, ti, solid, xi, yi, zi, vxi,
+                                                      vyi, vzi, o, W);
+    } else if (fast && eqr)
         pass_a_loop<true, DIM, true, LEAN>(P, s_ratio, s_mu, A, NL, plain, lm, end, ti, solid, xi, yi, zi, vxi, vyi,
                                            vzi, o);
     else if (fast)
@@ -374,13 +405,14 @@ __device__ __forceinline__ void pass_b_term(const DevParams& P, const double* s_
     f2 += c * q2;
 }
 
-template <bool FAST, bool SURF, int DIM, int U = MPH_UB>
+template <bool FAST, bool SURF, int DIM, bool S16 = false, int U = MPH_UB>
 __device__ __forceinline__ void pass_b_loop(const DevParams& P, const double* s_ratio,
                                             const double4* rec, const double* gx,
                                             const double* gy, const double* gz, const double* pa,
                                             NbrList NL, bool plain, const RowMask& M, int end, int ti, bool solid,
                                             double xi, double yi, double zi, double gxi, double gyi, double gzi,
-                                            double pai, double ai, double& f0, double& f1, double& f2)
+                                            double pai, double ai, double& f0, double& f1, double& f2,
+                                            GroupWalk W = GroupWalk{})
 {
     const double dscale = P.rg_r2g * (P.vol / P.dx);
     const double cpv = P.cdp * P.vol;
@@ -392,11 +424,13 @@ __device__ __forceinline__ void pass_b_loop(const DevParams& P, const double* s_
         double X[U], Y[U], Z[U], PJ[U];
         int TT[U];
         bool ok[U];
-        list_batch<U>(NL, [&] { return plain ? bit_range(0, end - k0) : row_bits(M, k0, end); }, k0, end, ok, jj,
-                      TT);
+        unsigned sb[U];
+        int j0[U];
+        list_batch<U, S16>(NL, [&] { return plain ? bit_range(0, end - k0) : row_bits(M, k0, end); }, k0, end, ok, jj,
+                           TT, W, sb, j0);
 #pragma unroll
         for (int u = 0; u < U; ++u) {   // (rows without an entry: past the buffer, as in pass_a_loop)
-            const unsigned off = ok[u] ? (unsigned)jj[u] * 16u : kGatherOob;
+            const unsigned off = ok[u] ? (S16 ? (unsigned)jj[u] * 16u + sb[u] : (unsigned)jj[u] * 16u) : kGatherOob;
             const double2 a = buf_ld16(recr, off), b = buf_ld16(recr, off == kGatherOob ? off : off + ps16);
             X[u] = a.x; Y[u] = a.y; Z[u] = b.x; PJ[u] = b.y;
         }
@@ -404,7 +438,7 @@ __device__ __forceinline__ void pass_b_loop(const DevParams& P, const double* s_
         for (int u = 0; u < U; ++u) {
             asm volatile("" ::"v"(X[u]), "v"(Y[u]), "v"(Z[u]), "v"(PJ[u]));   // (see pass_a_loop)
             if (!ok[u]) continue;
-            pass_b_term<FAST, SURF, DIM>(P, s_ratio, gx, gy, gz, pa, jj[u], TT[u], X[u], Y[u], Z[u], PJ[u], ti,
+            pass_b_term<FAST, SURF, DIM>(P, s_ratio, gx, gy, gz, pa, S16 ? jj[u] + j0[u] : jj[u], TT[u], X[u], Y[u], Z[u], PJ[u], ti,
                                          solid, xi, yi, zi, gxi, gyi, gzi, pai, ai, dscale, cpv, f0, f1, f2);
         }
     }
@@ -452,7 +486,8 @@ __global__ __launch_bounds__(MPH_LB) MPH_PB_ATTR void k_pass_b(DevParams P, cons
                                                 const unsigned long long* __restrict__ lgap,
                                                 double4* __restrict__ force, double4* __restrict__ acc,
                                                 Soa B, int phase, int* __restrict__ wface, StructHook H,
-                                                const DevState* __restrict__ st, KeyOut K)
+                                                const DevState* __restrict__ st, KeyOut K,
+                                                const int* __restrict__ lbase)
 {
     const int n = dev_n(P);
     const int lb = list_block(st, n);
@@ -500,10 +535,15 @@ __global__ __launch_bounds__(MPH_LB) MPH_PB_ATTR void k_pass_b(DevParams P, cons
     // on the steps that do not store it (force null, enqueue_step) its list loop is skipped
     const int end = !force && dev_is_wall(ti) ? 0 : (ncount[ir] < kTileRows ? ncount[ir] : kTileRows);
     const unsigned long long hdr = wave_hdr(lhdr, ir);
-    const bool plain = (hdr >> 56) == 0;   // no jumps: rows [0, end) (see k_pass_a)
+    const bool plain = gap_count(hdr) == 0;   // no gaps: rows [0, end) (see k_pass_a)
     const RowMask M = row_mask(hdr, lgap, ir, end);
     const NbrList NL = nbr_list(nbr, ir);
-    if (fast)
+    if (DIM == 3 && hdr_short(hdr)) {   // a short wave (interior): the same loop over its 16-bit rows
+        GroupWalk W;
+        W.init(lbase, ir, hdr, 16);
+        pass_b_loop<true, SURF, DIM, true>(P, s_ratio, rec, gx, gy, gz, pa, NL, plain, M, end, ti, solid, xi, yi, zi,
+                                           gxi, gyi, gzi, pai, ai, f0, f1, f2, W);
+    } else if (fast)
         pass_b_loop<true, SURF, DIM>(P, s_ratio, rec, gx, gy, gz, pa, NL, plain, M, end, ti, solid, xi, yi, zi, gxi,
                                      gyi, gzi, pai, ai, f0, f1, f2);
     else
@@ -601,7 +641,8 @@ __global__ __launch_bounds__(256) void k_virial(DevParams P, const DevTables* __
                                                 const int* __restrict__ ncount,
                                                 const unsigned long long* __restrict__ lhdr,
                                                 const unsigned long long* __restrict__ lgap,
-                                                double* __restrict__ vir, double* __restrict__ vpres)
+                                                double* __restrict__ vir, double* __restrict__ vpres,
+                                                const int* __restrict__ lbase)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= dev_n(P)) return;
@@ -616,12 +657,23 @@ __global__ __launch_bounds__(256) void k_virial(DevParams P, const DevTables* __
     const double cvis = DIM == 2 ? 8.0 : 10.0;
     double S[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
     const int end = ncount[i] < kTileRows ? ncount[i] : kTileRows;
-    const RowMask M = row_mask(lhdr[i >> 6], lgap, i, end);
+    const unsigned long long hdr = lhdr[i >> 6];
+    const RowMask M = row_mask(hdr, lgap, i, end);
     const int* row = ell_row(nbr, i);
+    const bool s16 = hdr_short(hdr);   // 16-bit rows: the entry's offset on its group's base
+    const unsigned short* row16 = reinterpret_cast<const unsigned short*>(nbr + (size_t)(i >> 6) * kTileStride);
     for (int k = 0; k < end; ++k) {
         if (!row_ok(M, k, end)) continue;
-        const int e = *ell_at(row, (int)(i & 63), k);
-        const int j = e & kIndexMask, tj = e >> kTypeShift;
+        int j, tj;
+        if (s16) {
+            const unsigned e = row16[ell_slot(k, (int)(i & 63))];
+            j = entry16_off(e) + lbase[(size_t)(i >> 6) * kBaseInts + row_group(hdr, k)];
+            tj = entry16_type(e);
+        } else {
+            const int e = *ell_at(row, (int)(i & 63), k);
+            j = e & kIndexMask;
+            tj = e >> kTypeShift;
+        }
         double q[3];
         q[0] = image_exact<false>(B.x[j] - xi, P.dw[0], P.hw[0], P.w075[0]);
         q[1] = image_exact<false>(B.y[j] - yi, P.dw[1], P.hw[1], P.w075[1]);
@@ -682,7 +734,7 @@ void launch_pass_a(const Launch& L)
         by_dim(P.dim, [&](auto D) {
             launch(L.prof, "pass_a", L.stream, k_pass_a<decltype(D)::value, decltype(LEAN)::value>,
                    dim3(list_grid(P.n, lazy_bal(L))), dim3(MPH_LB), P, L.T, L.A, L.nbr, L.ncount, L.lhdr, L.lgap,
-                   pass_a_out(L), L.st, lazy_cmap(L), L.cmap_bytes);
+                   pass_a_out(L), L.st, lazy_cmap(L), L.cmap_bytes, L.lbase);
         });
     });
 }
@@ -732,7 +784,7 @@ void launch_pass_b(const Launch& L, int phase)
                        k_pass_b<decltype(SURF)::value, decltype(D)::value, decltype(KEYS)::value>,
                        dim3(list_grid(P.n, lazy_bal(L))), dim3(MPH_LB), P, L.T, L.A, L.rec, L.fpart, L.gx, L.gy, L.gz,
                        L.pa, L.nbr, L.ncount, L.lhdr, L.lgap, L.force, L.acc, L.B, phase, L.wface, struct_hook(L),
-                       L.st, keys ? KeyOut{L.key, L.slot, L.cnt, L.cmap_next} : KeyOut{});
+                       L.st, keys ? KeyOut{L.key, L.slot, L.cnt, L.cmap_next} : KeyOut{}, L.lbase);
             });
         });
     });
@@ -744,7 +796,7 @@ void launch_virial(const Launch& L, const Soa& X, double* vir, double* vpres)
     if (P.n == 0) return;
     by_dim(P.dim, [&](auto D) {
         launch(L.prof, "virial", L.stream, k_virial<decltype(D)::value>, dim3(blocks(P.n, 256)), dim3(256), P, L.T,
-               L.A, X, L.pres, L.pa, L.gx, L.gy, L.gz, L.nbr, L.ncount, L.lhdr, L.lgap, vir, vpres);
+               L.A, X, L.pres, L.pa, L.gx, L.gy, L.gz, L.nbr, L.ncount, L.lhdr, L.lgap, vir, vpres, L.lbase);
     });
 }
 

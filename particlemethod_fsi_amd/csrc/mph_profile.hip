@@ -162,10 +162,12 @@ static int host_rows(MphCtx* c, HostRows& R)
     R.rows.resize(n);
     R.hdr.resize(ntile);
     R.gap.resize(ntile * kTile);
+    R.base.resize(ntile * kBaseInts);
     if (!n) return MPH_OK;
     MPH_HIP_OK(c, hipMemcpy(R.rows.data(), c->L.ncount, sizeof(int) * n, hipMemcpyDeviceToHost));
     MPH_HIP_OK(c, hipMemcpy(R.hdr.data(), c->L.lhdr, sizeof(R.hdr[0]) * ntile, hipMemcpyDeviceToHost));
     MPH_HIP_OK(c, hipMemcpy(R.gap.data(), c->L.lgap, sizeof(R.gap[0]) * n, hipMemcpyDeviceToHost));
+    MPH_HIP_OK(c, hipMemcpy(R.base.data(), c->L.lbase, sizeof(int) * R.base.size(), hipMemcpyDeviceToHost));
     return MPH_OK;
 }
 
@@ -193,7 +195,15 @@ int mph_list_layout(MphCtx* c, long long out[6])
     const long long waves = ((long long)n + kTile - 1) / kTile;
     long long jumped = 0, jumps = 0, max_jumps = 0, gap_rows = 0, max_rows = 0;
     for (long long t = 0; t < waves; ++t) {
-        const int J = jump_count(R.hdr[t]);
+        // the jumps that left a gap in some lane: every jump of a wide wave; of a short wave, which
+        // jumps at every group end, only those (so the counts compare with MPH_LIST16=0)
+        int J = 0;
+        for (int k = 0; k < gap_count(R.hdr[t]); ++k) {
+            bool gap = false;
+            for (long long s = t * kTile; s < std::min<long long>(n, (t + 1) * kTile) && !gap; ++s)
+                gap = gap_begin(R.gap[s], k) < std::min(gap_end(R.hdr[t], k), std::min(R.rows[s], kTileRows));
+            J += gap;
+        }
         jumped += J > 0;
         jumps += J;
         max_jumps = std::max<long long>(max_jumps, J);
@@ -250,6 +260,34 @@ int mph_lean_step_stats(MphCtx* c, long long out[2])
     static_assert(offsetof(DevState, lean_pass_a_steps) == offsetof(DevState, lean_search_steps) + sizeof(long long),
                   "the two counters are read in one copy");
     return counter_pair(c, offsetof(DevState, lean_search_steps), out);
+}
+
+int mph_list_format_stats(MphCtx* c, long long out[3])
+{
+    MPH_CK(counters_enter(c, out));
+    // the header words of the last search: the waves' flags
+    const size_t ntile = ((size_t)c->n + kTile - 1) / kTile;
+    std::vector<unsigned long long> hdr(ntile);
+    if (ntile) MPH_HIP_OK(c, hipMemcpy(hdr.data(), c->L.lhdr, sizeof(hdr[0]) * ntile, hipMemcpyDeviceToHost));
+    out[0] = out[1] = out[2] = 0;
+    // (only the 3-D search chooses a format and keeps the restart byte)
+    for (unsigned long long h : hdr) {
+        const bool d3 = c->P.dim == 3;
+        out[d3 && hdr_short(h) ? 0 : 1] += 1;
+        out[2] += d3 && hdr_restarted(h);
+    }
+    return MPH_OK;
+}
+
+int mph_list_span_misses(MphCtx* c, long long* out)
+{
+    MPH_CK(counters_enter(c, out));
+    const size_t ntile = ((size_t)c->n + kTile - 1) / kTile;
+    std::vector<unsigned long long> hdr(ntile);
+    if (ntile) MPH_HIP_OK(c, hipMemcpy(hdr.data(), c->L.lhdr, sizeof(hdr[0]) * ntile, hipMemcpyDeviceToHost));
+    *out = 0;
+    for (unsigned long long h : hdr) *out += c->P.dim == 3 && !hdr_short(h) && hdr_span_miss(h);
+    return MPH_OK;
 }
 
 int mph_key_fold_stats(MphCtx* c, long long out[2])
@@ -309,8 +347,7 @@ int mph_neighbor_rows(MphCtx* c, int first, int count, int* counts, int* ids, lo
         int q = 0;
         for (int e = 0; e < rows; ++e) {
             if (!R.ok(s, e)) continue;   // a gap of the row jumps
-            const int v = buf[(size_t)ell_slot(e, s & 63)];
-            const int j = v & kIndexMask;
+            const int j = R.entry(s, e, buf.data());
             if (j >= n || q >= m) return ctx_fail(c, MPH_ERR_HIP, "mph_neighbor_rows: list entry past the particle count");
             ids[w + q++] = id[j];
         }

@@ -41,6 +41,11 @@ __device__ __forceinline__ void start_landed(int& a, int& b) { asm volatile("" :
 __host__ __device__ constexpr int stage_d(int cap, int sb) { return (cap + sb + 2 + 1) & ~1; }
 __host__ __device__ constexpr int stage_t(int cap, int sb) { return (cap + sb + 8 + 3) & ~3; }
 __host__ __device__ constexpr int stage_words(int cap, int sb) { return 3 * stage_d(cap, sb) + stage_t(cap, sb) / 2; }
+// the group bases of a wave with 16-bit rows (3-D kernels; wave_list16): kBaseInts ints behind the staging area
+__device__ __forceinline__ int* stage_bases(double* stage)
+{
+    return reinterpret_cast<int*>(stage + stage_words(MPH_LDS_CAP, MPH_SB));
+}
 
 
 // Logical axes of the cell order for the search: the two column axes (A0 slowest, A1) and the
@@ -207,12 +212,26 @@ __device__ __forceinline__ int scan_candidates(const DevParams& P, const Soa& A,
 // rows; the return value counts the stored entries.  (A window that only the wider ranges push past
 // the staging area takes the gather loop in the full form alone, which then also stores the
 // shell's pairs: more rows, the same entries within the passes' radii in the same order.)
-template <int DIM, int PERM, bool LEAN, int SB = MPH_SB, int CAP = MPH_LDS_CAP>
+//
+// S16 (3-D; the caller has found every stencil group's candidates within DevParams.list16_span
+// indices of the group's base, sbase[group], in the wave's LDS): the wave's rows are 16-bit ones
+// (mph_params.h kOff16Bits).  A column's range, its window and the candidate loop run on indices
+// relative to the group's base (subtracted once per column), so an entry is formed by the one
+// instruction it costs in the wide format, and every group end is a jump -- taken whether or not
+// the lanes' rows differ -- so that each group starts on a wave-uniform row (header byte g - 1)
+// and the passes decode a row with one scalar base.  Returns -1, wave-uniformly, when the wave's
+// highest row has reached kAlignRows at a group end (a very dense cluster) or a column's window
+// does not fit the staging area: the caller then runs the wide form from column 0 over the same
+// tile (restarted).
+template <int DIM, int PERM, bool LEAN, bool S16, int SB = MPH_SB, int CAP = MPH_LDS_CAP>
 __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa& A, const int* start,
                                                    int i, bool act, double xi, double yi, double zi,
                                                    int cx, int cy, int cz, int* out, double* sx, int* stored,
                                                    unsigned long long* lgap, unsigned long long* lhdr)
 {
+    // S16: the groups' bases, behind the wave's staging area (stage_bases)
+    const int* sbase = reinterpret_cast<const int*>(sx + stage_words(CAP, SB));
+    static_assert(!S16 || DIM == 3, "the 16-bit rows are the 3-D search's");
     // the staging area holds the window's 16-byte FP32 records, SB past the window's end
     constexpr int kCap32 = stage_words(CAP, SB) / 2 - SB - 1;
     const int lane = threadIdx.x & 63;
@@ -222,8 +241,16 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
     const unsigned tlo = __builtin_amdgcn_readfirstlane((unsigned)tb);
     const unsigned thi = __builtin_amdgcn_readfirstlane((unsigned)(tb >> 32));
     const __amdgpu_buffer_rsrc_t tile_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<void*>(((unsigned long long)thi << 32) | tlo), 0, kTile * kTileRows * (int)sizeof(int),
-        0x00020000);
+        reinterpret_cast<void*>(((unsigned long long)thi << 32) | tlo), 0,
+        kTile * kTileRows * (int)(S16 ? sizeof(short) : sizeof(int)), 0x00020000);
+    // the entry of candidate j (S16: relative to the group's base) and its store
+    auto put = [&](int j, int type, int off) {
+        if constexpr (S16)
+            __builtin_amdgcn_raw_buffer_store_b16((short)(j | (type << kOff16Bits)), tile_rsrc, off, 0, 0);
+        else
+            __builtin_amdgcn_raw_buffer_store_b32(nbr_entry(j, type), tile_rsrc, off, 0, 0);
+    };
+    constexpr int kListKeep = soff_keep(S16);
     const double lo2 = P.rc2_lo, hi2 = P.rc2_hi;
     using X = CellAxes<DIM, PERM>;
     constexpr int NCOL = DIM == 3 ? kGroups * kGroups : kGroups;
@@ -294,11 +321,13 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
         // a lane without candidates reads start[0] twice (empty range)
         start_load2(srs, ok ? (unsigned)(b + lo) * 4u : 0u, ok ? (unsigned)(b + hi + 1) * 4u : 0u, jb, je);
     };
-    // the lane's next list slot: soff = stored * 256 + lane * 4 (one add per entry, no address
-    // arithmetic); bits 18 and up count every accepted neighbour (NeighborCount), bits 8-17 the
-    // stored ones (the FP32 path keeps only r^2 <= P.rlf: kListTotal, kListKeep), so the store
-    // offset is soff & kSoffMask
-    int soff = lane << 2;
+    // the lane's next list slot (mph_params.h soff_*): soff = stored * 256 + lane * 4 (S16: * 128,
+    // * 2; one add per entry, no address arithmetic); bits 18 and up count every accepted neighbour
+    // (NeighborCount), the bits below them the stored ones (the FP32 path keeps only r^2 <= P.rlf:
+    // kListTotal, kListKeep), so the store offset is soff & kSoffMask
+    int soff = soff_first(S16, lane);
+    // S16: bit 8 of `jumps` is set once a lane's row differed from the wave's at a group end
+    constexpr int kGapsBit = 0x100;
     // Row jumps (aligned rows, see RowMask): at the end of a stencil group (3-D: the 7 columns of
     // one slowest-axis offset; 2-D: a column) the lanes' next rows move on to the wave's highest
     // row, so the next group's entries start on one row for all lanes however far their counts
@@ -320,36 +349,71 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
         asm volatile("" : "+v"(ii));
         return reinterpret_cast<unsigned char*>(lhdr + __builtin_amdgcn_readfirstlane(ii >> 6)) + k;
     };
+    // (true: a short wave starts over in the wide format)
     auto group_end = [&]() {
-        if (jumps >= kMaxJumps) return;
-        const int row = soff_stored(soff);
+        if (!S16 && jumps >= kMaxJumps) return false;
+        const int row = soff_stored(S16, soff);
         const int m = __builtin_amdgcn_readfirstlane(wave_max(row));
         if (m >= kAlignRows) {
+            if (S16) return true;
             jumps += kMaxJumps + 1;   // no more jumps
-            return;
+            return false;
         }
-        if (kAlignDrift <= 1) {
-            if (!__ballot(act && row != m)) return;   // the rows agree
+        if (S16) {
+            // The lanes' gap bytes are stored from the wave's first real gap on: until a lane's row
+            // differs from the wave's nothing reads them (kHdrNoGap), and the wave that first differs
+            // at jump k stores the whole gap word, the bytes of the jumps before it 0xff -- an empty
+            // gap [255, header byte), which the row masks and the host readers take as none.
+            const int k = jumps & (kGapsBit - 1);
+            if (!(jumps & kGapsBit)) {
+                if (__ballot(act && row != m)) {
+                    int ii = i;
+                    asm volatile("" : "+v"(ii));
+                    lgap[ii] = ((unsigned long long)(unsigned)row << (8 * k)) | ~(~0ull << (8 * k));
+                    jumps |= kGapsBit;
+                }
+            } else {
+                int ii = i;
+                asm volatile("" : "+v"(ii));
+                reinterpret_cast<unsigned char*>(lgap + ii)[k] = (unsigned char)row;
+            }
+            if (lane == 0) *hdr_byte(k) = (unsigned char)m;
+            soff += (m - row) << soff_row_shift(S16);
+            ++jumps;
+            return false;
+        } else if (kAlignDrift <= 1) {
+            if (!__ballot(act && row != m)) return false;   // the rows agree
         } else {
             const int mn = __builtin_amdgcn_readfirstlane(wave_min(act ? row : m));
-            if (m - mn < kAlignDrift) return;
+            if (m - mn < kAlignDrift) return false;
         }
         // the address formed here, not hoisted out of the column loop as a register pair
         int ii = i;
         asm volatile("" : "+v"(ii));
         reinterpret_cast<unsigned char*>(lgap + ii)[jumps] = (unsigned char)row;   // the lane's gap [row, m)
         if (lane == 0) *hdr_byte(jumps) = (unsigned char)m;
-        soff += (m - row) << 8;
+        soff += (m - row) << soff_row_shift(S16);
         ++jumps;
+        return false;
     };
     constexpr int kSelfCol = DIM == 3 ? kReach * kGroups + kReach : kReach;   // the lane's own column
     // one stencil column: its range [jb, je) was loaded one column ahead; (nb_jb, nb_je) receive
     // column col + 1's.  The loop below is unrolled by two with the roles of the two register pairs
     // swapped, so no copy at the loop latch waits for the loads in flight.
+    int gb = 0;   // S16: the current group's base
+    // (true: group_end's)
     auto column = [&](int col, int jb, int je, int& nb_jb, int& nb_je) {
         start_landed(jb, je);   // loaded one column ahead; every path below ended in vmcnt(0)
-        if (col > 0 && col % GSZ == 0) group_end();
+        if (col > 0 && col % GSZ == 0)
+            if (group_end()) return true;   // (no start[] load is in flight here)
         if (col + 1 < NCOL) col_range(col + 1, nb_jb, nb_je);
+        // S16: the group's base gb (read at the group's first column, one scalar held through the
+        // group); everything below on indices relative to it
+        if constexpr (S16) {
+            if (col % GSZ == 0) gb = __builtin_amdgcn_readfirstlane(sbase[col / GSZ]);
+            jb -= gb;
+            je -= gb;
+        }
         const bool any = je > jb;
         // the wave's window [mn, mx): the lanes are in cell order, so the first lane with candidates
         // normally has the lowest jb and the last the highest je -- read those two lanes, and take
@@ -360,7 +424,7 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
             // has them landed and its first use needs no wait (which would also wait for this
             // column's list stores: loads and stores share vmcnt)
             __builtin_amdgcn_s_waitcnt(0x0F70);
-            return;
+            return false;
         }
         int mn = __builtin_amdgcn_readlane(jb, __ffsll((long long)am) - 1);
         int mx = __builtin_amdgcn_readlane(je, 63 - __clzll(am));
@@ -404,16 +468,17 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
             // FP32 records: candidate j at record j - lbase, 64 records (1 KB) per instruction
             float4* s4 = reinterpret_cast<float4*>(sx);
             for (int p = 0; p * 64 < n1; ++p)   // wave-uniform
-                if (p * 64 + lane < n1) __builtin_amdgcn_global_load_lds(A.f4 + mn + p * 64 + lane, s4 + p * 64, 16, 0, 0);
+                if (p * 64 + lane < n1) __builtin_amdgcn_global_load_lds(A.f4 + gb + mn + p * 64 + lane, s4 + p * 64, 16, 0, 0);
             for (int p = 0; p * 64 < n2; ++p)   // the second run (two), after the first
                 if (p * 64 + lane < n2)
-                    __builtin_amdgcn_global_load_lds(A.f4 + m2 + p * 64 + lane, s4 + n1 + p * 64, 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds(A.f4 + gb + m2 + p * 64 + lane, s4 + n1 + p * 64, 16, 0, 0);
             __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the records (and column col + 1's start[]) landed
             __builtin_amdgcn_wave_barrier();
             const float xf = (float)(xi - P.cref[0]), yf = (float)(yi - P.cref[1]), zf = (float)(zi - P.cref[2]);
             const float lof = P.rc2f_lo, hif = P.rc2f_hi;
             auto test32 = [&](auto self_tag) {
                 constexpr bool SELF = decltype(self_tag)::value;
+                const int self = SELF ? i - gb : 0;
                 for (int j0 = jb; j0 < je; j0 += SB) {
                     float4 r[SB];
 #pragma unroll
@@ -425,11 +490,10 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
                         const float r2f = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
                         bool live = true;
                         if (u > 0) live = j < je;
-                        if (SELF) live = live & (j != i);
+                        if (SELF) live = live & (j != self);
                         if constexpr (LEAN) {
                             if (live & (r2f <= P.rlf)) {
-                                __builtin_amdgcn_raw_buffer_store_b32(nbr_entry(j, __float_as_int(r[u].w)), tile_rsrc,
-                                                                      soff & kSoffMask, 0, 0);
+                                put(j, __float_as_int(r[u].w), soff & kSoffMask);
                                 soff += kListKeep;
                             }
                             continue;
@@ -446,7 +510,8 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
                             if (__builtin_amdgcn_inverse_ballot_w64(mband)) {
                                 // the index hidden from the loop's induction analysis, so the addresses
                                 // are formed here and not carried through the loop
-                                int jj = j;
+                                // (S16: the base read again here, not held through the loop)
+                                int jj = S16 ? j + sbase[col / GSZ] : j;
                                 asm volatile("" : "+v"(jj));
                                 const double ddx = A.x[jj] - xi, ddy = A.y[jj] - yi, ddz = A.z[jj] - zi;
                                 const double r2a = fma(ddx, ddx, fma(ddy, ddy, ddz * ddz));
@@ -459,9 +524,7 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
                             // stored when within the passes' largest radius (FP32, an upper bound:
                             // the passes' own exact tests decide); counted always
                             const bool keep = r2f <= P.rlf;
-                            if (keep)
-                                __builtin_amdgcn_raw_buffer_store_b32(nbr_entry(j, __float_as_int(r[u].w)), tile_rsrc,
-                                                                      soff & kSoffMask, 0, 0);
+                            if (keep) put(j, __float_as_int(r[u].w), soff & kSoffMask);
                             soff += keep ? kListKeep : kListTotal;
                         }
                     }
@@ -470,6 +533,11 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
             if (col == kSelfCol) test32(std::true_type{});
             else test32(std::false_type{});
             __builtin_amdgcn_wave_barrier();   // every lane done reading before the next staging
+        } else if constexpr (S16) {
+            // a window wider than the staging area (rare): the wave starts over in the wide format,
+            // whose gather loop takes it
+            __builtin_amdgcn_s_waitcnt(0x0F70);   // column col + 1's start[] loads
+            return true;
         } else {
             // a window wider than the staging area: per-lane gathers, every accepted pair stored
             for (int j0 = jb; j0 < je; j0 += SB) {
@@ -485,7 +553,7 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
                 for (int u = 0; u < SB; ++u) {
                     const int j = j0 + u;
                     if (accept_interior(P, xs[u] - xi, ys[u] - yi, zs[u] - zi, lo2, hi2) && j < je && j != i) {
-                        const int row = soff_stored(soff);
+                        const int row = soff_stored(S16, soff);
                         if (soff_total(soff) < kMaxNeighbor && row < kTileRows)
                             out[(size_t)row * kTile] = nbr_entry(j, A.type[j]);
                         soff += kListKeep;
@@ -494,16 +562,27 @@ __device__ __forceinline__ int scan_candidates_lds(const DevParams& P, const Soa
             }
             __builtin_amdgcn_s_waitcnt(0x0F70);   // column col + 1's start[] loads (wide windows are rare)
         }
+        return false;
     };
     int ra_b, ra_e, rb_b = 0, rb_e = 0;   // the two register pairs of the column ranges
     col_range(0, ra_b, ra_e);
     __builtin_amdgcn_s_waitcnt(0x0F70);
     for (int col = 0; col < NCOL; col += 2) {
-        column(col, ra_b, ra_e, rb_b, rb_e);
-        if (col + 1 < NCOL) column(col + 1, rb_b, rb_e, ra_b, ra_e);
+        bool again = column(col, ra_b, ra_e, rb_b, rb_e);
+        if (!again && col + 1 < NCOL) again = column(col + 1, rb_b, rb_e, ra_b, ra_e);
+        if (S16 && again) {
+            if (lane == 0) *hdr_byte(kHdrRestartByte) = 1;
+            __builtin_amdgcn_s_waitcnt(0x0F70);   // the 16-bit stores done before the wide ones over them
+            return -1;
+        }
     }
-    *stored = soff_stored(soff);  // the list's rows, gaps included (entries: r^2 <= P.rlf)
-    if (lane == 0) *hdr_byte(7) = (unsigned char)(jumps > kMaxJumps ? jumps - kMaxJumps - 1 : jumps);
+    *stored = soff_stored(S16, soff);  // the list's rows, gaps included (entries: r^2 <= P.rlf)
+    // header byte 7: the jumps and the wave's flags (mph_params.h kHdrShort)
+    if (S16) {
+        if (lane == 0) *hdr_byte(7) = (unsigned char)(kMaxJumps | kHdrShort | (jumps & kGapsBit ? 0u : kHdrNoGap));
+    } else {
+        if (lane == 0) *hdr_byte(7) = (unsigned char)(jumps > kMaxJumps ? jumps - kMaxJumps - 1 : jumps);
+    }
     return soff_total(soff);      // every neighbour (NeighborCount; LEAN: the stored entries)
 }
 
@@ -580,6 +659,45 @@ __device__ __forceinline__ bool wave_idle_walls(const DevParams& P, const Soa& A
     return true;
 }
 
+// The format of an interior 3-D wave's rows, decided before its first store: for each stencil group
+// (slowest-axis offset g - kReach) every index a lane can store lies in [start[lo_g], start[hi_g]),
+// the cell-order indices of the group's first cell seen from the wave's lowest cell and of the cell
+// past its last seen from the wave's highest (an interior wave's stencil wraps nowhere, so a cell's
+// index is the lane's own plus the stencil offset, and start[] is monotone).  Lane g loads the lower
+// bound and lane 8 + g the upper one, one load instruction for the wave; the wave is short when
+// every span is at most DevParams.list16_span, and then the lower bounds are the groups' bases:
+// sbase (the wave's LDS, for its search) and lbase (the passes').
+template <int PERM>
+__device__ __forceinline__ bool wave_list16(const DevParams& P, const int* start, bool own, int cx, int cy, int cz,
+                                            int tile, int* sbase, int* lbase, unsigned long long* lhdr)
+{
+    using X = CellAxes<3, PERM>;
+    if (P.list16_span <= 0 || !__ballot(own)) return false;   // wave-uniform
+    const int cc[3] = {cx, cy, cz};
+    const int g1 = P.gc[X::A1], g2 = P.gc[X::A2];
+    const int lin = (cc[X::A0] * g1 + cc[X::A1]) * g2 + cc[X::A2];
+    const int lmin = __builtin_amdgcn_readfirstlane(wave_min(own ? lin : 0x7fffffff));
+    const int lmax = __builtin_amdgcn_readfirstlane(wave_max(own ? lin : -1));
+    const int lane = threadIdx.x & 63;
+    const int g = lane & 7, dg = g - kReach;
+    const bool hi = lane >= 8;
+    int idx = hi ? lmax + (dg * g1 + kReach) * g2 + P.sa + 1 : lmin + (dg * g1 - kReach) * g2 - P.sa;
+    idx = min(max(idx, 0), P.ncell);   // (an interior wave's are inside; start[] has ncell + 1 entries)
+    const int v = lane < 16 && g < kGroups ? start[idx] : 0;
+    const int span = __shfl_down(v, 8, 64) - v;
+    if (__ballot(lane < kGroups && (span < 0 || span > P.list16_span))) {
+        // (counted apart from the waves that never decide: mph_list_span_misses)
+        if (lane == 0) reinterpret_cast<unsigned char*>(lhdr + tile)[kHdrRestartByte] = kHdrSpanMiss;
+        return false;
+    }
+    if (lane < kGroups) {
+        sbase[lane] = v;
+        lbase[(size_t)tile * kBaseInts + lane] = v;
+    }
+    __builtin_amdgcn_wave_barrier();
+    return true;
+}
+
 // ncount: the rows of each particle's stored list, gaps included (what the passes walk; the
 // entries, r^2 <= P.rlf, are the rows outside the gaps, RowMask); nbcount: NeighborCount, every
 // neighbour within the search radius; lhdr / lgap: the row jumps (RowMask)
@@ -588,7 +706,8 @@ __device__ __forceinline__ bool wave_idle_walls(const DevParams& P, const Soa& A
 template <int DIM, int PERM, bool LEAN>
 __device__ __forceinline__ int neighbors_body(const DevParams& P, const Soa& A, const int* start, int* nbr,
                                                int* ncount, int* nbcount, unsigned long long* lhdr,
-                                               unsigned long long* lgap, DevState* st, double* stage, int i)
+                                               unsigned long long* lgap, DevState* st, double* stage, int i,
+                                               int* lbase)
 {
     const int n = dev_n(P);
     const bool live = i < n;
@@ -611,13 +730,41 @@ __device__ __forceinline__ int neighbors_body(const DevParams& P, const Soa& A, 
     const int cx = cell_axis(xi, P.corg[0], P.dw[0], P.ginv[0], P.gc[0]);
     const int cy = cell_axis(yi, P.corg[1], P.dw[1], P.ginv[1], P.gc[1]);
     const int cz = DIM == 3 ? cell_axis(zi, P.corg[2], P.dw[2], P.ginv[2], P.gc[2]) : 0;
-    int* out = nbr + (size_t)(i >> 6) * kTileStride + (i & 63);
+    // the lane's column of its wave's tile (formed where it is used: no register holds it across
+    // the format decision or the short form)
+    auto tile_out = [&](int iv) { return nbr + (size_t)(iv >> 6) * kTileStride + (iv & 63); };
     if (fast) {
-        cnt = scan_candidates_lds<DIM, PERM, LEAN>(P, A, start, i, own, xi, yi, zi, cx, cy, cz, out, stage, &stored,
-                                             lgap, lhdr);
+        // 16-bit rows where the wave's spans allow (3-D); a short wave that runs out of aligned rows
+        // starts over in the wide format
+        bool s16 = false;
+        if constexpr (DIM == 3) {
+            // (header byte kHdrRestartByte: cleared here, set by a short wave that starts over)
+            if ((threadIdx.x & 63) == 0) reinterpret_cast<unsigned char*>(lhdr + tile)[kHdrRestartByte] = 0;
+            s16 = wave_list16<PERM>(P, start, own, cx, cy, cz, tile, stage_bases(stage), lbase, lhdr);
+            cnt = -1;
+            if (s16) {
+                int is = i;
+                asm volatile("" : "+v"(is));
+                cnt = scan_candidates_lds<DIM, PERM, LEAN, true>(P, A, start, i, own, xi, yi, zi, cx, cy, cz,
+                                                                 tile_out(is), stage, &stored, lgap, lhdr);
+            }
+        }
+        if (DIM != 3 || cnt < 0) {
+            // (3-D: the cells and the tile pointer are formed again from the position and the index,
+            // so that the short form holds no register for a restart)
+            double xw = xi, yw = yi, zw = zi;
+            int iw = i;
+            int g0 = P.gc[0], g1 = P.gc[1], g2 = P.gc[2];   // (likewise what cell_axis derives from them)
+            if (DIM == 3) asm volatile("" : "+v"(xw), "+v"(yw), "+v"(zw), "+v"(iw), "+s"(g0), "+s"(g1), "+s"(g2));
+            const int cxw = DIM == 3 ? cell_axis(xw, P.corg[0], P.dw[0], P.ginv[0], g0) : cx;
+            const int cyw = DIM == 3 ? cell_axis(yw, P.corg[1], P.dw[1], P.ginv[1], g1) : cy;
+            const int czw = DIM == 3 ? cell_axis(zw, P.corg[2], P.dw[2], P.ginv[2], g2) : 0;
+            cnt = scan_candidates_lds<DIM, PERM, LEAN, false>(P, A, start, i, own, xw, yw, zw, cxw, cyw, czw,
+                                                              tile_out(iw), stage, &stored, lgap, lhdr);
+        }
     } else {
         if (own)
-            cnt = scan_candidates<DIM, PERM>(P, A, start, i, xi, yi, zi, cx, cy, cz, out);
+            cnt = scan_candidates<DIM, PERM>(P, A, start, i, xi, yi, zi, cx, cy, cz, tile_out(i));
         stored = cnt;
         if ((threadIdx.x & 63) == 0) lhdr[tile] = 0;   // plain rows
     }
@@ -644,7 +791,8 @@ template <int DIM, int PERM, bool LAZY, bool LEAN = false>
 __global__ __launch_bounds__(MPH_LB) __attribute__((amdgpu_waves_per_eu(MPH_NB_WPE))) void k_neighbors(
     DevParams P, Soa A, const int* __restrict__ start, int* __restrict__ nbr, int* __restrict__ ncount,
     int* __restrict__ nbcount, unsigned long long* __restrict__ lhdr, unsigned long long* __restrict__ lgap,
-    DevState* __restrict__ st, int* __restrict__ wface, int bal, const unsigned char* __restrict__ cmap_arg)
+    DevState* __restrict__ st, int* __restrict__ wface, int bal, const unsigned char* __restrict__ cmap_arg,
+    int* __restrict__ lbase)
 {
     const unsigned char* cmap = LAZY ? cmap_arg : nullptr;
     const int n = dev_n(P);
@@ -663,14 +811,17 @@ __global__ __launch_bounds__(MPH_LB) __attribute__((amdgpu_waves_per_eu(MPH_NB_W
         if ((int)blockIdx.x >= list_blocks(n)) return;
         tb = xcd_block(blockIdx.x, list_blocks(n));
     }
-    __shared__ __attribute__((aligned(16))) double stage[kWB][stage_words(MPH_LDS_CAP, MPH_SB)];
+    // (3-D: a short wave's group bases behind its staging area, stage_bases: 32 bytes per wave,
+    // inside what the staging areas leave of a CU's LDS at 8 waves per SIMD)
+    __shared__ __attribute__((aligned(16))) double stage[kWB][stage_words(MPH_LDS_CAP, MPH_SB) +
+                                                              (DIM == 3 ? kBaseInts / 2 : 0)];
     const int i = tb * blockDim.x + threadIdx.x;
     slab_wave_flag(P, A, i, n, wface);
     // a lazy wall step (cmap set): an idle wave of walls only adds its fixed costs to the histograms
     const bool idle = cmap && wave_idle_walls<DIM, LEAN>(P, A, cmap, st, ncount, nbcount, lhdr, i, n);
     const int cnt = idle ? 0
                          : neighbors_body<DIM, PERM, LEAN>(P, A, start, nbr, ncount, nbcount, lhdr, lgap, st,
-                                                     stage[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)], i);
+                                                     stage[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)], i, lbase);
     if (bal) {
         if (cmap) add_wave_work(st->seg_lwork, cnt, i, n, st->seg_swork, idle);
         else add_wave_work(st->seg_work, cnt, i, n);
@@ -696,7 +847,7 @@ void launch_neighbors(const Launch& L)
                                k_neighbors<DIM, decltype(PERM)::value, decltype(LAZY)::value, decltype(LEAN)::value>,
                                dim3(lazy_bal(L) ? list_grid(P.n, true) : blocks(P.n, MPH_LB)), dim3(MPH_LB), P, L.A,
                                L.start, L.nbr, L.ncount, L.nbcount, L.lhdr, L.lgap, L.st, L.wface, (int)xcd_bal(L),
-                               lazy_cmap(L));
+                               lazy_cmap(L), L.lbase);
                 });
             });
         };

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
     "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
     "mph_lean_step_stats", "mph_key_fold_stats", "mph_gauge_configure", "mph_gauge_grid",
+    "mph_list_format_stats", "mph_list_span_misses",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -254,6 +255,8 @@ def load_library() -> ctypes.CDLL:
         "mph_idle_wall_stats": (ip, [vp, vp]),
         "mph_lean_step_stats": (ip, [vp, vp]),
         "mph_key_fold_stats": (ip, [vp, vp]),
+        "mph_list_format_stats": (ip, [vp, vp]),
+        "mph_list_span_misses": (ip, [vp, vp]),
         "mph_gauge_configure": (ip, [vp, ctypes.POINTER(MphGaugeConfig)]),
         "mph_gauge_grid": (ip, [vp, ctypes.POINTER(MphGaugeGrid), vp]),
     }
@@ -262,7 +265,8 @@ def load_library() -> ctypes.CDLL:
                 "mph_dist_overlap", "mph_profile_graphs", "mph_list_stats", "mph_list_layout",
                 "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
                 "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
-                "mph_lean_step_stats", "mph_key_fold_stats", "mph_gauge_configure", "mph_gauge_grid"}
+                "mph_lean_step_stats", "mph_key_fold_stats", "mph_gauge_configure", "mph_gauge_grid",
+                "mph_list_format_stats", "mph_list_span_misses"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -737,6 +741,22 @@ class MphSolver:
         ("prep_launches"); the first 0 with structure particles, monitors, in slab mode or with
         MPH_KEY_FOLD=0 at creation, both 0 from a library built before the entry point."""
         return self._counter_pair("mph_key_fold_stats", ("folded_steps", "prep_launches"))
+
+    def list_format_stats(self) -> dict:
+        """The list formats of the last search (mph_list_format_stats): the waves with 16-bit rows
+        ("short_waves"), those with 32-bit rows ("wide_waves") and, among the latter, the waves that
+        began in the 16-bit format and started over ("restarted_waves"); zeros from a library built
+        before the entry point."""
+        a = np.zeros(3, np.int64)
+        if hasattr(self._L, "mph_list_format_stats"):
+            _check(self._L.mph_list_format_stats(self._h, a.ctypes.data), self._h)
+        out = {k: int(v) for k, v in zip(("short_waves", "wide_waves", "restarted_waves"), a)}
+        # of the wide waves, the interior ones the span limit alone turned away (mph_list_span_misses)
+        m = np.zeros(1, np.int64)
+        if hasattr(self._L, "mph_list_span_misses"):
+            _check(self._L.mph_list_span_misses(self._h, m.ctypes.data), self._h)
+        out["span_miss_waves"] = int(m[0])
+        return out
 
     def neighbor_rows(self, first: int = 0, count: int | None = None):
         """(counts, offsets, ids): the neighbour sets of the particles [first, first + count) from
