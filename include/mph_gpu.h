@@ -632,6 +632,13 @@ int mph_list_format_stats(MphCtx* ctx, long long out3[3]);
  * by the span limit alone (the others are waves at periodic faces, idle wall waves, ghosts,
  * restarted waves): *out.  A flush point.  Additive: no change of MPH_ABI_VERSION.               */
 int mph_list_span_misses(MphCtx* ctx, long long* out);
+/* The same decision wave by wave, for verification: out holds 8 ints per wave (tile of 64 particles
+ * in the last search's sorted order; mph_list_layout's out6[0] waves).  out[8 w] = 0: the wave
+ * never decided (at a periodic face, idle walls, ghosts, 2-D, slab mode, MPH_LIST16=0), 1: 16-bit
+ * rows, 2: it began in the 16-bit format and started over, 3: turned away by the span limit.
+ * out[8 w + 1 .. 8 w + 7] = the seven group bases of a wave with 16-bit rows (sorted indices), else
+ * 0.  Read-only, reduced on the host.  A flush point.  Additive: no change of MPH_ABI_VERSION.   */
+int mph_list_wave_formats(MphCtx* ctx, int* out);
 /* The neighbour lists of calculateNeighbor themselves (main.cpp:1764-1772: Neighbor[i][k] = j for
  * k < 512), for verification: the sets of the `count` particles [first, first + count) (original
  * order) from the last search, each row as ascending original indices (the reference's rows are in

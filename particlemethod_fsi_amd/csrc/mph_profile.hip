@@ -1,7 +1,7 @@
 // mph_profile.hip -- measurement and diagnostics of a context: the per-kernel profilers
 // (mph_profile_steps, mph_profile_graphs) and the list and counter readers (mph_neighbor_stats,
 // mph_list_stats, mph_list_layout, mph_idle_wall_stats, mph_lean_step_stats, mph_key_fold_stats,
-// mph_neighbor_rows).
+// mph_list_format_stats, mph_list_span_misses, mph_list_wave_formats, mph_neighbor_rows).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -287,6 +287,31 @@ int mph_list_span_misses(MphCtx* c, long long* out)
     if (ntile) MPH_HIP_OK(c, hipMemcpy(hdr.data(), c->L.lhdr, sizeof(hdr[0]) * ntile, hipMemcpyDeviceToHost));
     *out = 0;
     for (unsigned long long h : hdr) *out += c->P.dim == 3 && !hdr_short(h) && hdr_span_miss(h);
+    return MPH_OK;
+}
+
+int mph_list_wave_formats(MphCtx* c, int* out)
+{
+    if (!out) return MPH_ERR_ARG;
+    MPH_CK(ctx_enter(c));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    // the header words and the group bases of the last search, wave by wave
+    const size_t ntile = ((size_t)c->n + kTile - 1) / kTile;
+    std::vector<unsigned long long> hdr(ntile);
+    std::vector<int> base(ntile * kBaseInts);
+    if (ntile) {
+        MPH_HIP_OK(c, hipMemcpy(hdr.data(), c->L.lhdr, sizeof(hdr[0]) * ntile, hipMemcpyDeviceToHost));
+        MPH_HIP_OK(c, hipMemcpy(base.data(), c->L.lbase, sizeof(int) * base.size(), hipMemcpyDeviceToHost));
+    }
+    static_assert(kGroups < kBaseInts && kBaseInts == 8, "a wave's record: the format and its kGroups bases");
+    for (size_t t = 0; t < ntile; ++t) {
+        int* o = out + t * kBaseInts;
+        const unsigned long long h = hdr[t];
+        // (only the 3-D search chooses a format and keeps the restart byte)
+        const bool d3 = c->P.dim == 3;
+        o[0] = !d3 ? 0 : hdr_short(h) ? 1 : hdr_restarted(h) ? 2 : hdr_span_miss(h) ? 3 : 0;
+        for (int g = 0; g < kGroups; ++g) o[1 + g] = o[0] == 1 ? base[t * kBaseInts + g] : 0;
+    }
     return MPH_OK;
 }
 

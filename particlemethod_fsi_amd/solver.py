@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = [
     "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
     "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
     "mph_lean_step_stats", "mph_key_fold_stats", "mph_gauge_configure", "mph_gauge_grid",
-    "mph_list_format_stats", "mph_list_span_misses",
+    "mph_list_format_stats", "mph_list_span_misses", "mph_list_wave_formats",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -257,6 +257,7 @@ def load_library() -> ctypes.CDLL:
         "mph_key_fold_stats": (ip, [vp, vp]),
         "mph_list_format_stats": (ip, [vp, vp]),
         "mph_list_span_misses": (ip, [vp, vp]),
+        "mph_list_wave_formats": (ip, [vp, vp]),
         "mph_gauge_configure": (ip, [vp, ctypes.POINTER(MphGaugeConfig)]),
         "mph_gauge_grid": (ip, [vp, ctypes.POINTER(MphGaugeGrid), vp]),
     }
@@ -266,7 +267,7 @@ def load_library() -> ctypes.CDLL:
                 "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
                 "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
                 "mph_lean_step_stats", "mph_key_fold_stats", "mph_gauge_configure", "mph_gauge_grid",
-                "mph_list_format_stats", "mph_list_span_misses"}
+                "mph_list_format_stats", "mph_list_span_misses", "mph_list_wave_formats"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -757,6 +758,15 @@ class MphSolver:
             _check(self._L.mph_list_span_misses(self._h, m.ctypes.data), self._h)
         out["span_miss_waves"] = int(m[0])
         return out
+
+    def list_wave_formats(self):
+        """The last search's format decision wave by wave (mph_list_wave_formats): (codes, bases), one
+        code per wave of 64 sorted particles -- 0 never decided, 1 16-bit rows, 2 began in the 16-bit
+        format and started over, 3 turned away by the span limit -- and the seven group bases of
+        every wave with 16-bit rows (zeros elsewhere)."""
+        a = np.zeros(((self.n + 63) // 64, 8), np.int32)
+        _check(self._L.mph_list_wave_formats(self._h, a.ctypes.data), self._h)
+        return a[:, 0].copy(), a[:, 1:].copy()
 
     def neighbor_rows(self, first: int = 0, count: int | None = None):
         """(counts, offsets, ids): the neighbour sets of the particles [first, first + count) from
