@@ -237,7 +237,8 @@ int mph_step(MphCtx* ctx, int nsteps);
  * Steps still pending run, and the error flags of everything launched are read, at the next
  * flush point: mph_synchronize, mph_get, mph_set, every writer, mph_compute_virial,
  * mph_neighbor_stats, mph_profile_steps, mph_phase_timing, mph_monitor_configure, mph_monitor_read,
- * mph_sample_grid, mph_gauge_configure, mph_gauge_grid, turning batching off, mph_destroy; so
+ * mph_sample_grid, mph_gauge_configure, mph_gauge_grid, mph_select and the selection's consumers,
+ * turning batching off, mph_destroy; so
  * every field read after a step is that step's, bit for bit as without batching.  A launched
  * batch's error is also reported by a later mph_step once its flags have landed (no wait).
  * Errors therefore surface up to two batches late, or at the next flush point.  Off by default. */
@@ -472,6 +473,97 @@ typedef struct MphGaugeGrid {        /* 72 bytes: origin 0, spacing 24, count 48
  * after mph_set, MPH_ERR_UNSUPPORTED in slab mode); it changes no state and touches no step graph.  A
  * context without particles gives {0, -inf, +inf, 0} for every line.                              */
 int mph_gauge_grid(MphCtx* ctx, const MphGaugeGrid* g, double* out);
+
+/* ---- particle selections ---------------------------------------------------------------------- */
+
+/* A selection is a subset of the particles, built on the device on demand: read any field for the
+ * subset only, write a frame of the subset only, reduce load, momentum and extent over it -- without
+ * copying a whole array.  A context holds one selection: the selected original indices, ascending,
+ * and each one's place in the sorted device arrays.  It is a snapshot of the current state: the next
+ * mph_step, mph_set or mph_set_initial_velocity_profile makes it stale, and every consumer below
+ * then returns MPH_ERR_ARG until the next mph_select (as it does before the first one).  Single
+ * contexts only: every context entry point returns MPH_ERR_UNSUPPORTED in slab mode.  Additive: no
+ * change of MPH_ABI_VERSION.
+ *
+ * Particle i of type t is selected iff all of: type_mask is 0 or has bit t; i % every == phase; box
+ * is 0, or lo[d] <= x[d] < hi[d] on every axis d < dim (2-D: z is ignored) for x the particle's
+ * Position as mph_get returns it now (box 1) or its InitialPosition (box 2: a body, wherever it has
+ * moved).  The compares are raw: no periodic wrap, and a NaN coordinate or bound is never inside.   */
+typedef struct MphSelection {   /* 64 bytes: type_mask 0, box 4, every 8, phase 12, lo 16, hi 40 */
+    int type_mask;   /* bit t = particle type t (0..5); 0 = every type */
+    int box;         /* 0 none, 1 on Position (as mph_get returns it now), 2 on InitialPosition */
+    int every, phase;/* keep original index i iff i % every == phase; every >= 1, 0 <= phase < every */
+    double lo[3], hi[3]; /* lo[d] <= x[d] < hi[d] for d < dim (2-D: z ignored); raw compare, no wrap; NaN never in */
+} MphSelection;
+/* Host only: *out from "types=0,1;box=x0,y0,z0,x1,y1,z1;on=initial;every=4;phase=1" -- any subset
+ * of the keys in any order, separated by ';'; on=position (the default) or on=initial says what the
+ * box tests and needs a box; without keys: every particle.  MPH_ERR_ARG on anything else (an unknown
+ * key, a key twice, a wrong count of numbers, a type outside 0..5, every < 1, a phase outside
+ * [0, every), trailing characters).                                                                */
+int mph_selection_parse(const char* text, MphSelection* out);
+/* Host only: 1 if particle `index` of type `type` at Position pos / InitialPosition pos0 is selected,
+ * else 0 (the very function the device evaluates); MPH_ERR_ARG for every < 1, a phase outside
+ * [0, every), box outside 0..2, mask bits above 0x3f, lo[d] > hi[d] (or a NaN bound) on an axis
+ * d < dim of a box, dim not 2 or 3.  pos / pos0 may be NULL where the box does not read them.       */
+int mph_selection_accepts(const MphSelection* s, int dim, int index, int type, const double pos[3],
+                          const double pos0[3]);
+/* sizeof(MphSelection) and the offsets of its six members as compiled into the library (out7).     */
+int mph_selection_layout(int out7[7]);
+
+/* Make *s the context's selection, evaluated on the current state, and return its size in *count
+ * (may be NULL; 0 is a legal size).  A flush point like mph_get; legal before the first step.
+ * MPH_ERR_ARG for what mph_selection_accepts refuses; a refused call leaves the selection made
+ * before it as it was.                                                                             */
+int mph_select(MphCtx* ctx, const MphSelection* s, int* count);
+/* The selected original indices, ascending: `count` ints.                                          */
+int mph_selected_ids(MphCtx* ctx, int* out);
+/* mph_get for the selection: row r of out is, bit for bit, row ids[r] of what mph_get(field) returns
+ * now, with the same widths (double[count][3], double[count], int[count], double[count][3][3]).
+ * The sorted device arrays are gathered on the device and only the `count` rows are copied.         */
+int mph_get_selected(MphCtx* ctx, int field, void* out);
+/* Sums and extrema over the selection, reduced on the device: MPH_TOTALS doubles (MphTotalSlot), of
+ * x = Position, v = Velocity, F = Force as mph_get returns them now and m = MPH_FIELD_MASS.
+ * v.v = vx vx + vy vy + vz vz, left to right, no contraction; KE adds (0.5 m)(v.v); the torque adds
+ * (x - c) x F with d = x - c a plain difference -- NO minimum image: take a centre on the same side
+ * of a periodic face as the body; each component is d_a F_b - d_b F_a, two rounded products and
+ * their rounded difference.  Empty selection: sums 0, minima +inf, maxima -inf, VMAX2 0.
+ * The terms are added in an order fixed by `count` alone, over ascending original index (fixed
+ * blocks of ranks, a wave fold, the blocks in order; no floating-point atomics), so the totals are a
+ * bit-exact function of the state, the selection and c -- whatever the sorted order, the list format
+ * or the batch shape that led to the state.
+ * What Force holds, hence what a "load" is: for a fluid particle the step's total force; for a
+ * structure particle the interface force plus gravity, zero on clamped particles; for a wall
+ * particle the pair forces from every neighbour, which the reference computes and never applies.
+ * Force is the LAST SUCCESSFUL mph_step's (stored by a call's last step; zeros or the creation's
+ * values before the first): a load of step k needs an mph_step call that ends at step k.           */
+#define MPH_TOTALS 24
+typedef enum MphTotalSlot {
+    MPH_TOT_COUNT = 0,           /* selected particles */
+    MPH_TOT_MASS = 1,            /* sum m */
+    MPH_TOT_PX = 2, MPH_TOT_PY = 3, MPH_TOT_PZ = 4,      /* sum m v */
+    MPH_TOT_KE = 5,              /* sum (0.5 m)(v.v) */
+    MPH_TOT_FX = 6, MPH_TOT_FY = 7, MPH_TOT_FZ = 8,      /* sum Force */
+    MPH_TOT_TX = 9, MPH_TOT_TY = 10, MPH_TOT_TZ = 11,    /* sum (x - c) x Force */
+    MPH_TOT_MX = 12, MPH_TOT_MY = 13, MPH_TOT_MZ = 14,   /* sum m x */
+    MPH_TOT_XMIN = 15, MPH_TOT_XMAX = 16, MPH_TOT_YMIN = 17, MPH_TOT_YMAX = 18,
+    MPH_TOT_ZMIN = 19, MPH_TOT_ZMAX = 20,                /* extent */
+    MPH_TOT_VMAX2 = 21,          /* max v.v */
+    MPH_TOT_RESERVED0 = 22,      /* zero */
+    MPH_TOT_RESERVED1 = 23
+} MphTotalSlot;
+int mph_selection_totals(MphCtx* ctx, const double center[3], double out[MPH_TOTALS]);
+/* mph_write_vtk / mph_write_vtu of the selection alone: the gathered arrays handed to
+ * mph_write_vtk_arrays / mph_write_vtu_arrays with n = count, so the file is exactly what those
+ * writers give for mph_get(...)[ids].                                                              */
+int mph_write_vtk_selected(MphCtx* ctx, const char* path);
+int mph_write_vtu_selected(MphCtx* ctx, const char* path);
+/* For measurement: mph_select(*s), mph_get_selected of Position, Velocity and PressureP, and
+ * mph_selection_totals(center), with every kernel launch timed through the profiler of
+ * mph_profile_steps: ms[k] and names32 (32 chars each) receive launch k's duration from HIP events
+ * and the name it was recorded under, for the first `max` launches; returns the number of launches.
+ * The selection it made stays the context's.                                                       */
+int mph_select_profile(MphCtx* ctx, const MphSelection* s, const double center[3], int max, double* ms,
+                       char* names32);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

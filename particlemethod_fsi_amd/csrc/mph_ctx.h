@@ -82,6 +82,15 @@ struct MphCtx {
     double* sample_out = nullptr;
     size_t sample_cap = 0;       // doubles the allocation holds
     bool a_current = false;
+    // the selection (mph_select, mph_select.hip): the kernels' buffers (allocated at the first
+    // mph_select, regrown when a larger selection or result arrives), the host copy of the selected
+    // ids, and whether the selection is the current state's -- made since the last step or mph_set
+    mph::SelectDev sel;
+    size_t sel_rank_cap = 0;     // ranks sel.ids / slot_a / slot_b hold
+    double* sel_out = nullptr;   // a gathered field; the totals' partial records behind kSelTotals doubles
+    size_t sel_out_cap = 0;      // doubles it holds
+    std::vector<int> sel_ids;
+    bool sel_current = false;
     bool lazy_walls = false;     // lazy wall steps on (ctx_fill_launch; L.cmap allocated at creation)
     MphDist* dist = nullptr;     // non-null in slab mode
 };
@@ -147,6 +156,7 @@ inline void ctx_stepped(MphCtx* c, int nsteps, bool a_current)
 {
     ctx_advance_time(c, nsteps);
     c->stepped = true;
+    c->sel_current = false;   // the selection was the state's before these steps (mph_select)
     if (a_current) c->a_current = true;
 }
 

@@ -1,8 +1,9 @@
 // mph_device.h -- device helpers and the host-side launcher shared by the kernel translation units
 // (mph_sort.hip, mph_search.hip, mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip,
-// mph_sample.hip, mph_gauge.hip): the reference's exact periodic arithmetic, the cell grid's indexing, buffer-
-// descriptor loads, the type predicates, wave-level helpers, a particle's wall motion and wrap, the prep tail, the
-// stencil around a point, and launch / blocks / by_dim / by_flag.  A helper used by one unit alone stays in that
+// mph_sample.hip, mph_gauge.hip, mph_select.hip): the reference's exact periodic arithmetic, the cell
+// grid's indexing, buffer-descriptor loads, the type predicates, wave-level helpers, a particle's wall
+// motion and wrap, the prep tail, the reductions' wave fold, the stencil around a point, and launch /
+// blocks / by_dim / by_flag.  A helper used by one unit alone stays in that
 // unit; the neighbour lists' layout is mph_list.h.
 #pragma once
 
@@ -356,6 +357,37 @@ __device__ __forceinline__ bool mon_sampled(const MonitorDev& M, long long& step
 {
     step = M.counters[0] + 1;
     return step % M.stride == 0;
+}
+
+// The wave fold of the deterministic reductions (the monitors' k_monitor_partial, the selection
+// totals' k_sel_totals_partial).  OP: 0 sum, 1 min, 2 max.
+template <int OP> __device__ __forceinline__ double mon_op2(double a, double b)
+{
+#pragma clang fp contract(off)
+    return OP == 0 ? a + b : (OP == 1 ? fmin(a, b) : fmax(a, b));
+}
+
+// N (a power of two) accumulators per lane over the 64 lanes: every xor stage halves what a lane
+// holds -- it keeps the entries of its side and hands the others across -- so N values cost N - 1 +
+// (6 - log2 N) exchanges instead of 6 N.  Returns entry (lane & (N - 1)) over the whole wave; the
+// order of the additions is fixed by the lane numbers alone.
+template <int OP, int N> __device__ __forceinline__ double mon_wave_fold(double (&v)[N])
+{
+    const int lane = threadIdx.x & 63;
+    int m = 1;
+#pragma unroll
+    for (int n = N; n > 1; n >>= 1, m <<= 1) {
+        const bool hi = (lane & m) != 0;
+#pragma unroll
+        for (int i = 0; i < n / 2; ++i) {
+            const double keep = hi ? v[2 * i + 1] : v[2 * i];
+            const double send = hi ? v[2 * i] : v[2 * i + 1];
+            v[i] = mon_op2<OP>(keep, __shfl_xor(send, m, 64));
+        }
+    }
+#pragma unroll
+    for (; m < 64; m <<= 1) v[0] = mon_op2<OP>(v[0], __shfl_xor(v[0], m, 64));
+    return v[0];
 }
 
 // ------------------------------------------------------------------------ point stencil -----

@@ -1,8 +1,10 @@
 // mph_fields.hip -- the fields of a context: download in the reference's AoS layout and original
-// particle order (mph_get), upload (mph_set), the virial diagnostic, and the file writers.
+// particle order (mph_get), upload (mph_set), the virial diagnostic, the file writers, and the host half
+// of the particle selections (mph_select*; kernels: mph_select.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -210,6 +212,7 @@ int mph_set(MphCtx* c, int field, const void* in)
         return ctx_fail(c, MPH_ERR_ARG, "mph_set supports Position and Velocity");
     MPH_HIP_OK(c, hipSetDevice(c->device));
     c->a_current = false;   // the sorted set A is the last step's, no longer this state's (mph_sample_grid)
+    c->sel_current = false; // nor is the selection this state's (mph_select)
     const int n = c->n;
     const double* v = (const double*)in;
     // current state lives in the B set in the order of B.id: rewrite it in that order
@@ -320,5 +323,323 @@ int mph_write_vtk_async(MphCtx* c, const char* path)
     });
     return MPH_OK;
 }
+
+}  // extern "C"
+
+// ---- particle selections (kernels: mph_select.hip) ----------------------------------------------
+
+namespace {
+
+// a device array of the selection regrown to hold `need` elements (its contents are not kept)
+template <typename T>
+int sel_grow(MphCtx* c, T** p, size_t* cap, size_t need)
+{
+    if (need <= *cap && *p) return MPH_OK;
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    ctx_dfree(c, *p);
+    *p = nullptr;
+    *cap = 0;
+    MPH_CK(ctx_dalloc(c, p, need));
+    *cap = need;
+    return MPH_OK;
+}
+
+// the entry of a consumer of the selection: flush, single contexts, a current selection
+int sel_enter(MphCtx* c, const char* who)
+{
+    MPH_CK(ctx_enter(c));
+    if (c->dist) return ctx_fail(c, MPH_ERR_UNSUPPORTED, std::string(who) + ": selections are not available in slab mode");
+    if (!c->sel_current)
+        return ctx_fail(c, MPH_ERR_ARG, std::string(who) + ": no current selection (none was made, or the state has changed "
+                                            "since: mph_select again after mph_step / mph_set)");
+    return MPH_OK;
+}
+
+// rows of the selection gathered on the device into sel_out and copied to out: nc doubles per row
+// from src[e][slot[r] * stride]
+int sel_gather(MphCtx* c, const double* const* src, int nc, int stride, const int* slot, double* out)
+{
+    const size_t cnt = (size_t)c->sel.count;
+    if (cnt == 0) return MPH_OK;
+    MPH_CK(sel_grow(c, &c->sel_out, &c->sel_out_cap, cnt * nc));
+    launch_select_gather(c->L, src, nc, stride, slot, (int)cnt, c->sel_out);
+    MPH_HIP_OK(c, hipGetLastError());
+    MPH_HIP_OK(c, hipMemcpyAsync(out, c->sel_out, sizeof(double) * cnt * nc, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    return MPH_OK;
+}
+
+// the selected row of original index i, or -1
+long sel_row(const MphCtx* c, int i)
+{
+    const auto it = std::lower_bound(c->sel_ids.begin(), c->sel_ids.end(), i);
+    return it != c->sel_ids.end() && *it == i ? (long)(it - c->sel_ids.begin()) : -1;
+}
+
+// DeformGradient / Strain / Stress: the element planes fetched whole, as download_struct_m33 does
+// (the structure is a small part of a case), and the selected slots' rows picked on the host
+int sel_struct_m33(MphCtx* c, const double* d, double* out)
+{
+    const int ns = c->Sd.n_own;
+    std::memset(out, 0, sizeof(double) * 9 * c->sel_ids.size());
+    if (ns == 0 || c->sel_ids.empty()) return MPH_OK;
+    const size_t fes = (size_t)c->Sd.fes;
+    std::vector<double> h(fes * 9);
+    MPH_HIP_OK(c, hipMemcpyAsync(h.data(), d, sizeof(double) * 9 * fes, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    for (int s = 0; s < ns; ++s) {
+        const long r = sel_row(c, c->sl_orig[s]);
+        if (r < 0) continue;
+        for (int e = 0; e < 9; ++e) out[9 * (size_t)r + e] = h[e * fes + s];
+    }
+    return MPH_OK;
+}
+
+int write_selected(MphCtx* c, const char* path, bool xml)
+{
+    if (!c || !path) return MPH_ERR_ARG;
+    MPH_CK(sel_enter(c, xml ? "mph_write_vtu_selected" : "mph_write_vtk_selected"));
+    const size_t m = c->sel_ids.size(), m1 = std::max<size_t>(m, 1);
+    Snap s;
+    for (auto* v : {&s.pos, &s.vel, &s.acc, &s.force}) v->resize(3 * m1);
+    s.stress.resize(9 * m1); s.strain.resize(9 * m1); s.isnc.resize(m1); s.nc.resize(m1);
+    std::vector<int> prop(m1);
+    std::vector<double> pos0(3 * m1);
+    MPH_CK(mph_get_selected(c, MPH_FIELD_POSITION, s.pos.data()));
+    MPH_CK(mph_get_selected(c, MPH_FIELD_VELOCITY, s.vel.data()));
+    MPH_CK(mph_get_selected(c, MPH_FIELD_ACCELERATION, s.acc.data()));
+    MPH_CK(mph_get_selected(c, MPH_FIELD_FORCE, s.force.data()));
+    MPH_CK(mph_get_selected(c, MPH_FIELD_STRESS, s.stress.data()));
+    MPH_CK(mph_get_selected(c, MPH_FIELD_STRAIN, s.strain.data()));
+    MPH_CK(mph_get_selected(c, MPH_FIELD_INITIAL_STRUCTURE_NEIGHBOR_COUNT, s.isnc.data()));
+    MPH_CK(mph_get_selected(c, MPH_FIELD_NEIGHBOR_COUNT, s.nc.data()));
+    MPH_CK(mph_get_selected(c, MPH_FIELD_PROPERTY, prop.data()));
+    MPH_CK(mph_get_selected(c, MPH_FIELD_INITIAL_POSITION, pos0.data()));
+    auto writer = xml ? mph_write_vtu_arrays : mph_write_vtk_arrays;
+    return writer(path, (int)m, prop.data(), s.pos.data(), pos0.data(), s.vel.data(), s.acc.data(), s.force.data(),
+                  s.stress.data(), s.strain.data(), s.isnc.data(), s.nc.data());
+}
+
+}  // namespace
+
+extern "C" {
+
+int mph_select(MphCtx* c, const MphSelection* s, int* count)
+{
+    if (!s) return MPH_ERR_ARG;
+    MPH_CK(ctx_enter(c));
+    if (c->dist) return ctx_fail(c, MPH_ERR_UNSUPPORTED, "mph_select: selections are not available in slab mode");
+    if (!sel_valid(*s, c->cfg.dim))
+        return ctx_fail(c, MPH_ERR_ARG, "mph_select: every must be >= 1, phase in [0, every), box in 0..2, type_mask within "
+                                        "0x3f and lo <= hi on every axis of a box");
+    SelectDev& D = c->sel;
+    c->sel_current = false;
+    c->sel_ids.clear();
+    D.count = 0;
+    const int n = c->n;
+    if (n > 0) {
+        const int nb = select_blocks(n);
+        if (!D.flag) {   // once: these are sized by the particle count
+            MPH_CK(ctx_dalloc(c, &D.flag, (size_t)n));
+            MPH_CK(ctx_dalloc(c, &D.slot_a_of, (size_t)n));
+            MPH_CK(ctx_dalloc(c, &D.slot_b_of, (size_t)n));
+            MPH_CK(ctx_dalloc(c, &D.mask, ((size_t)n + 31) / 32));
+            MPH_CK(ctx_dalloc(c, &D.bsum, (size_t)nb + 1));
+        }
+        // a box on InitialPosition: that array lives on the host (only the structure's is on the
+        // device), so the host decides with the shared predicate and uploads one bit per particle
+        const bool with_mask = s->box == 2;
+        std::vector<unsigned> mask;
+        if (with_mask) {
+            mask.assign(((size_t)n + 31) / 32, 0u);
+            for (int i = 0; i < n; ++i)
+                if (sel_accepts(*s, c->cfg.dim, i, c->prop[i], &c->pos0[3 * (size_t)i])) mask[i >> 5] |= 1u << (i & 31);
+            MPH_HIP_OK(c, hipMemcpyAsync(D.mask, mask.data(), sizeof(unsigned) * mask.size(), hipMemcpyHostToDevice, c->stream));
+        }
+        // Position as mph_get reads it: the integrated set B in the order of B.id
+        launch_select_scan(c->L, c->L.B, *s, with_mask, D);
+        MPH_HIP_OK(c, hipGetLastError());
+        int cnt = 0;
+        MPH_HIP_OK(c, hipMemcpyAsync(&cnt, D.bsum + nb, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+        if (cnt < 0 || cnt > n) return ctx_fail(c, MPH_ERR_HIP, "mph_select: the scan returned " + std::to_string(cnt));
+        if ((size_t)cnt > c->sel_rank_cap || !D.ids) {
+            size_t cap = 0;
+            for (int** p : {&D.ids, &D.slot_a, &D.slot_b}) {
+                cap = 0;
+                MPH_CK(sel_grow(c, p, &cap, (size_t)std::max(cnt, 1)));
+            }
+            c->sel_rank_cap = cap;
+        }
+        D.count = cnt;
+        if (cnt > 0) {
+            launch_select_fill(c->L, D);
+            MPH_HIP_OK(c, hipGetLastError());
+            MPH_CK(fetch(c, (const int*)D.ids, c->sel_ids, (size_t)cnt));
+            MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    c->sel_current = true;
+    if (count) *count = D.count;
+    return MPH_OK;
+}
+
+int mph_selected_ids(MphCtx* c, int* out)
+{
+    MPH_CK(sel_enter(c, "mph_selected_ids"));
+    if (!out && !c->sel_ids.empty()) return MPH_ERR_ARG;
+    if (!c->sel_ids.empty()) std::memcpy(out, c->sel_ids.data(), sizeof(int) * c->sel_ids.size());
+    return MPH_OK;
+}
+
+int mph_get_selected(MphCtx* c, int field, void* out)
+{
+    MPH_CK(sel_enter(c, "mph_get_selected"));
+    const std::vector<int>& ids = c->sel_ids;
+    const size_t m = ids.size();
+    if (field < 0 || field >= MPH_FIELD_COUNT) return ctx_fail(c, MPH_ERR_ARG, "unknown field " + std::to_string(field));
+    if (m == 0) return MPH_OK;
+    if (!out) return MPH_ERR_ARG;
+    double* o = (double*)out;
+    int* oi = (int*)out;
+    const Launch& L = c->L;
+    const SelectDev& D = c->sel;
+    // the sorted arrays through the slot maps, as mph_get reads them: Position and Velocity from
+    // the set B in B.id order, everything else in A.id order
+    auto planes = [&](const double* x, const double* y, const double* z, const int* slot) {
+        const double* const src[3] = {x, y, z};
+        return sel_gather(c, src, 3, 1, slot, o);
+    };
+    auto xyz4 = [&](const double4* d) {
+        const double* b = (const double*)d;
+        const double* const src[3] = {b, b + 1, b + 2};
+        return sel_gather(c, src, 3, 4, D.slot_a, o);
+    };
+    auto scalar = [&](const double* d, double* to) {
+        const double* const src[1] = {d};
+        return sel_gather(c, src, 1, 1, D.slot_a, to);
+    };
+    // the structure's host tables: row k of S belongs to original index S.orig[k]
+    auto struct_rows = [&](auto put) {
+        for (size_t k = 0; k < c->S.orig.size(); ++k) {
+            const long r = sel_row(c, c->S.orig[k]);
+            if (r >= 0) put((size_t)r, k);
+        }
+    };
+    switch (field) {
+    case MPH_FIELD_POSITION: return planes(L.B.x, L.B.y, L.B.z, D.slot_b);
+    case MPH_FIELD_VELOCITY: return planes(L.B.vx, L.B.vy, L.B.vz, D.slot_b);
+    case MPH_FIELD_INITIAL_POSITION:
+        for (size_t r = 0; r < m; ++r) std::memcpy(o + 3 * r, &c->pos0[3 * (size_t)ids[r]], 3 * sizeof(double));
+        return MPH_OK;
+    case MPH_FIELD_FORCE: return xyz4(L.force);
+    case MPH_FIELD_ACCELERATION: return xyz4(L.acc);
+    case MPH_FIELD_GRAVITY_CENTER: return planes(L.gx, L.gy, L.gz, D.slot_a);
+    case MPH_FIELD_PRESSURE_P: return scalar(L.pres, o);
+    case MPH_FIELD_PRESSURE_A: return scalar(L.pa, o);
+    case MPH_FIELD_DENSITY_A: return scalar(L.dens_a, o);
+    case MPH_FIELD_VOL_STRAIN_P: return scalar(L.vstrain, o);
+    case MPH_FIELD_DIVERGENCE_P: return scalar(L.divp, o);
+    case MPH_FIELD_NEIGHBOR_COUNT:
+        MPH_CK(sel_grow(c, &c->sel_out, &c->sel_out_cap, m));
+        launch_select_gather_int(L, L.nbcount, D.slot_a, (int)m, (int*)c->sel_out);
+        MPH_HIP_OK(c, hipGetLastError());
+        MPH_HIP_OK(c, hipMemcpyAsync(oi, c->sel_out, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
+        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+        return MPH_OK;
+    case MPH_FIELD_MASS:
+        for (size_t r = 0; r < m; ++r) o[r] = c->cfg.density[c->prop[ids[r]]] * c->h.vol;
+        return MPH_OK;
+    case MPH_FIELD_KAPPA: {
+        std::vector<double> vs(c->stepped ? m : 0, 0.0);
+        if (c->stepped) MPH_CK(scalar(L.vstrain, vs.data()));
+        for (size_t r = 0; r < m; ++r)
+            o[r] = (c->stepped && vs[r] < 0.0) ? 0.0 : c->cfg.bulk_modulus[c->prop[ids[r]]];
+        return MPH_OK;
+    }
+    case MPH_FIELD_LAMBDA:
+        for (size_t r = 0; r < m; ++r) o[r] = c->cfg.bulk_viscosity[c->prop[ids[r]]];
+        return MPH_OK;
+    case MPH_FIELD_MU:
+        for (size_t r = 0; r < m; ++r) o[r] = c->cfg.shear_viscosity[c->prop[ids[r]]];
+        return MPH_OK;
+    case MPH_FIELD_PROPERTY:
+        for (size_t r = 0; r < m; ++r) oi[r] = c->prop[ids[r]];
+        return MPH_OK;
+    case MPH_FIELD_INITIAL_STRUCTURE_NEIGHBOR_COUNT:
+        std::memset(oi, 0, sizeof(int) * m);
+        struct_rows([&](size_t r, size_t k) { oi[r] = c->S.count[k]; });
+        return MPH_OK;
+    case MPH_FIELD_DEFORM_GRADIENT: return sel_struct_m33(c, c->Sd.F, o);
+    case MPH_FIELD_STRAIN: return sel_struct_m33(c, c->Sd.E, o);
+    case MPH_FIELD_STRESS: return sel_struct_m33(c, c->Sd.S, o);
+    case MPH_FIELD_NORMALIZER:
+        std::memset(o, 0, sizeof(double) * 9 * m);
+        struct_rows([&](size_t r, size_t k) { std::memcpy(o + 9 * r, &c->S.normalizer[9 * k], sizeof(double) * 9); });
+        return MPH_OK;
+    case MPH_FIELD_VIRIAL_STRESS:
+    case MPH_FIELD_VIRIAL_PRESSURE: {
+        const int w = field == MPH_FIELD_VIRIAL_STRESS ? 9 : 1;
+        std::memset(o, 0, sizeof(double) * w * m);
+        if (!c->vir) return MPH_OK;   // never computed: zeros, as mph_get
+        const double* src[9];
+        for (int e = 0; e < w; ++e) src[e] = (w == 9 ? c->vir : c->vpres) + e;
+        return sel_gather(c, src, w, w, D.slot_a, o);
+    }
+    case MPH_FIELD_LAMBDA_LAMES:
+    case MPH_FIELD_MU_LAMES:
+        for (size_t r = 0; r < m; ++r) o[r] = 0.0;
+        struct_rows([&](size_t r, size_t k) { o[r] = field == MPH_FIELD_LAMBDA_LAMES ? c->S.lame_l[k] : c->S.lame_m[k]; });
+        return MPH_OK;
+    default: return ctx_fail(c, MPH_ERR_ARG, "unknown field " + std::to_string(field));
+    }
+}
+
+int mph_selection_totals(MphCtx* c, const double center[3], double out[MPH_TOTALS])
+{
+    if (!center || !out) return MPH_ERR_ARG;
+    MPH_CK(sel_enter(c, "mph_selection_totals"));
+    if (c->n == 0) {   // (no device arrays)
+        for (int k = 0; k < MPH_TOTALS; ++k)
+            out[k] = k >= MPH_TOT_XMIN && k <= MPH_TOT_ZMAX ? ((k - MPH_TOT_XMIN) % 2 ? -INFINITY : INFINITY) : 0.0;
+        return MPH_OK;
+    }
+    const size_t nb = (size_t)select_total_blocks(c->sel.count);
+    MPH_CK(sel_grow(c, &c->sel_out, &c->sel_out_cap, (size_t)kSelTotals * (nb + 1)));
+    launch_select_totals(c->L, c->L.B, c->sel, center, c->sel_out + kSelTotals, c->sel_out);
+    MPH_HIP_OK(c, hipGetLastError());
+    MPH_HIP_OK(c, hipMemcpyAsync(out, c->sel_out, sizeof(double) * kSelTotals, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    return MPH_OK;
+}
+
+int mph_select_profile(MphCtx* c, const MphSelection* s, const double center[3], int max, double* ms, char* names32)
+{
+    if (!s || !center || max < 0 || (max > 0 && (!ms || !names32))) return MPH_ERR_ARG;
+    MPH_CK(ctx_enter(c));
+    EventProfiler prof;
+    c->L.prof = &prof;
+    int rc = mph_select(c, s, nullptr);
+    std::vector<double> buf(3 * std::max<size_t>(c->sel_ids.size(), 1));
+    double tot[MPH_TOTALS];
+    for (int f : {MPH_FIELD_POSITION, MPH_FIELD_VELOCITY, MPH_FIELD_PRESSURE_P})
+        if (rc == MPH_OK) rc = mph_get_selected(c, f, buf.data());
+    if (rc == MPH_OK) rc = mph_selection_totals(c, center, tot);
+    c->L.prof = nullptr;
+    MPH_CK(rc);
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    const int k = (int)prof.recs.size();
+    for (int i = 0; i < std::min(k, max); ++i) {
+        float t = 0.0f;
+        MPH_HIP_OK(c, hipEventElapsedTime(&t, prof.recs[i].a, prof.recs[i].b));
+        ms[i] = t;
+        std::snprintf(names32 + 32 * (size_t)i, 32, "%s", prof.recs[i].name.c_str());
+    }
+    return k;
+}
+
+int mph_write_vtk_selected(MphCtx* c, const char* path) { return write_selected(c, path, false); }
+
+int mph_write_vtu_selected(MphCtx* c, const char* path) { return write_selected(c, path, true); }
 
 }  // extern "C"

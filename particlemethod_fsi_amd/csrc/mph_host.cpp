@@ -563,6 +563,114 @@ extern "C" int mph_velocity_profile_arrays(const MphConfig* c, double time, int 
     return MPH_OK;
 }
 
+// ---- particle selections: the spec text and the predicate (include/mph_gpu.h) ------------------
+
+namespace {
+
+// the comma-separated numbers of a value: false on anything that is no number
+bool spec_numbers(const std::string& v, std::vector<double>& out)
+{
+    out.clear();
+    size_t a = 0;
+    while (a <= v.size()) {
+        const size_t b = std::min(v.find(',', a), v.size());
+        const std::string tok = v.substr(a, b - a);
+        if (tok.empty()) return false;
+        char* e = nullptr;
+        const double x = std::strtod(tok.c_str(), &e);
+        if (e == tok.c_str() || *e != 0) return false;
+        out.push_back(x);
+        a = b + 1;
+    }
+    return true;
+}
+
+bool spec_int(double x, int lo, int hi, int* out)
+{
+    if (!(x >= lo && x <= hi) || x != std::floor(x)) return false;
+    *out = (int)x;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int mph_selection_parse(const char* text, MphSelection* out)
+{
+    if (!text || !out) return MPH_ERR_ARG;
+    MphSelection s{};
+    s.every = 1;
+    int on = -1;   // -1 not given, 1 position, 2 initial
+    bool have_box = false;
+    unsigned seen = 0;
+    static const char* keys[5] = {"types", "box", "on", "every", "phase"};
+    const std::string t(text);
+    size_t a = 0;
+    while (a < t.size()) {
+        const size_t b = std::min(t.find(';', a), t.size());
+        const std::string item = t.substr(a, b - a);
+        a = b + 1;
+        if (item.empty()) continue;   // (a trailing or doubled ';')
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos) return MPH_ERR_ARG;
+        const std::string key = item.substr(0, eq), val = item.substr(eq + 1);
+        int k = 0;
+        while (k < 5 && key != keys[k]) ++k;
+        if (k == 5 || ((seen >> k) & 1)) return MPH_ERR_ARG;
+        seen |= 1u << k;
+        std::vector<double> v;
+        if (k == 2) {
+            if (val == "position") on = 1;
+            else if (val == "initial") on = 2;
+            else return MPH_ERR_ARG;
+            continue;
+        }
+        if (!spec_numbers(val, v)) return MPH_ERR_ARG;
+        if (k == 0) {
+            for (double x : v) {
+                int ty = 0;
+                if (!spec_int(x, 0, MPH_TYPE_COUNT - 1, &ty)) return MPH_ERR_ARG;
+                s.type_mask |= 1 << ty;
+            }
+        } else if (k == 1) {
+            if (v.size() != 6) return MPH_ERR_ARG;
+            for (int d = 0; d < 3; ++d) {
+                s.lo[d] = v[d];
+                s.hi[d] = v[3 + d];
+            }
+            have_box = true;
+        } else if (v.size() != 1 || !spec_int(v[0], k == 3 ? 1 : 0, 0x7fffffff, k == 3 ? &s.every : &s.phase)) {
+            return MPH_ERR_ARG;
+        }
+    }
+    if (on != -1 && !have_box) return MPH_ERR_ARG;
+    s.box = have_box ? (on == 2 ? 2 : 1) : 0;
+    if (s.phase >= s.every) return MPH_ERR_ARG;
+    *out = s;
+    return MPH_OK;
+}
+
+extern "C" int mph_selection_accepts(const MphSelection* s, int dim, int index, int type, const double pos[3],
+                                     const double pos0[3])
+{
+    if (!s || index < 0 || !sel_valid(*s, dim)) return MPH_ERR_ARG;
+    const double* x = s->box == 2 ? pos0 : pos;
+    if (s->box && !x) return MPH_ERR_ARG;
+    return sel_accepts(*s, dim, index, type, x) ? 1 : 0;
+}
+
+extern "C" int mph_selection_layout(int out7[7])
+{
+    if (!out7) return MPH_ERR_ARG;
+    out7[0] = (int)sizeof(MphSelection);
+    out7[1] = (int)offsetof(MphSelection, type_mask);
+    out7[2] = (int)offsetof(MphSelection, box);
+    out7[3] = (int)offsetof(MphSelection, every);
+    out7[4] = (int)offsetof(MphSelection, phase);
+    out7[5] = (int)offsetof(MphSelection, lo);
+    out7[6] = (int)offsetof(MphSelection, hi);
+    return MPH_OK;
+}
+
 namespace mph {
 
 // ---- derived constants: initializeWeight/Fluid/Wall/Domain (main.cpp:1191-1469) ------------

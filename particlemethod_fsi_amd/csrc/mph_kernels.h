@@ -1,6 +1,7 @@
 // mph_kernels.h -- launch interface of the hand-written HIP/CDNA4 (gfx950) kernels of the MPH explicit
 // hot path, the one host-visible interface of the kernel units (mph_sort.hip, mph_search.hip,
-// mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip, mph_sample.hip, mph_gauge.hip), used by the context's
+// mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip, mph_sample.hip, mph_gauge.hip,
+// mph_select.hip), used by the context's
 // host units (mph_ctx.h) and the slab layer's (mph_dist.h).  It also decides a step's form
 // (seq_step): plain host C++, so a host compiler can include this header and test it.
 #pragma once
@@ -293,6 +294,34 @@ struct GaugeGridDev {
     int waves;       // lines (waves) per block: 1 or 4
     double h;        // radius
 };
+
+// Particle selections (mph_select.hip, mph_select): the device buffers of a context's selection,
+// passed to the kernels by value.  Index spaces: i an original particle index (< n), q an index
+// into the sorted arrays (< n), r a rank among the selected (< count).
+constexpr int kSelTotals = MPH_TOTALS;   // doubles of a totals record (MphTotalSlot)
+struct SelectDev {
+    int* flag = nullptr;           // [n] by i: 1 selected, 0 not
+    int* slot_a_of = nullptr;      // [n] i -> q in the sorted set A (pass-A products, Force, virial)
+    int* slot_b_of = nullptr;      // [n] i -> q in the integrated set B (Position, Velocity)
+    unsigned* mask = nullptr;      // [(n + 31) / 32] a box on InitialPosition: the host's verdict, bit i
+    int* bsum = nullptr;           // [select_blocks(n) + 1] selected per block of i, then their offsets; last: count
+    int *ids = nullptr, *slot_a = nullptr, *slot_b = nullptr;   // [count] by r: i ascending, and its two q
+    int count = 0;
+};
+int select_blocks(int n);          // blocks of original indices of the scan (k_sel_count / k_sel_fill)
+int select_total_blocks(int count);// partial records of the totals
+// flag (with_mask: from D.mask, else the predicate on the device), count and scan: leaves D.flag, the
+// two maps, the block offsets and the count in D.bsum[select_blocks(n)]; L.P->n > 0
+void launch_select_scan(const Launch& L, const Soa& X, const MphSelection& s, bool with_mask, const SelectDev& D);
+// D.ids / slot_a / slot_b of the D.count selected; D.count > 0
+void launch_select_fill(const Launch& L, const SelectDev& D);
+// out[r][e] = src[e][slot[r] * stride] for r < count, e < nc (1, 3 or 9; ints: 1)
+void launch_select_gather(const Launch& L, const double* const* src, int nc, int stride, const int* slot, int count,
+                          double* out);
+void launch_select_gather_int(const Launch& L, const int* src, const int* slot, int count, int* out);
+// the totals about `center` into out[kSelTotals] (device); partial: select_total_blocks(D.count) records
+void launch_select_totals(const Launch& L, const Soa& X, const SelectDev& D, const double* center, double* partial,
+                          double* out);
 
 // One time step of the reference (main.cpp:597-686) is mapped onto these launches:
 //

@@ -8,7 +8,9 @@
 // the .prof holds the current state (the OpenACC build writes stale host arrays);
 // the timing report is wall time of the step loop, not clock() CPU time.  A <vtk pattern> ending
 // in ".vtu" writes binary VTK XML files instead (mph_write_vtu).  MPH_MONITOR and
-// MPH_SAMPLE add a time history and, per VTK output step, the fields on a lattice (below).
+// MPH_SAMPLE add a time history and, per VTK output step, the fields on a lattice (below);
+// MPH_OUTPUT_SELECT crops the VTK-step files to a particle selection and MPH_LOADS appends the
+// totals of a selection -- the load on a body -- to a CSV every MPH_LOADS_STRIDE-th step (below).
 //
 // Several GPUs: MPH_SLABS=N runs the same case as N slab ranks (include/mph_gpu.h, one process
 // per rank): the process forks N - 1 ranks before any HIP call, rank r takes device
@@ -309,6 +311,12 @@ int main(int argc, char** argv)
                                          "the cross-rank reduction is not built yet)");
     if (nslabs > 1 && std::getenv("MPH_SAMPLE"))
         die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_SAMPLE with MPH_SLABS > 1 (sampling needs a single context)");
+    if (nslabs > 1 && (std::getenv("MPH_OUTPUT_SELECT") || std::getenv("MPH_LOADS"))) {
+        const std::string what = std::string(std::getenv("MPH_OUTPUT_SELECT") ? "MPH_OUTPUT_SELECT " : "") +
+                                 (std::getenv("MPH_LOADS") ? "MPH_LOADS " : "") +
+                                 "with MPH_SLABS > 1 (selections need a single context)";
+        die(nullptr, MPH_ERR_UNSUPPORTED, what.c_str());
+    }
     if (nslabs > 1 && spawn_ranks(R, nslabs, host_transport) < 0) {
         std::fprintf(stderr, "error: could not start %d slab ranks\n", nslabs);
         return 1;
@@ -465,6 +473,43 @@ int main(int argc, char** argv)
         if (const char* e = std::getenv("MPH_SAMPLE_FILE")) sfile = e;
         sbuf.resize((size_t)points * MPH_SAMPLE_CHANNELS);
     }
+    // MPH_OUTPUT_SELECT=<spec> (include/mph_gpu.h mph_selection_parse): every VTK-step file, .vtk or
+    // .vtu, holds only that selection, evaluated at that step (written before the loop goes on: the
+    // background writer takes whole frames only); the .prof restart files stay whole.
+    MphSelection out_sel{};
+    const bool out_select = std::getenv("MPH_OUTPUT_SELECT") != nullptr;
+    if (out_select && mph_selection_parse(std::getenv("MPH_OUTPUT_SELECT"), &out_sel) != MPH_OK)
+        die(nullptr, MPH_ERR_ARG, "MPH_OUTPUT_SELECT (types=..;box=x0,y0,z0,x1,y1,z1;on=position|initial;every=..;phase=..)");
+    // MPH_LOADS=<csv path>: every MPH_LOADS_STRIDE-th step (default 10) of this run the selection
+    // MPH_LOADS_SELECT (default: every particle) is made and one row appended: step (counted from the
+    // start of the run), time, and the MPH_TOTALS totals about MPH_LOADS_CENTER=x,y,z (default the
+    // origin) as %.17g -- the summed Force and its torque among them.  Force is stored by the last
+    // step of an mph_step call, so the loop below ends its call on every such step: a loads row is a
+    // flush point (DESIGN.md section 13 has its cost).
+    FILE* loads_f = nullptr;
+    MphSelection loads_sel{};
+    loads_sel.every = 1;
+    int loads_stride = 10;
+    double loads_center[3] = {0.0, 0.0, 0.0};
+    if (const char* lp = std::getenv("MPH_LOADS")) {
+        if (const char* e = std::getenv("MPH_LOADS_SELECT"))
+            if (mph_selection_parse(e, &loads_sel) != MPH_OK) die(nullptr, MPH_ERR_ARG, "MPH_LOADS_SELECT (a selection spec)");
+        if (const char* e = std::getenv("MPH_LOADS_STRIDE")) loads_stride = std::atoi(e);
+        if (loads_stride < 1) die(nullptr, MPH_ERR_ARG, "MPH_LOADS_STRIDE (>= 1)");
+        if (const char* e = std::getenv("MPH_LOADS_CENTER")) {
+            const std::vector<double> v = parse_numbers(e);
+            if (v.size() != 3) die(nullptr, MPH_ERR_ARG, "MPH_LOADS_CENTER (x,y,z)");
+            for (int d = 0; d < 3; ++d) loads_center[d] = v[d];
+        }
+        loads_f = std::fopen(lp, "w");
+        if (!loads_f) die(nullptr, MPH_ERR_IO, "opening the MPH_LOADS file");
+        static const char* cols[MPH_TOTALS] = {"count", "mass", "px", "py", "pz", "ke", "fx", "fy", "fz", "tx", "ty", "tz",
+                                               "mx", "my", "mz", "xmin", "xmax", "ymin", "ymax", "zmin", "zmax", "vmax2",
+                                               "reserved0", "reserved1"};
+        std::fprintf(loads_f, "step,time");
+        for (int k = 0; k < MPH_TOTALS; ++k) std::fprintf(loads_f, ",%s", cols[k]);
+        std::fprintf(loads_f, "\n");
+    }
     const auto loop_t0 = std::chrono::steady_clock::now();
     double time_now = cfg.time;
     int istep = (int)(time_now / dt);
@@ -492,7 +537,9 @@ int main(int argc, char** argv)
             if (t + 1.0e-5 * dt >= vtk_next) { vtk_after = true; break; }
             t += dt;
             if (t + 1.0e-5 * dt >= out_next || !(t < cfg.end_time + 1.0e-5 * dt)) break;
+            if (loads_f && (steps_run + k) % loads_stride == 0) break;   // (that step stores Force)
         }
+        const bool loads_after = loads_f && (steps_run + k) % loads_stride == 0;
         const auto t0 = std::chrono::steady_clock::now();
         roctxRangePushA("mph_step");
         rc = mph_step(ctx, k);
@@ -517,6 +564,17 @@ int main(int argc, char** argv)
             if (nslabs > 1 && std::atoi(f) == R.rank) die(ctx, MPH_ERR_ARG, "MPH_FAIL_RANK fault injection");
         loop_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         steps_run += k;
+        if (loads_after) {
+            double tot[MPH_TOTALS];
+            rc = mph_select(ctx, &loads_sel, nullptr);
+            if (rc) die(ctx, rc, "mph_select (MPH_LOADS_SELECT)");
+            rc = mph_selection_totals(ctx, loads_center, tot);
+            if (rc) die(ctx, rc, "mph_selection_totals");
+            std::fprintf(loads_f, "%lld,%.17g", steps_run, mph_time(ctx));
+            for (int q = 0; q < MPH_TOTALS; ++q) std::fprintf(loads_f, ",%.17g", tot[q]);
+            std::fprintf(loads_f, "\n");
+            std::fflush(loads_f);
+        }
         for (int s = 0; s < k; ++s) {
             if (vtk_after && s == k - 1 && sampling) {
                 rc = mph_sample_grid(ctx, &sgrid, sbuf.data());
@@ -533,7 +591,13 @@ int main(int argc, char** argv)
                 if (rc) die(ctx, rc, "mph_compute_virial");
                 std::snprintf(name, sizeof(name), vtk.c_str(), istep);
                 // formatted and written by a background thread while the next steps run
-                rc = vtu ? mph_write_vtu(ctx, name) : mph_write_vtk_async(ctx, name);
+                if (out_select) {
+                    rc = mph_select(ctx, &out_sel, nullptr);
+                    if (rc) die(ctx, rc, "mph_select (MPH_OUTPUT_SELECT)");
+                    rc = vtu ? mph_write_vtu_selected(ctx, name) : mph_write_vtk_selected(ctx, name);
+                } else {
+                    rc = vtu ? mph_write_vtu(ctx, name) : mph_write_vtk_async(ctx, name);
+                }
                 if (rc) die(ctx, rc, "writing a .vtk file");
                 logf("@ Vtk Output Time : %e\n", time_now);
                 vtk_next += cfg.vtk_output_interval;
@@ -568,6 +632,7 @@ int main(int argc, char** argv)
     if (rc) die(ctx, rc, "writing a .vtk file");
     mph_destroy(ctx);
     if (mon.f) std::fclose(mon.f);
+    if (loads_f) std::fclose(loads_f);
     if (g_log) std::fclose(g_log);
     // rank 0 waits for the other ranks (the SIGCHLD handler reaps them and ends the run if one failed)
     for (;;) {

@@ -52,35 +52,6 @@ __host__ __device__ constexpr int mon_entry_sum(int i) { return i == 15 ? 27 : 6
 __host__ __device__ constexpr int mon_entry_min(int i) { return i == 3 ? 24 : 18 + 2 * i; }
 __host__ __device__ constexpr int mon_entry_max(int i) { return i < 3 ? 6 * i + 5 : (i < 6 ? 19 + 2 * (i - 3) : 19 + i); }
 
-template <int OP> __device__ __forceinline__ double mon_op2(double a, double b)
-{
-#pragma clang fp contract(off)
-    return OP == 0 ? a + b : (OP == 1 ? fmin(a, b) : fmax(a, b));
-}
-
-// N (a power of two) accumulators per lane over the 64 lanes: every xor stage halves what a lane
-// holds -- it keeps the entries of its side and hands the others across -- so N values cost N - 1 +
-// (6 - log2 N) exchanges instead of 6 N.  Returns entry (lane & (N - 1)) over the whole wave; the
-// order of the additions is fixed by the lane numbers alone.
-template <int OP, int N> __device__ __forceinline__ double mon_wave_fold(double (&v)[N])
-{
-    const int lane = threadIdx.x & 63;
-    int m = 1;
-#pragma unroll
-    for (int n = N; n > 1; n >>= 1, m <<= 1) {
-        const bool hi = (lane & m) != 0;
-#pragma unroll
-        for (int i = 0; i < n / 2; ++i) {
-            const double keep = hi ? v[2 * i + 1] : v[2 * i];
-            const double send = hi ? v[2 * i] : v[2 * i + 1];
-            v[i] = mon_op2<OP>(keep, __shfl_xor(send, m, 64));
-        }
-    }
-#pragma unroll
-    for (; m < 64; m <<= 1) v[0] = mon_op2<OP>(v[0], __shfl_xor(v[0], m, 64));
-    return v[0];
-}
-
 // a block's record from its lanes' accumulators: the waves' records through LDS, combined in wave
 // order; entry k in thread k (k < kMonPartial)
 __device__ __forceinline__ double mon_block_reduce(double (&sum)[kMonSums], double (&mn)[kMonMins],

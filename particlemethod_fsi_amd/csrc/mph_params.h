@@ -442,6 +442,31 @@ MPH_HD inline int slab_class_static(const SlabGeom& g, double c)
     return kInner;
 }
 
+// Particle selections (include/mph_gpu.h MphSelection).  One body for the host's
+// mph_selection_accepts and the device's k_sel_flag, so the two cannot drift apart.
+// sel_valid: the argument rules; sel_accepts: the predicate of a valid selection, x the coordinates
+// its box tests (Position for box 1, InitialPosition for box 2; not read for box 0).
+MPH_HD inline bool sel_valid(const MphSelection& s, int dim)
+{
+    if (dim != 2 && dim != 3) return false;
+    if (s.every < 1 || s.phase < 0 || s.phase >= s.every) return false;
+    if (s.box < 0 || s.box > 2 || (s.type_mask & ~0x3f)) return false;
+    if (s.box)
+        for (int d = 0; d < 3; ++d)
+            if (d < dim && !(s.lo[d] <= s.hi[d])) return false;
+    return true;
+}
+MPH_HD inline bool sel_accepts(const MphSelection& s, int dim, int index, int type, const double* x)
+{
+    if (s.type_mask && (type < 0 || type >= kTypes || !((s.type_mask >> type) & 1))) return false;
+    if (index % s.every != s.phase) return false;
+    // (three rounds whatever dim is: the device unrolls them and x stays in registers)
+    bool in = true;
+    if (s.box)
+        for (int d = 0; d < 3; ++d) in = in && (d >= dim || (x[d] >= s.lo[d] && x[d] < s.hi[d]));
+    return in;
+}
+
 // Device-resident sizes of one slab redistribution (mph_dist.hip), written by the kernels of the
 // step itself, so that a whole step -- RCCL calls included -- can be captured into a hipGraph.
 // send/recv double as the count messages of the exchange (2 ints to each neighbour).

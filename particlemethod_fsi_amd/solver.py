@@ -62,6 +62,9 @@ EXPORTED_SYMBOLS = [
     "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
     "mph_lean_step_stats", "mph_key_fold_stats", "mph_gauge_configure", "mph_gauge_grid",
     "mph_list_format_stats", "mph_list_span_misses", "mph_list_wave_formats",
+    "mph_selection_parse", "mph_selection_accepts", "mph_selection_layout", "mph_select",
+    "mph_selected_ids", "mph_get_selected", "mph_selection_totals", "mph_write_vtk_selected",
+    "mph_write_vtu_selected", "mph_select_profile",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -124,6 +127,57 @@ GAUGE_CHANNELS = {"COUNT": 0, "TOP": 1, "BOTTOM": 2, "WET": 3}
 GAUGE_MAX = 64
 GAUGE_MAX_BINS = 8192
 GAUGE_GRID_MAX_LINES = 1 << 20
+
+
+class MphSelection(ctypes.Structure):
+    """include/mph_gpu.h MphSelection."""
+    _fields_ = [("type_mask", ctypes.c_int), ("box", ctypes.c_int), ("every", ctypes.c_int),
+                ("phase", ctypes.c_int), ("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3)]
+
+
+# MphTotalSlot (include/mph_gpu.h): name -> index into the record of mph_selection_totals
+TOTALS = 24
+TOTAL_SLOTS = {"COUNT": 0, "MASS": 1, "PX": 2, "PY": 3, "PZ": 4, "KE": 5, "FX": 6, "FY": 7, "FZ": 8,
+               "TX": 9, "TY": 10, "TZ": 11, "MX": 12, "MY": 13, "MZ": 14, "XMIN": 15, "XMAX": 16,
+               "YMIN": 17, "YMAX": 18, "ZMIN": 19, "ZMAX": 20, "VMAX2": 21, "RESERVED0": 22, "RESERVED1": 23}
+SELECTION_BOX = {"position": 1, "initial": 2}
+
+
+def parse_selection(spec: str) -> MphSelection:
+    """mph_selection_parse: "types=0,1;box=x0,y0,z0,x1,y1,z1;on=initial;every=4;phase=1" (any subset
+    of the keys, any order) -> MphSelection; MphError(MPH_ERR_ARG) on anything else.  Host only."""
+    s = MphSelection()
+    _check(load_library().mph_selection_parse(spec.encode(), ctypes.byref(s)))
+    return s
+
+
+def make_selection(types=None, box=None, on: str = "position", every: int = 1, phase: int = 0) -> MphSelection:
+    """An MphSelection from Python values: types an iterable of particle types (None: every type),
+    box ((x0, y0, z0), (x1, y1, z1)) or six numbers (None: no box) tested on Position or, with
+    on="initial", on InitialPosition."""
+    s = MphSelection()
+    for t in (types if types is not None else ()):
+        if not 0 <= int(t) < 6:
+            raise ValueError("selection: particle types are 0..5")
+        s.type_mask |= 1 << int(t)
+    if box is not None:
+        b = np.asarray(box, np.float64).reshape(6)
+        for d in range(3):
+            s.lo[d], s.hi[d] = b[d], b[3 + d]
+        s.box = SELECTION_BOX[on]
+    elif on not in SELECTION_BOX:
+        raise ValueError("selection: on is 'position' or 'initial'")
+    s.every, s.phase = int(every), int(phase)
+    return s
+
+
+def selection_accepts(sel: MphSelection, dim: int, index: int, ptype: int, pos=None, pos0=None) -> int:
+    """mph_selection_accepts: 1 / 0 for one particle (the function the device evaluates); host only."""
+    p = None if pos is None else np.ascontiguousarray(pos, np.float64)
+    p0 = None if pos0 is None else np.ascontiguousarray(pos0, np.float64)
+    return _check(load_library().mph_selection_accepts(ctypes.byref(sel), int(dim), int(index), int(ptype),
+                                                       None if p is None else p.ctypes.data,
+                                                       None if p0 is None else p0.ctypes.data))
 
 
 # MphMonitorSlot (include/mph_gpu.h): name -> index into a sample's head
@@ -260,6 +314,16 @@ def load_library() -> ctypes.CDLL:
         "mph_list_wave_formats": (ip, [vp, vp]),
         "mph_gauge_configure": (ip, [vp, ctypes.POINTER(MphGaugeConfig)]),
         "mph_gauge_grid": (ip, [vp, ctypes.POINTER(MphGaugeGrid), vp]),
+        "mph_selection_parse": (ip, [ctypes.c_char_p, ctypes.POINTER(MphSelection)]),
+        "mph_selection_accepts": (ip, [ctypes.POINTER(MphSelection), ip, ip, ip, vp, vp]),
+        "mph_selection_layout": (ip, [vp]),
+        "mph_select": (ip, [vp, ctypes.POINTER(MphSelection), ctypes.POINTER(ctypes.c_int)]),
+        "mph_selected_ids": (ip, [vp, vp]),
+        "mph_get_selected": (ip, [vp, ip, vp]),
+        "mph_selection_totals": (ip, [vp, vp, vp]),
+        "mph_write_vtk_selected": (ip, [vp, ctypes.c_char_p]),
+        "mph_write_vtu_selected": (ip, [vp, ctypes.c_char_p]),
+        "mph_select_profile": (ip, [vp, ctypes.POINTER(MphSelection), vp, ip, vp, vp]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
@@ -267,7 +331,10 @@ def load_library() -> ctypes.CDLL:
                 "mph_monitor_configure", "mph_monitor_sample_doubles", "mph_monitor_read",
                 "mph_sample_grid", "mph_sample_grid_timed", "mph_write_vti_arrays", "mph_idle_wall_stats",
                 "mph_lean_step_stats", "mph_key_fold_stats", "mph_gauge_configure", "mph_gauge_grid",
-                "mph_list_format_stats", "mph_list_span_misses", "mph_list_wave_formats"}
+                "mph_list_format_stats", "mph_list_span_misses", "mph_list_wave_formats",
+                "mph_selection_parse", "mph_selection_accepts", "mph_selection_layout", "mph_select",
+                "mph_selected_ids", "mph_get_selected", "mph_selection_totals", "mph_write_vtk_selected",
+                "mph_write_vtu_selected", "mph_select_profile"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -690,6 +757,65 @@ class MphSolver:
         _check(self._L.mph_sample_grid_timed(self._h, ctypes.byref(g), out.ctypes.data, ctypes.byref(ms),
                                              ctypes.addressof(name)), self._h)
         return out, ms.value, name.value.decode()
+
+    # -- particle selections ----------------------------------------------------------------------
+    def select(self, types=None, box=None, on: str = "position", every: int = 1, phase: int = 0, spec=None) -> int:
+        """mph_select: make the particles of `types` (None: every type) with original index
+        i % every == phase inside `box` ((x0, y0, z0), (x1, y1, z1): lo <= x < hi, tested on Position
+        or, with on="initial", on InitialPosition; None: no box) the context's selection and return
+        its size.  spec: a text spec (parse_selection) or an MphSelection instead of the other
+        arguments.  A snapshot of the current state: the next step() or set() makes it stale, and
+        the consumers below then raise MPH_ERR_ARG.  A flush point like get()."""
+        if spec is None:
+            sel = make_selection(types, box, on, every, phase)
+        else:
+            sel = spec if isinstance(spec, MphSelection) else parse_selection(spec)
+        cnt = ctypes.c_int(0)
+        _check(self._L.mph_select(self._h, ctypes.byref(sel), ctypes.byref(cnt)), self._h)
+        self._sel_count = cnt.value
+        return cnt.value
+
+    def selected_ids(self) -> np.ndarray:
+        """The selected original indices, ascending."""
+        out = np.zeros(getattr(self, "_sel_count", 0), np.int32)
+        _check(self._L.mph_selected_ids(self._h, out.ctypes.data), self._h)
+        return out
+
+    def get_selected(self, name: str) -> np.ndarray:
+        """get(name)[selected_ids()], bit for bit, gathered on the device: only the selected rows
+        are copied."""
+        fid, w, dt = FIELDS[name]
+        m = getattr(self, "_sel_count", 0)
+        out = np.zeros((m,) if w == 1 else ((m, 3) if w == 3 else (m, 3, 3)), dt)
+        _check(self._L.mph_get_selected(self._h, fid, out.ctypes.data), self._h)
+        return out
+
+    def selection_totals(self, center=(0.0, 0.0, 0.0)) -> dict:
+        """mph_selection_totals: {TOTAL_SLOTS name: value} over the selection -- COUNT, MASS, momentum
+        P*, KE, the summed Force F*, its torque T* about `center` (plain differences, no minimum
+        image), the mass moment M*, the extent and VMAX2 -- reduced on the device in a fixed order."""
+        c = np.ascontiguousarray(center, np.float64).reshape(3)
+        out = np.zeros(TOTALS)
+        _check(self._L.mph_selection_totals(self._h, c.ctypes.data, out.ctypes.data), self._h)
+        return {k: float(out[i]) for k, i in TOTAL_SLOTS.items()}
+
+    def write_vtk_selected(self, path: str):
+        """write_vtk of the selection alone: the array writer's file for get(...)[selected_ids()]."""
+        _check(self._L.mph_write_vtk_selected(self._h, path.encode()), self._h)
+
+    def write_vtu_selected(self, path: str):
+        _check(self._L.mph_write_vtu_selected(self._h, path.encode()), self._h)
+
+    def select_profile(self, sel: MphSelection, center=(0.0, 0.0, 0.0)) -> list:
+        """mph_select_profile: [(kernel name, ms)] of every launch of select(spec=sel), get_selected
+        of Position, Velocity and PressureP, and selection_totals(center), from HIP events."""
+        c = np.ascontiguousarray(center, np.float64).reshape(3)
+        ms = np.zeros(64)
+        names = ctypes.create_string_buffer(64 * 32)
+        k = _check(self._L.mph_select_profile(self._h, ctypes.byref(sel), c.ctypes.data, 64, ms.ctypes.data,
+                                              ctypes.addressof(names)), self._h)
+        raw = names.raw
+        return [(raw[32 * i:32 * (i + 1)].split(b"\0", 1)[0].decode(), float(ms[i])) for i in range(min(k, 64))]
 
     def owned_ids(self) -> np.ndarray:
         """Original indices of the particles this context owns (all of them without a slab)."""
