@@ -238,7 +238,8 @@ int mph_step(MphCtx* ctx, int nsteps);
  * flush point: mph_synchronize, mph_get, mph_set, every writer, mph_compute_virial,
  * mph_neighbor_stats, mph_profile_steps, mph_phase_timing, mph_monitor_configure, mph_monitor_read,
  * mph_sample_grid, mph_gauge_configure, mph_gauge_grid, mph_select and the selection's consumers,
- * turning batching off, mph_destroy; so
+ * mph_compute_kinematics (and _timed), mph_get_kinematics (and _selected), mph_write_vtu_kinematics
+ * (and _selected), turning batching off, mph_destroy; so
  * every field read after a step is that step's, bit for bit as without batching.  A launched
  * batch's error is also reported by a later mph_step once its flags have landed (no wait).
  * Errors therefore surface up to two batches late, or at the next flush point.  Off by default. */
@@ -564,6 +565,114 @@ int mph_write_vtu_selected(MphCtx* ctx, const char* path);
  * The selection it made stays the context's.                                                       */
 int mph_select_profile(MphCtx* ctx, const MphSelection* s, const double center[3], int max, double* ms,
                        char* names32);
+
+/* ---- velocity gradient, vorticity and free-surface fields ------------------------------------- */
+
+/* Per-particle fields derived from the state on demand, by one pass over the step's neighbour lists:
+ * the velocity gradient with divergence, vorticity and shear rate, and a free-surface marker.  Per
+ * particle MPH_KIN_CHANNELS doubles (MphKinChannel), read whole, for the current selection, or
+ * written as a .vtu.  Single contexts only: every context entry point returns MPH_ERR_UNSUPPORTED in
+ * slab mode.  Additive: no change of MPH_ABI_VERSION and no new MphField value.
+ *
+ * Inputs.  For particle i of any type, x_i and v_i are Position and Velocity as mph_get returns them
+ * now (the set mph_compute_virial reads: the integrated set in list order after a step, the sorted
+ * set before the first step).
+ * Neighbours: the particles j != i of the classes in `classes` with r < h.  classes is the sampler's
+ * mask (1 fluid: types 0, 1; 2 structure: 2, 3; 4 walls: 4, 5); 0 means all three.  The mask filters
+ * neighbours only: every particle i gets a record.  q is the minimum image of x_j - x_i (the
+ * reference's Mod(d + w/2, w) - w/2 per axis; 2-D: q_z = 0), r^2 = q_x q_x + q_y q_y + q_z q_z,
+ * r = sqrt(r^2), w = (1 - r/h)^2 -- the weight of the probes and the sampler.  FP64, IEEE division
+ * and square root, products left to right, no contraction.
+ * Sums over those j, each in the order of the particle's list (the host function: j ascending):
+ *   COUNT, WSUM = sum w, c_a = sum w q_a, G_ab = sum (w (v_j,a - v_i,a)) q_b,
+ *   M_ab = sum (w q_a) q_b for a <= b, and M_ba = M_ab.
+ * Channels:
+ *   COUNT; WSUM; FILL = WSUM / n0(h), n0(h) the same sum w over a full lattice of spacing
+ *   particle_spacing in dim dimensions, centre excluded (mph_kinematics_n0);
+ *   CX CY CZ = c / WSUM, the offset of the neighbourhood's weighted centroid (0 with no neighbour;
+ *   -C/|C| is the outward surface normal);
+ *   L[a][b], row-major, dv_a/dx_b: L = G M^-1 on the dim x dim block by the closed-form adjugate,
+ *     3-D: A00 = M11 M22 - M12 M12, A01 = M02 M12 - M01 M22, A02 = M01 M12 - M02 M11,
+ *          A11 = M00 M22 - M02 M02, A12 = M01 M02 - M00 M12, A22 = M00 M11 - M01 M01 (A symmetric),
+ *          det = M00 A00 + M01 A01 + M02 A02;   2-D: A00 = M11, A01 = -M01, A11 = M00,
+ *          det = M00 M11 - M01 M01;   L_ab = (G_a0 A_0b + G_a1 A_1b [+ G_a2 A_2b]) / det,
+ *     every sum left to right; in 2-D the z row and column are 0;
+ *   DIV = L00 + L11 [+ L22]; WX WY WZ = (L21 - L12, L02 - L20, L10 - L01);
+ *   SHEAR = sqrt(2 sum D_ab^2), D_ab = 0.5 (L_ab + L_ba), the nine squares added row-major;
+ *   FLAGS as a double: bit 1 degenerate -- COUNT < dim + 1, or not det > det_floor (tr M / dim)^dim
+ *   (the power as repeated products); then L, DIV, W and SHEAR are 0 -- bit 2 surface, FILL <
+ *   surface_beta; bit 4, COUNT = 0;   the last three channels are reserved, zero.
+ * The corrected gradient G M^-1 is what the elastic solid's Normalizer does: it returns a linear
+ * velocity field's matrix exactly (to rounding), at a free surface and off the lattice alike.
+ *
+ * Radius: h <= MaxRadius, not MaxRadius + MARGIN.  After a step the pass repeats the step's search
+ * storing every neighbour (as mph_compute_virial does), over the positions the step started from: a
+ * pair within MaxRadius now was within MaxRadius + MARGIN then -- the reference's own assumption for
+ * its virial.  Before the first step the lists are the state's own.                                 */
+#define MPH_KIN_CHANNELS 24
+typedef enum MphKinChannel {
+    MPH_KIN_COUNT = 0, MPH_KIN_WSUM = 1, MPH_KIN_FILL = 2,
+    MPH_KIN_CX = 3, MPH_KIN_CY = 4, MPH_KIN_CZ = 5,
+    MPH_KIN_L = 6,               /* 6..14: L[a][b] at MPH_KIN_L + 3 a + b */
+    MPH_KIN_DIV = 15,
+    MPH_KIN_WX = 16, MPH_KIN_WY = 17, MPH_KIN_WZ = 18,
+    MPH_KIN_SHEAR = 19,
+    MPH_KIN_FLAGS = 20,          /* 1 degenerate | 2 surface | 4 no neighbour */
+    MPH_KIN_RESERVED0 = 21, MPH_KIN_RESERVED1 = 22, MPH_KIN_RESERVED2 = 23
+} MphKinChannel;
+#define MPH_KIN_FLAG_DEGENERATE 1
+#define MPH_KIN_FLAG_SURFACE    2
+#define MPH_KIN_FLAG_ALONE      4
+typedef struct MphKinematics {   /* 32 bytes: radius 0, surface_beta 8, det_floor 16, classes 24, reserved 28 */
+    double radius;        /* 0: RadiusRatioV * dx; must be > 0 and <= MaxRadius */
+    double surface_beta;  /* 0: 0.97 (the usual MPS number-density criterion); must be >= 0 */
+    double det_floor;     /* 0: 1e-6; scale-free conditioning floor; must be >= 0 and < 1 */
+    int classes, reserved;/* classes 0..7; reserved must be 0 */
+} MphKinematics;
+/* Host only: sizeof(MphKinematics) and the offsets of its five members as compiled (out6).         */
+int mph_kinematics_layout(int out6[6]);
+/* Host only: *n0 = n0(radius) of the configuration (radius 0: RadiusRatioV * dx), the lattice sum
+ * over ix, iy [, iz] ascending.  MPH_ERR_ARG: a radius below 0 or not finite, dim not 2 or 3.       */
+int mph_kinematics_n0(const MphConfig* cfg, double radius, double* n0);
+/* Host only: the record of every particle from arrays (property[n], pos[n][3], vel[n][3]) into
+ * out[n][MPH_KIN_CHANNELS] by a plain double loop over j ascending with the minimum image -- the
+ * definition above, the per-pair and finishing arithmetic being the very functions the device runs.
+ * O(n^2): MPH_ERR_ARG above 65,536 particles, and for what mph_compute_kinematics refuses in *kin.
+ * For tests and small cases.                                                                        */
+int mph_kinematics_arrays(const MphConfig* cfg, const MphKinematics* kin, int n, const int* property,
+                          const double* pos, const double* vel, double* out);
+/* Host only: a .vtu of n records in the style of mph_write_vtu_arrays (raw appended data, UInt64
+ * headers): Points (Float64, pos[n][3]), Property (Int32) and the Float64 arrays Count, Fill,
+ * Centroid (3 components), VelocityGradient (9), Divergence, Vorticity (3), ShearRate, Flags, the
+ * doubles as computed.                                                                             */
+int mph_write_vtu_kinematics_arrays(const char* path, int n, const int* property, const double* pos,
+                                    const double* kin);
+/* Compute the records of every particle on the device and keep them in the context.  A flush point
+ * like mph_get; legal before the first step; it changes no state a step reads.  MPH_ERR_ARG: a bad
+ * member of *kin (a radius below 0 or above MaxRadius, surface_beta < 0, det_floor outside [0, 1),
+ * class bits above 7, reserved != 0), and after any mph_set or mph_set_initial_velocity_profile
+ * until the next step (the lists and the sorted set are not that state's).  The result is a
+ * snapshot: the next mph_step or mph_set makes it stale, and the getters and writers below then
+ * return MPH_ERR_ARG (as they do before the first mph_compute_kinematics).                          */
+int mph_compute_kinematics(MphCtx* ctx, const MphKinematics* kin);
+/* The snapshot in original order: out[n][MPH_KIN_CHANNELS].                                         */
+int mph_get_kinematics(MphCtx* ctx, double* out);
+/* The snapshot's rows of the current selection: out[count][MPH_KIN_CHANNELS], row r bit for bit row
+ * ids[r] of mph_get_kinematics, gathered on the device (only the count rows are copied).
+ * MPH_ERR_ARG without a current selection or a current snapshot.                                   */
+int mph_get_kinematics_selected(MphCtx* ctx, double* out);
+/* mph_write_vtu_kinematics_arrays of the snapshot with Position and Property: every particle, or the
+ * current selection's rows (the file the array writer gives for those rows).                        */
+int mph_write_vtu_kinematics(MphCtx* ctx, const char* path);
+int mph_write_vtu_kinematics_selected(MphCtx* ctx, const char* path);
+/* mph_compute_kinematics with the kernel timed through the profiler of mph_profile_steps, like
+ * mph_sample_grid_timed: *kernel_ms (may be NULL) its duration from HIP events, name32 (32 chars,
+ * may be NULL) the name it was recorded under (empty where no kernel ran).                         */
+int mph_compute_kinematics_timed(MphCtx* ctx, const MphKinematics* kin, double* kernel_ms, char* name32);
+/* Host only: *out from "radius=..;classes=..;beta=..;det=.." -- any subset of the keys in any order,
+ * separated by ';'; empty text: the defaults (all members 0).  MPH_ERR_ARG on anything else (an
+ * unknown key, a key twice, no number, a class mask that is no integer in 0..7).                    */
+int mph_kinematics_parse(const char* text, MphKinematics* out);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

@@ -1,7 +1,7 @@
 // mph_ctx.h -- the device context behind the C ABI (include/mph_gpu.h) and what its host units share:
 // mph_ctx.hip (errors, allocation, the helpers below, destroy), mph_create.hip (the create phases),
 // mph_step.hip (the step sequencer: graphs, batching, phase timing), mph_fields.hip (download, upload,
-// virial, writers), mph_profile.hip (per-kernel profilers, list and counter diagnostics),
+// virial, writers, selections, kinematics), mph_profile.hip (per-kernel profilers, list and counter diagnostics),
 // mph_observe.hip (host half of the monitors and of the lattice sampling), and the slab-decomposed
 // multi-GPU step (mph_dist.h and its units).
 #pragma once
@@ -91,6 +91,13 @@ struct MphCtx {
     size_t sel_out_cap = 0;      // doubles it holds
     std::vector<int> sel_ids;
     bool sel_current = false;
+    // kinematics (mph_compute_kinematics, mph_kinematics.hip): the records [n][MPH_KIN_CHANNELS] in A
+    // order (allocated at the first call, like vir), whether they are the current state's -- computed
+    // since the last step or mph_set -- and whether an mph_set has changed the state since the last
+    // step or the creation (the lists and the sorted set are then not that state's)
+    double* kin = nullptr;
+    bool kin_current = false;
+    bool set_since_step = false;
     bool lazy_walls = false;     // lazy wall steps on (ctx_fill_launch; L.cmap allocated at creation)
     MphDist* dist = nullptr;     // non-null in slab mode
 };
@@ -157,6 +164,8 @@ inline void ctx_stepped(MphCtx* c, int nsteps, bool a_current)
     ctx_advance_time(c, nsteps);
     c->stepped = true;
     c->sel_current = false;   // the selection was the state's before these steps (mph_select)
+    c->kin_current = false;   // and so were the kinematics (mph_compute_kinematics)
+    c->set_since_step = false;
     if (a_current) c->a_current = true;
 }
 

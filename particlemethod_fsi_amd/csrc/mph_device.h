@@ -1,6 +1,6 @@
 // mph_device.h -- device helpers and the host-side launcher shared by the kernel translation units
 // (mph_sort.hip, mph_search.hip, mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip,
-// mph_sample.hip, mph_gauge.hip, mph_select.hip): the reference's exact periodic arithmetic, the cell
+// mph_sample.hip, mph_gauge.hip, mph_select.hip, mph_kinematics.hip): the reference's exact periodic arithmetic, the cell
 // grid's indexing, buffer-descriptor loads, the type predicates, wave-level helpers, a particle's wall
 // motion and wrap, the prep tail, the reductions' wave fold, the stencil around a point, and launch /
 // blocks / by_dim / by_flag.  A helper used by one unit alone stays in that

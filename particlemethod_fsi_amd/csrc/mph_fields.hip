@@ -1,6 +1,7 @@
 // mph_fields.hip -- the fields of a context: download in the reference's AoS layout and original
-// particle order (mph_get), upload (mph_set), the virial diagnostic, the file writers, and the host half
-// of the particle selections (mph_select*; kernels: mph_select.hip).
+// particle order (mph_get), upload (mph_set), the virial diagnostic, the file writers, the host half
+// of the particle selections (mph_select*; kernels: mph_select.hip) and of the kinematics
+// (mph_compute_kinematics and its readers; kernels: mph_kinematics.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -213,6 +214,8 @@ int mph_set(MphCtx* c, int field, const void* in)
     MPH_HIP_OK(c, hipSetDevice(c->device));
     c->a_current = false;   // the sorted set A is the last step's, no longer this state's (mph_sample_grid)
     c->sel_current = false; // nor is the selection this state's (mph_select)
+    c->kin_current = false; // nor the kinematics, and none can be computed before the next step
+    c->set_since_step = true;
     const int n = c->n;
     const double* v = (const double*)in;
     // current state lives in the B set in the order of B.id: rewrite it in that order
@@ -641,5 +644,126 @@ int mph_select_profile(MphCtx* c, const MphSelection* s, const double center[3],
 int mph_write_vtk_selected(MphCtx* c, const char* path) { return write_selected(c, path, false); }
 
 int mph_write_vtu_selected(MphCtx* c, const char* path) { return write_selected(c, path, true); }
+
+}  // extern "C"
+
+// ---- kinematics (kernels: mph_kinematics.hip) ----------------------------------------------------
+
+namespace {
+
+// the entry of a reader of the kinematics: flush, single contexts, a current snapshot
+int kin_enter(MphCtx* c, const char* who)
+{
+    MPH_CK(ctx_enter(c));
+    if (c->dist) return ctx_fail(c, MPH_ERR_UNSUPPORTED, std::string(who) + ": kinematics are not available in slab mode");
+    if (!c->kin_current)
+        return ctx_fail(c, MPH_ERR_ARG, std::string(who) + ": no current kinematics (none were computed, or the state has "
+                                            "changed since: mph_compute_kinematics again after mph_step / mph_set)");
+    return MPH_OK;
+}
+
+// prof set: the kernel's launch is recorded by it (its events are read by the caller)
+int compute_kinematics(MphCtx* c, const MphKinematics* k, Profiler* prof)
+{
+    if (!k) return MPH_ERR_ARG;
+    MPH_CK(ctx_enter(c));
+    if (c->dist) return ctx_fail(c, MPH_ERR_UNSUPPORTED, "mph_compute_kinematics: not available in slab mode");
+    if (!kin_valid(*k) || k->radius > c->h.max_radius)
+        return ctx_fail(c, MPH_ERR_ARG, "mph_compute_kinematics: radius in [0, MaxRadius = " + std::to_string(c->h.max_radius) +
+                                            "], surface_beta >= 0, det_floor in [0, 1), classes in 0..7, reserved 0");
+    if (c->set_since_step)
+        return ctx_fail(c, MPH_ERR_ARG, "mph_compute_kinematics: run a step first (none since the last mph_set: the lists "
+                                        "are not that state's)");
+    c->kin_current = false;
+    double n0 = 0.0;
+    MPH_CK(mph_kinematics_n0(&c->cfg, k->radius, &n0));
+    const KinDev K = kin_resolve(*k, c->h.rv, n0);
+    if (c->n > 0) {
+        if (!c->kin) MPH_CK(ctx_dalloc(c, &c->kin, (size_t)MPH_KIN_CHANNELS * c->n));
+        // after a step the integrated state B is in A (list) order; before the first step A is current
+        MPH_CK(virial_full_lists(c));
+        Launch L = c->L;
+        L.prof = prof;
+        launch_kinematics(L, c->stepped, K, c->kin);
+        MPH_HIP_OK(c, hipGetLastError());
+        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    }
+    c->kin_current = true;
+    return MPH_OK;
+}
+
+int write_kinematics(MphCtx* c, const char* path, bool selected)
+{
+    if (!c || !path) return MPH_ERR_ARG;
+    const char* who = selected ? "mph_write_vtu_kinematics_selected" : "mph_write_vtu_kinematics";
+    MPH_CK(kin_enter(c, who));
+    if (selected) MPH_CK(sel_enter(c, who));
+    const size_t m = selected ? c->sel_ids.size() : (size_t)c->n_glob, m1 = std::max<size_t>(m, 1);
+    std::vector<double> pos(3 * m1), kin((size_t)MPH_KIN_CHANNELS * m1);
+    std::vector<int> prop(m1);
+    if (selected) {
+        MPH_CK(mph_get_selected(c, MPH_FIELD_POSITION, pos.data()));
+        MPH_CK(mph_get_selected(c, MPH_FIELD_PROPERTY, prop.data()));
+        MPH_CK(mph_get_kinematics_selected(c, kin.data()));
+    } else {
+        MPH_CK(mph_get(c, MPH_FIELD_POSITION, pos.data()));
+        MPH_CK(mph_get(c, MPH_FIELD_PROPERTY, prop.data()));
+        MPH_CK(mph_get_kinematics(c, kin.data()));
+    }
+    const int rc = mph_write_vtu_kinematics_arrays(path, (int)m, prop.data(), pos.data(), kin.data());
+    if (rc) return ctx_fail(c, rc, std::string(who) + ": writing " + path);
+    return MPH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mph_compute_kinematics(MphCtx* c, const MphKinematics* k) { return compute_kinematics(c, k, nullptr); }
+
+int mph_compute_kinematics_timed(MphCtx* c, const MphKinematics* k, double* kernel_ms, char* name32)
+{
+    EventProfiler prof;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (name32) name32[0] = 0;
+    MPH_CK(compute_kinematics(c, k, &prof));
+    if (prof.recs.empty()) return MPH_OK;
+    float ms = 0.0f;
+    MPH_HIP_OK(c, hipEventElapsedTime(&ms, prof.recs[0].a, prof.recs[0].b));
+    if (kernel_ms) *kernel_ms = ms;
+    if (name32) std::snprintf(name32, 32, "%s", prof.recs[0].name.c_str());
+    return MPH_OK;
+}
+
+int mph_get_kinematics(MphCtx* c, double* out)
+{
+    MPH_CK(kin_enter(c, "mph_get_kinematics"));
+    if (c->n == 0) return MPH_OK;
+    if (!out) return MPH_ERR_ARG;
+    constexpr size_t w = MPH_KIN_CHANNELS;
+    double* const src[1] = {c->kin};
+    return download(c, src, w * (size_t)c->n, c->L.A.id, [out](auto* h, size_t i, size_t id) {
+        std::memcpy(out + w * id, &h[0][w * i], sizeof(double) * w);
+    });
+}
+
+int mph_get_kinematics_selected(MphCtx* c, double* out)
+{
+    MPH_CK(kin_enter(c, "mph_get_kinematics_selected"));
+    MPH_CK(sel_enter(c, "mph_get_kinematics_selected"));
+    const size_t cnt = (size_t)c->sel.count;
+    if (cnt == 0) return MPH_OK;
+    if (!out) return MPH_ERR_ARG;
+    MPH_CK(sel_grow(c, &c->sel_out, &c->sel_out_cap, cnt * MPH_KIN_CHANNELS));
+    launch_kin_gather(c->L, c->kin, c->sel.slot_a, (int)cnt, c->sel_out);
+    MPH_HIP_OK(c, hipGetLastError());
+    MPH_HIP_OK(c, hipMemcpyAsync(out, c->sel_out, sizeof(double) * cnt * MPH_KIN_CHANNELS, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    return MPH_OK;
+}
+
+int mph_write_vtu_kinematics(MphCtx* c, const char* path) { return write_kinematics(c, path, false); }
+
+int mph_write_vtu_kinematics_selected(MphCtx* c, const char* path) { return write_kinematics(c, path, true); }
 
 }  // extern "C"

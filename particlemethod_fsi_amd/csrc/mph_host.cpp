@@ -671,6 +671,135 @@ extern "C" int mph_selection_layout(int out7[7])
     return MPH_OK;
 }
 
+// ---- kinematics: the host's form of the device pass (include/mph_gpu.h MphKinematics) ----------
+
+extern "C" int mph_kinematics_layout(int out6[6])
+{
+    if (!out6) return MPH_ERR_ARG;
+    out6[0] = (int)sizeof(MphKinematics);
+    out6[1] = (int)offsetof(MphKinematics, radius);
+    out6[2] = (int)offsetof(MphKinematics, surface_beta);
+    out6[3] = (int)offsetof(MphKinematics, det_floor);
+    out6[4] = (int)offsetof(MphKinematics, classes);
+    out6[5] = (int)offsetof(MphKinematics, reserved);
+    return MPH_OK;
+}
+
+extern "C" int mph_kinematics_parse(const char* text, MphKinematics* out)
+{
+    if (!text || !out) return MPH_ERR_ARG;
+    MphKinematics k{};
+    unsigned seen = 0;
+    static const char* keys[4] = {"radius", "classes", "beta", "det"};
+    const std::string t(text);
+    size_t a = 0;
+    while (a < t.size()) {
+        const size_t b = std::min(t.find(';', a), t.size());
+        const std::string item = t.substr(a, b - a);
+        a = b + 1;
+        if (item.empty()) continue;   // (a trailing or doubled ';')
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos) return MPH_ERR_ARG;
+        const std::string key = item.substr(0, eq);
+        int q = 0;
+        while (q < 4 && key != keys[q]) ++q;
+        if (q == 4 || ((seen >> q) & 1)) return MPH_ERR_ARG;
+        seen |= 1u << q;
+        std::vector<double> v;
+        if (!spec_numbers(item.substr(eq + 1), v) || v.size() != 1 || !std::isfinite(v[0])) return MPH_ERR_ARG;
+        if (q == 0) k.radius = v[0];
+        else if (q == 1) { if (!spec_int(v[0], 0, 7, &k.classes)) return MPH_ERR_ARG; }
+        else if (q == 2) k.surface_beta = v[0];
+        else k.det_floor = v[0];
+    }
+    *out = k;
+    return MPH_OK;
+}
+
+extern "C" int mph_kinematics_n0(const MphConfig* cfg, double radius, double* n0)
+{
+    if (!cfg || !n0 || (cfg->dim != 2 && cfg->dim != 3) || !(radius >= 0.0) || !std::isfinite(radius)) return MPH_ERR_ARG;
+    const double dx = cfg->particle_spacing;
+    const double h = radius > 0.0 ? radius : cfg->radius_ratio_v * dx;
+    if (!(dx > 0.0) || !(h / dx < 1024.0)) return MPH_ERR_ARG;
+    const int range = (int)(h / dx + 3.0), zr = cfg->dim == 2 ? 0 : range;
+    double sum = 0.0;
+    for (int ix = -range; ix <= range; ++ix)
+        for (int iy = -range; iy <= range; ++iy)
+            for (int iz = -zr; iz <= zr; ++iz) {
+                if (ix == 0 && iy == 0 && iz == 0) continue;
+                const double x = dx * ((double)ix), y = dx * ((double)iy), z = dx * ((double)iz);
+                const double r = std::sqrt(mph::r2_hd(x, y, z));
+                if (!(r < h)) continue;
+                const double u = 1.0 - r / h;
+                sum += u * u;
+            }
+    *n0 = sum;
+    return MPH_OK;
+}
+
+// (mph_kinematics_arrays: at the end of this file, behind derive_constants and parallel_ranges)
+
+extern "C" int mph_write_vtu_kinematics_arrays(const char* path, int n, const int* prop, const double* pos,
+                                               const double* kin)
+{
+    if (!path || n < 0 || (n > 0 && (!prop || !pos || !kin))) return MPH_ERR_ARG;
+    const size_t N = (size_t)n;
+    // channel c0 (.. c0 + ncomp - 1) of every record, in particle order
+    struct Arr { const char* name; int ncomp, c0; };
+    const Arr pd[8] = {{"Count", 1, MPH_KIN_COUNT}, {"Fill", 1, MPH_KIN_FILL}, {"Centroid", 3, MPH_KIN_CX},
+                       {"VelocityGradient", 9, MPH_KIN_L}, {"Divergence", 1, MPH_KIN_DIV}, {"Vorticity", 3, MPH_KIN_WX},
+                       {"ShearRate", 1, MPH_KIN_SHEAR}, {"Flags", 1, MPH_KIN_FLAGS}};
+    FILE* fp = std::fopen(path, "wb");
+    if (!fp) return MPH_ERR_IO;
+    uint64_t off = 0;
+    auto decl = [&](const char* type, const char* name, int ncomp, size_t bytes) {
+        std::fprintf(fp, "        <DataArray type=\"%s\"", type);
+        if (name) std::fprintf(fp, " Name=\"%s\"", name);
+        if (ncomp > 1) std::fprintf(fp, " NumberOfComponents=\"%d\"", ncomp);
+        std::fprintf(fp, " format=\"appended\" offset=\"%llu\"/>\n", (unsigned long long)off);
+        off += sizeof(uint64_t) + bytes;
+    };
+    std::fprintf(fp, "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" "
+                     "byte_order=\"LittleEndian\" header_type=\"UInt64\">\n  <UnstructuredGrid>\n"
+                     "    <Piece NumberOfPoints=\"%d\" NumberOfCells=\"%d\">\n      <PointData>\n", n, n);
+    decl("Int32", "Property", 1, 4 * N);
+    for (const Arr& a : pd) decl("Float64", a.name, a.ncomp, sizeof(double) * a.ncomp * N);
+    std::fprintf(fp, "      </PointData>\n      <Points>\n");
+    decl("Float64", nullptr, 3, sizeof(double) * 3 * N);
+    std::fprintf(fp, "      </Points>\n      <Cells>\n");
+    decl("Int32", "connectivity", 1, 4 * N);
+    decl("Int32", "offsets", 1, 4 * N);
+    decl("UInt8", "types", 1, N);
+    std::fprintf(fp, "      </Cells>\n    </Piece>\n  </UnstructuredGrid>\n  <AppendedData encoding=\"raw\">\n   _");
+    auto block = [&](const void* p, size_t bytes) {
+        const uint64_t nb = bytes;
+        std::fwrite(&nb, sizeof(nb), 1, fp);
+        if (bytes) std::fwrite(p, 1, bytes, fp);
+    };
+    block(prop, 4 * N);
+    std::vector<double> buf;
+    for (const Arr& a : pd) {
+        buf.resize(std::max<size_t>((size_t)a.ncomp * N, 1));
+        for (size_t p = 0; p < N; ++p)
+            for (int k = 0; k < a.ncomp; ++k) buf[a.ncomp * p + k] = kin[MPH_KIN_CHANNELS * p + a.c0 + k];
+        block(buf.data(), sizeof(double) * a.ncomp * N);
+    }
+    block(pos, sizeof(double) * 3 * N);
+    std::vector<int> idx(std::max<size_t>(N, 1));
+    for (size_t k = 0; k < N; ++k) idx[k] = (int)k;
+    block(idx.data(), 4 * N);
+    for (size_t k = 0; k < N; ++k) idx[k] = (int)k + 1;
+    block(idx.data(), 4 * N);
+    const std::vector<unsigned char> types(std::max<size_t>(N, 1), 1);   // VTK_VERTEX
+    block(types.data(), N);
+    std::fprintf(fp, "\n  </AppendedData>\n</VTKFile>\n");
+    std::fflush(fp);
+    const bool ok = !std::ferror(fp);
+    std::fclose(fp);
+    return ok ? MPH_OK : MPH_ERR_IO;
+}
+
 namespace mph {
 
 // ---- derived constants: initializeWeight/Fluid/Wall/Domain (main.cpp:1191-1469) ------------
@@ -1149,4 +1278,50 @@ int build_structure(const MphConfig& c, const HostDerived& h, int n, const int* 
     return MPH_OK;
 }
 
+// ---- kinematics from arrays (include/mph_gpu.h mph_kinematics_arrays) --------------------------
+
+// rows [b, e): every j != i in ascending order through the functions the device runs (mph_params.h)
+template <int DIM>
+static void kinematics_rows(const KinDev& K, const double* dw, int n, const int* prop, const double* pos,
+                            const double* vel, double* out, int b, int e)
+{
+    const double hw[3] = {0.5 * dw[0], 0.5 * dw[1], 0.5 * dw[2]};   // (make_dev_params: DevParams.hw)
+    for (int i = b; i < e; ++i) {
+        const double* xi = pos + 3 * (size_t)i;
+        const double* vi = vel + 3 * (size_t)i;
+        KinAcc<DIM> acc;
+        for (int j = 0; j < n; ++j) {
+            if (j == i || !kin_class(K.mask, prop[j])) continue;
+            const double* xj = pos + 3 * (size_t)j;
+            const double* vj = vel + 3 * (size_t)j;
+            double q[3] = {0.0, 0.0, 0.0}, dv[3] = {0.0, 0.0, 0.0};
+            for (int d = 0; d < DIM; ++d) {
+                q[d] = image_hd(xj[d] - xi[d], dw[d], hw[d]);
+                dv[d] = vj[d] - vi[d];
+            }
+            kin_pair<DIM>(acc, K.h, q, r2_hd(q[0], q[1], q[2]), dv);
+        }
+        kin_finish<DIM>(acc, K, out + (size_t)MPH_KIN_CHANNELS * i);
+    }
+}
+
 }  // namespace mph
+
+extern "C" int mph_kinematics_arrays(const MphConfig* cfg, const MphKinematics* kin, int n, const int* property,
+                                     const double* pos, const double* vel, double* out)
+{
+    if (!cfg || !kin || n < 0 || n > 65536 || (n > 0 && (!property || !pos || !vel || !out))) return MPH_ERR_ARG;
+    if (cfg->dim != 2 && cfg->dim != 3) return MPH_ERR_ARG;
+    HostDerived h{};
+    derive_constants(*cfg, h);
+    if (!kin_valid(*kin) || kin->radius > h.max_radius) return MPH_ERR_ARG;
+    double n0 = 0.0;
+    if (const int rc = mph_kinematics_n0(cfg, kin->radius, &n0)) return rc;
+    const KinDev K = kin_resolve(*kin, h.rv, n0);
+    // (rows are independent: any split over the host's cores gives the same bits)
+    parallel_ranges(n, [&](int b, int e) {
+        if (cfg->dim == 3) kinematics_rows<3>(K, h.dw, n, property, pos, vel, out, b, e);
+        else kinematics_rows<2>(K, h.dw, n, property, pos, vel, out, b, e);
+    });
+    return MPH_OK;
+}

@@ -1,7 +1,7 @@
 // mph_kernels.h -- launch interface of the hand-written HIP/CDNA4 (gfx950) kernels of the MPH explicit
 // hot path, the one host-visible interface of the kernel units (mph_sort.hip, mph_search.hip,
 // mph_passes.hip, mph_elastic.hip, mph_slab.hip, mph_monitor.hip, mph_sample.hip, mph_gauge.hip,
-// mph_select.hip), used by the context's
+// mph_select.hip, mph_kinematics.hip), used by the context's
 // host units (mph_ctx.h) and the slab layer's (mph_dist.h).  It also decides a step's form
 // (seq_step): plain host C++, so a host compiler can include this header and test it.
 #pragma once
@@ -392,6 +392,11 @@ void launch_struct_velocity(const Launch& L, bool last, int s0 = 0, int s1 = -1)
 void launch_struct_pack(const Launch& L, const double4* src, int w, const int* idx, int m, double4* buf);
 void launch_struct_unpack(const Launch& L, const double4* buf, int w, const int* idx, int m, double4* dst);
 void launch_virial(const Launch& L, const Soa& X, double* vir, double* vpres);   // X: state in A order
+// kinematics (mph_kinematics.hip): the MPH_KIN_CHANNELS doubles of every particle into out (A order)
+// over the lists as they stand, of the state in A order -- stepped: the integrated set B, else (before
+// the first step) the sorted set A's records; and out[r] = kin[slot[r]] for r < count
+void launch_kinematics(const Launch& L, bool stepped, const KinDev& K, double* out);
+void launch_kin_gather(const Launch& L, const double* kin, const int* slot, int count, double* out);
 
 // slab decomposition (mph_dist.hip; the left / right arguments are the two DistSide records' values)
 struct HaloFields {

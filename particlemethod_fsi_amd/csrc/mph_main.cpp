@@ -10,7 +10,9 @@
 // in ".vtu" writes binary VTK XML files instead (mph_write_vtu).  MPH_MONITOR and
 // MPH_SAMPLE add a time history and, per VTK output step, the fields on a lattice (below);
 // MPH_OUTPUT_SELECT crops the VTK-step files to a particle selection and MPH_LOADS appends the
-// totals of a selection -- the load on a body -- to a CSV every MPH_LOADS_STRIDE-th step (below).
+// totals of a selection -- the load on a body -- to a CSV every MPH_LOADS_STRIDE-th step (below);
+// MPH_KINEMATICS writes the velocity gradient, vorticity and free-surface fields beside every VTK-step
+// file (below).
 //
 // Several GPUs: MPH_SLABS=N runs the same case as N slab ranks (include/mph_gpu.h, one process
 // per rank): the process forks N - 1 ranks before any HIP call, rank r takes device
@@ -317,6 +319,8 @@ int main(int argc, char** argv)
                                  "with MPH_SLABS > 1 (selections need a single context)";
         die(nullptr, MPH_ERR_UNSUPPORTED, what.c_str());
     }
+    if (nslabs > 1 && std::getenv("MPH_KINEMATICS"))
+        die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_KINEMATICS with MPH_SLABS > 1 (kinematics need a single context)");
     if (nslabs > 1 && spawn_ranks(R, nslabs, host_transport) < 0) {
         std::fprintf(stderr, "error: could not start %d slab ranks\n", nslabs);
         return 1;
@@ -480,6 +484,19 @@ int main(int argc, char** argv)
     const bool out_select = std::getenv("MPH_OUTPUT_SELECT") != nullptr;
     if (out_select && mph_selection_parse(std::getenv("MPH_OUTPUT_SELECT"), &out_sel) != MPH_OK)
         die(nullptr, MPH_ERR_ARG, "MPH_OUTPUT_SELECT (types=..;box=x0,y0,z0,x1,y1,z1;on=position|initial;every=..;phase=..)");
+    // MPH_KINEMATICS="radius=..;classes=..;beta=..;det=.." (include/mph_gpu.h mph_kinematics_parse; any
+    // subset of the keys, empty text: the defaults): at every VTK output step the velocity gradient,
+    // vorticity and free-surface fields are computed (mph_compute_kinematics) and written as a .vtu to
+    // MPH_KINEMATICS_FILE, a printf pattern taking the .vtk files' index (default kin%03d.vtu), cropped
+    // to MPH_OUTPUT_SELECT where that is set
+    MphKinematics kin{};
+    std::string kfile = "kin%03d.vtu";
+    const bool kinematics = std::getenv("MPH_KINEMATICS") != nullptr;
+    if (kinematics) {
+        if (mph_kinematics_parse(std::getenv("MPH_KINEMATICS"), &kin) != MPH_OK)
+            die(nullptr, MPH_ERR_ARG, "MPH_KINEMATICS (radius=..;classes=..;beta=..;det=..)");
+        if (const char* e = std::getenv("MPH_KINEMATICS_FILE")) kfile = e;
+    }
     // MPH_LOADS=<csv path>: every MPH_LOADS_STRIDE-th step (default 10) of this run the selection
     // MPH_LOADS_SELECT (default: every particle) is made and one row appended: step (counted from the
     // start of the run), time, and the MPH_TOTALS totals about MPH_LOADS_CENTER=x,y,z (default the
@@ -582,6 +599,19 @@ int main(int argc, char** argv)
                 std::snprintf(name, sizeof(name), sfile.c_str(), istep);
                 rc = mph_write_vti_arrays(name, &sgrid, sbuf.data());
                 if (rc) die(ctx, rc, "writing a .vti file");
+            }
+            if (vtk_after && s == k - 1 && kinematics) {
+                rc = mph_compute_kinematics(ctx, &kin);
+                if (rc) die(ctx, rc, "mph_compute_kinematics");
+                std::snprintf(name, sizeof(name), kfile.c_str(), istep);
+                if (out_select) {
+                    rc = mph_select(ctx, &out_sel, nullptr);
+                    if (rc) die(ctx, rc, "mph_select (MPH_OUTPUT_SELECT)");
+                    rc = mph_write_vtu_kinematics_selected(ctx, name);
+                } else {
+                    rc = mph_write_vtu_kinematics(ctx, name);
+                }
+                if (rc) die(ctx, rc, "writing a kinematics .vtu file");
             }
             if (vtk_after && s == k - 1) {
                 // main.cpp:672-673: the virial diagnostic runs before every VTK write

@@ -467,6 +467,141 @@ MPH_HD inline bool sel_accepts(const MphSelection& s, int dim, int index, int ty
     return in;
 }
 
+// Kinematics (include/mph_gpu.h MphKinematics; kernel: mph_kinematics.hip k_kinematics, host:
+// mph_kinematics_arrays).  One body each for the argument rules, a pair's contribution and the
+// finishing step, so the device and the host's double loop cannot drift apart: only the order in
+// which a particle's pairs arrive differs.  All of it without contraction.
+// The resolved arguments, passed to the kernel by value.
+struct KinDev {
+    double h, n0, beta, det_floor;
+    int mask;   // classes summed: bit 0 fluid, 1 structure, 2 walls
+};
+// the argument rules but the radius's upper bound (MaxRadius: the caller's)
+MPH_HD inline bool kin_valid(const MphKinematics& k)
+{
+    return k.radius >= 0.0 && k.surface_beta >= 0.0 && k.det_floor >= 0.0 && k.det_floor < 1.0 && k.classes >= 0 &&
+           k.classes <= 7 && k.reserved == 0;
+}
+// the defaults resolved (rv: RadiusRatioV * dx; n0: mph_kinematics_n0 of the resolved radius)
+MPH_HD inline KinDev kin_resolve(const MphKinematics& k, double rv, double n0)
+{
+    KinDev K;
+    K.h = k.radius > 0.0 ? k.radius : rv;
+    K.n0 = n0;
+    K.beta = k.surface_beta > 0.0 ? k.surface_beta : 0.97;
+    K.det_floor = k.det_floor > 0.0 ? k.det_floor : 1e-6;
+    K.mask = k.classes ? k.classes : 7;
+    return K;
+}
+MPH_HD inline bool kin_class(int mask, int type) { return (unsigned)type < (unsigned)kTypes && ((mask >> (type >> 1)) & 1); }
+// the periodic minimum image of every pair loop, Mod(d + w/2, w) - w/2 (mph_device.h image_exact's
+// general branch; its short cut for 0 <= s < 0.75 w gives the same bits: floor(s / w) is 0 there)
+MPH_HD inline double image_hd(double d, double w, double hw)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double s = d + hw;
+    return (s - w * floor(s / w)) - hw;
+}
+MPH_HD inline double r2_hd(double q0, double q1, double q2)   // (mph_device.h r2_exact)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return q0 * q0 + q1 * q1 + q2 * q2;
+}
+// a particle's sums: COUNT, WSUM, c, G and the upper triangle of M {00, 01, 02, 11, 12, 22}
+template <int DIM> struct KinAcc {
+    double cnt = 0.0, sw = 0.0;
+    double c[DIM] = {}, G[DIM][DIM] = {}, M[DIM * (DIM + 1) / 2] = {};
+};
+// neighbour j of an accepted class: q its minimum image (q[2] = 0 in 2-D), r2 = r2_exact(q), dv = v_j - v_i
+template <int DIM> MPH_HD inline void kin_pair(KinAcc<DIM>& a, double h, const double (&q)[3], double r2, const double (&dv)[3])
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double r = sqrt(r2);
+    if (!(r < h)) return;
+    const double u = 1.0 - r / h;
+    const double w = u * u;
+    a.cnt += 1.0;
+    a.sw += w;
+    int m = 0;
+    for (int d = 0; d < DIM; ++d) {
+        const double wq = w * q[d];
+        a.c[d] += wq;
+        for (int e = d; e < DIM; ++e) a.M[m++] += wq * q[e];
+        const double wv = w * dv[d];
+        for (int e = 0; e < DIM; ++e) a.G[d][e] += wv * q[e];
+    }
+}
+// the record of a particle's sums: o[MPH_KIN_CHANNELS]
+template <int DIM> MPH_HD inline void kin_finish(const KinAcc<DIM>& a, const KinDev& K, double* o)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    for (int k = 0; k < MPH_KIN_CHANNELS; ++k) o[k] = 0.0;
+    const bool any = a.sw > 0.0;
+    const double fill = a.sw / K.n0;
+    o[MPH_KIN_COUNT] = a.cnt;
+    o[MPH_KIN_WSUM] = a.sw;
+    o[MPH_KIN_FILL] = fill;
+    for (int d = 0; d < DIM; ++d) o[MPH_KIN_CX + d] = any ? a.c[d] / a.sw : 0.0;
+    double A[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, det, floor_;
+    if constexpr (DIM == 3) {
+        const double m00 = a.M[0], m01 = a.M[1], m02 = a.M[2], m11 = a.M[3], m12 = a.M[4], m22 = a.M[5];
+        A[0][0] = m11 * m22 - m12 * m12;
+        A[0][1] = m02 * m12 - m01 * m22;
+        A[0][2] = m01 * m12 - m02 * m11;
+        A[1][1] = m00 * m22 - m02 * m02;
+        A[1][2] = m01 * m02 - m00 * m12;
+        A[2][2] = m00 * m11 - m01 * m01;
+        A[1][0] = A[0][1];
+        A[2][0] = A[0][2];
+        A[2][1] = A[1][2];
+        det = m00 * A[0][0] + m01 * A[0][1] + m02 * A[0][2];
+        const double t = (m00 + m11 + m22) / 3.0;
+        floor_ = K.det_floor * (t * t * t);
+    } else {
+        const double m00 = a.M[0], m01 = a.M[1], m11 = a.M[2];
+        A[0][0] = m11;
+        A[0][1] = -m01;
+        A[1][0] = -m01;
+        A[1][1] = m00;
+        det = m00 * m11 - m01 * m01;
+        const double t = (m00 + m11) / 2.0;
+        floor_ = K.det_floor * (t * t);
+    }
+    const bool degenerate = a.cnt < (double)(DIM + 1) || !(det > floor_);
+    double L[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    if (!degenerate) {
+        for (int d = 0; d < DIM; ++d)
+            for (int e = 0; e < DIM; ++e) {
+                double s = a.G[d][0] * A[0][e] + a.G[d][1] * A[1][e];
+                if constexpr (DIM == 3) s += a.G[d][2] * A[2][e];
+                L[d][e] = s / det;
+            }
+        for (int d = 0; d < 3; ++d)
+            for (int e = 0; e < 3; ++e) o[MPH_KIN_L + 3 * d + e] = L[d][e];
+        o[MPH_KIN_DIV] = DIM == 3 ? L[0][0] + L[1][1] + L[2][2] : L[0][0] + L[1][1];
+        o[MPH_KIN_WX] = L[2][1] - L[1][2];
+        o[MPH_KIN_WY] = L[0][2] - L[2][0];
+        o[MPH_KIN_WZ] = L[1][0] - L[0][1];
+        double s2 = 0.0;
+        for (int d = 0; d < 3; ++d)
+            for (int e = 0; e < 3; ++e) {
+                const double D = 0.5 * (L[d][e] + L[e][d]);
+                s2 += D * D;
+            }
+        o[MPH_KIN_SHEAR] = sqrt(2.0 * s2);
+    }
+    o[MPH_KIN_FLAGS] = (double)((degenerate ? MPH_KIN_FLAG_DEGENERATE : 0) | (fill < K.beta ? MPH_KIN_FLAG_SURFACE : 0) |
+                                (a.cnt == 0.0 ? MPH_KIN_FLAG_ALONE : 0));
+}
+
 // Device-resident sizes of one slab redistribution (mph_dist.hip), written by the kernels of the
 // step itself, so that a whole step -- RCCL calls included -- can be captured into a hipGraph.
 // send/recv double as the count messages of the exchange (2 ints to each neighbour).

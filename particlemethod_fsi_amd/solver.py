@@ -65,6 +65,10 @@ EXPORTED_SYMBOLS = [
     "mph_selection_parse", "mph_selection_accepts", "mph_selection_layout", "mph_select",
     "mph_selected_ids", "mph_get_selected", "mph_selection_totals", "mph_write_vtk_selected",
     "mph_write_vtu_selected", "mph_select_profile",
+    "mph_kinematics_layout", "mph_kinematics_parse", "mph_kinematics_n0", "mph_kinematics_arrays",
+    "mph_write_vtu_kinematics_arrays", "mph_compute_kinematics", "mph_compute_kinematics_timed",
+    "mph_get_kinematics", "mph_get_kinematics_selected", "mph_write_vtu_kinematics",
+    "mph_write_vtu_kinematics_selected",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -178,6 +182,71 @@ def selection_accepts(sel: MphSelection, dim: int, index: int, ptype: int, pos=N
     return _check(load_library().mph_selection_accepts(ctypes.byref(sel), int(dim), int(index), int(ptype),
                                                        None if p is None else p.ctypes.data,
                                                        None if p0 is None else p0.ctypes.data))
+
+
+class MphKinematics(ctypes.Structure):
+    """include/mph_gpu.h MphKinematics."""
+    _fields_ = [("radius", ctypes.c_double), ("surface_beta", ctypes.c_double), ("det_floor", ctypes.c_double),
+                ("classes", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+# MphKinChannel (include/mph_gpu.h): name -> column of a particle's kinematics record; L is the first
+# of the nine columns of the velocity gradient, L[a][b] at KIN["L"] + 3 a + b
+KIN_CHANNELS = 24
+KIN = {"COUNT": 0, "WSUM": 1, "FILL": 2, "CX": 3, "CY": 4, "CZ": 5, "L": 6, "DIV": 15, "WX": 16, "WY": 17,
+       "WZ": 18, "SHEAR": 19, "FLAGS": 20, "RESERVED0": 21, "RESERVED1": 22, "RESERVED2": 23}
+KIN_FLAGS = {"DEGENERATE": 1, "SURFACE": 2, "ALONE": 4}
+
+
+def make_kinematics(radius: float = 0.0, classes: int = 0, beta: float = 0.0, det_floor: float = 0.0) -> MphKinematics:
+    k = MphKinematics()
+    k.radius, k.surface_beta, k.det_floor = float(radius), float(beta), float(det_floor)
+    k.classes, k.reserved = int(classes), 0
+    return k
+
+
+def parse_kinematics(spec: str) -> MphKinematics:
+    """mph_kinematics_parse: "radius=..;classes=..;beta=..;det=.." (any subset of the keys; empty: the
+    defaults) -> MphKinematics; MphError(MPH_ERR_ARG) on anything else.  Host only."""
+    k = MphKinematics()
+    _check(load_library().mph_kinematics_parse(spec.encode(), ctypes.byref(k)))
+    return k
+
+
+def kinematics_n0(cfg: "mphio.MphConfig", radius: float = 0.0) -> float:
+    """mph_kinematics_n0: the weight sum of a full lattice within `radius` (0: RadiusRatioV dx), the
+    denominator of the FILL channel.  Host only."""
+    out = ctypes.c_double(0.0)
+    _check(load_library().mph_kinematics_n0(ctypes.byref(cfg), float(radius), ctypes.byref(out)))
+    return out.value
+
+
+def kinematics_arrays(cfg: "mphio.MphConfig", prop, pos, vel, radius: float = 0.0, classes: int = 0,
+                      beta: float = 0.0, det_floor: float = 0.0, kin: "MphKinematics | None" = None) -> np.ndarray:
+    """mph_kinematics_arrays: the [n, 24] records from arrays by the host's O(n^2) loop (j ascending),
+    the reference of MphSolver.kinematics.  Host only; at most 65,536 particles."""
+    k = kin if kin is not None else make_kinematics(radius, classes, beta, det_floor)
+    prop = np.ascontiguousarray(prop, np.int32)
+    pos, vel = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(vel, np.float64)
+    n = prop.shape[0]
+    if pos.shape != (n, 3) or vel.shape != (n, 3):
+        raise ValueError("kinematics_arrays: pos and vel must have shape (n, 3)")
+    out = np.zeros((n, KIN_CHANNELS))
+    _check(load_library().mph_kinematics_arrays(ctypes.byref(cfg), ctypes.byref(k), n, prop.ctypes.data,
+                                                pos.ctypes.data, vel.ctypes.data, out.ctypes.data))
+    return out
+
+
+def write_vtu_kinematics(path: str, prop, pos, kin):
+    """mph_write_vtu_kinematics_arrays: a .vtu of the records kin [n, 24] at pos [n, 3] (read_vtu reads
+    it back).  Host only."""
+    prop = np.ascontiguousarray(prop, np.int32)
+    pos, kin = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(kin, np.float64)
+    n = prop.shape[0]
+    if pos.shape != (n, 3) or kin.shape != (n, KIN_CHANNELS):
+        raise ValueError("write_vtu_kinematics: pos (n, 3) and kin (n, %d) expected" % KIN_CHANNELS)
+    _check(load_library().mph_write_vtu_kinematics_arrays(path.encode(), n, prop.ctypes.data, pos.ctypes.data,
+                                                          kin.ctypes.data))
 
 
 # MphMonitorSlot (include/mph_gpu.h): name -> index into a sample's head
@@ -324,6 +393,17 @@ def load_library() -> ctypes.CDLL:
         "mph_write_vtk_selected": (ip, [vp, ctypes.c_char_p]),
         "mph_write_vtu_selected": (ip, [vp, ctypes.c_char_p]),
         "mph_select_profile": (ip, [vp, ctypes.POINTER(MphSelection), vp, ip, vp, vp]),
+        "mph_kinematics_layout": (ip, [vp]),
+        "mph_kinematics_parse": (ip, [ctypes.c_char_p, ctypes.POINTER(MphKinematics)]),
+        "mph_kinematics_n0": (ip, [cfgp, dp, ctypes.POINTER(ctypes.c_double)]),
+        "mph_kinematics_arrays": (ip, [cfgp, ctypes.POINTER(MphKinematics), ip, vp, vp, vp, vp]),
+        "mph_write_vtu_kinematics_arrays": (ip, [ctypes.c_char_p, ip, vp, vp, vp]),
+        "mph_compute_kinematics": (ip, [vp, ctypes.POINTER(MphKinematics)]),
+        "mph_compute_kinematics_timed": (ip, [vp, ctypes.POINTER(MphKinematics), ctypes.POINTER(ctypes.c_double), vp]),
+        "mph_get_kinematics": (ip, [vp, vp]),
+        "mph_get_kinematics_selected": (ip, [vp, vp]),
+        "mph_write_vtu_kinematics": (ip, [vp, ctypes.c_char_p]),
+        "mph_write_vtu_kinematics_selected": (ip, [vp, ctypes.c_char_p]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
@@ -334,7 +414,11 @@ def load_library() -> ctypes.CDLL:
                 "mph_list_format_stats", "mph_list_span_misses", "mph_list_wave_formats",
                 "mph_selection_parse", "mph_selection_accepts", "mph_selection_layout", "mph_select",
                 "mph_selected_ids", "mph_get_selected", "mph_selection_totals", "mph_write_vtk_selected",
-                "mph_write_vtu_selected", "mph_select_profile"}
+                "mph_write_vtu_selected", "mph_select_profile",
+                "mph_kinematics_layout", "mph_kinematics_parse", "mph_kinematics_n0", "mph_kinematics_arrays",
+                "mph_write_vtu_kinematics_arrays", "mph_compute_kinematics", "mph_compute_kinematics_timed",
+                "mph_get_kinematics", "mph_get_kinematics_selected", "mph_write_vtu_kinematics",
+                "mph_write_vtu_kinematics_selected"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -387,7 +471,7 @@ def read_vtu(path: str) -> dict:
     raw = open(path, "rb").read()
     head, _, data = raw.partition(b'<AppendedData encoding="raw">')
     data = data[data.index(b"_") + 1:]
-    dt = {"Float32": np.float32, "Int32": np.int32, "UInt8": np.uint8}
+    dt = {"Float32": np.float32, "Float64": np.float64, "Int32": np.int32, "UInt8": np.uint8}
     out = {}
     for m in re.finditer(rb"<DataArray ([^>]*)/>", head):
         attrs = dict(re.findall(rb'(\w+)="([^"]*)"', m.group(1)))
@@ -816,6 +900,45 @@ class MphSolver:
                                               ctypes.addressof(names)), self._h)
         raw = names.raw
         return [(raw[32 * i:32 * (i + 1)].split(b"\0", 1)[0].decode(), float(ms[i])) for i in range(min(k, 64))]
+
+    # -- velocity gradient, vorticity and free-surface fields ---------------------------------------
+    def kinematics(self, radius: float = 0.0, classes: int = 0, beta: float = 0.0, det_floor: float = 0.0,
+                   selected: bool = False, timed: bool = False):
+        """mph_compute_kinematics + mph_get_kinematics: the [n, 24] array of per-particle records
+        (columns KIN: COUNT, WSUM, FILL, the centroid offset C*, the velocity gradient L, DIV, the
+        vorticity W*, SHEAR, FLAGS with the bits KIN_FLAGS) from one pass over the step's neighbour
+        lists, over the neighbours of `classes` (SAMPLE_CLASSES mask, 0: all) within `radius` (0:
+        RadiusRatioV dx, at most MaxRadius); beta: the FILL below which a particle is marked surface
+        (0: 0.97); det_floor: the conditioning floor (0: 1e-6).  Legal before the first step, not
+        between set() and the next step.  selected: the rows of the current selection only, gathered
+        on the device.  timed: (array, kernel milliseconds from HIP events, the kernel's name)."""
+        k = make_kinematics(radius, classes, beta, det_floor)
+        ms = ctypes.c_double(0.0)
+        name = ctypes.create_string_buffer(32)
+        if timed:
+            _check(self._L.mph_compute_kinematics_timed(self._h, ctypes.byref(k), ctypes.byref(ms),
+                                                        ctypes.addressof(name)), self._h)
+        else:
+            _check(self._L.mph_compute_kinematics(self._h, ctypes.byref(k)), self._h)
+        out = self.get_kinematics(selected)
+        return (out, ms.value, name.value.decode()) if timed else out
+
+    def get_kinematics(self, selected: bool = False) -> np.ndarray:
+        """The records of the last kinematics() again (MPH_ERR_ARG once a step or set() made them
+        stale): every particle in original order, or the current selection's rows."""
+        if selected:
+            out = np.zeros((getattr(self, "_sel_count", 0), KIN_CHANNELS))
+            _check(self._L.mph_get_kinematics_selected(self._h, out.ctypes.data), self._h)
+        else:
+            out = np.zeros((self.n, KIN_CHANNELS))
+            _check(self._L.mph_get_kinematics(self._h, out.ctypes.data), self._h)
+        return out
+
+    def write_vtu_kinematics(self, path: str, selected: bool = False):
+        """The last kinematics() as a .vtu (mph_write_vtu_kinematics): every particle, or the current
+        selection's rows."""
+        f = self._L.mph_write_vtu_kinematics_selected if selected else self._L.mph_write_vtu_kinematics
+        _check(f(self._h, path.encode()), self._h)
 
     def owned_ids(self) -> np.ndarray:
         """Original indices of the particles this context owns (all of them without a slab)."""
