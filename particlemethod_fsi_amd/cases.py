@@ -391,6 +391,99 @@ CUTOFF_CASES = (
 )
 
 
+# Mixed materials: both fluids (0, 1), both structures (2, 3) and both wall types (4, 5) in one
+# run, with per-type tables in which no two types share a value and a fully asymmetric ratio table,
+# so that a pass which read table[tj] for table[ti], or ratio[j][i] for ratio[i][j], moves the
+# result (tests/test_materials_model.py measures by how much).  DAM_DATA's type-3 BulkViscosity
+# of 1e3 is a trap: lambda dt / (rho dx^2) ~ 77 blows any type-3 solid up within three steps,
+# so the block overrides it (and type 3's BulkModulus of 1e6 with it).
+_MIX = {"Density": [8e2, 1e3, 1.1e3, 1.3e3, 1e3, 6e3],
+        "BulkModulus": [2e4, 1e4, 1e4, 2e4, 1e4, 1e5],
+        "BulkViscosity": [1.0, 0.1, 0.1, 0.2, 0.1, 1e2],
+        "ShearViscosity": [1e-2, 1e-3, 1e-2, 2e-2, 1e3, 1e-1],
+        "YoungModulus": [1e5, 6e4, 1e8, 1e4],
+        "PoissonRatio": [0.2, 0.4, 0.3, 0.3],
+        "ElasticDt": [2.5e-5]}
+for _t in range(6):
+    _MIX["InteractionRatio(Type%d)" % _t] = [1.0 if _j == _t else 1.0 - 0.05 * ((3 * _t + 5 * _j) % 7 + 1)
+                                             for _j in range(6)]
+_MIX_ST = dict(_MIX, SurfaceTension=[0.072, 0.05, 0.03, 0.01])
+
+
+def _box(t, lo, hi):
+    return Cuboid(t, lo, hi, 0.001)
+
+
+def _flat(t, lo, hi):
+    return Cuboid(t, (lo[0], lo[1], 0.0), (hi[0], hi[1], 0.001), 0.001)
+
+
+# gate3d's tank: two fluids layered in z in a tall and a low column, a gate of type 2 below type 3,
+# floors and walls of both wall types
+_MIX3D = [
+    _box(1, (0.0, 0.003, 0.0), (0.012, 0.02, 0.004)),
+    _box(0, (0.0, 0.003, 0.004), (0.012, 0.02, 0.008)),
+    _box(1, (0.012, 0.003, 0.0), (0.022, 0.012, 0.004)),
+    _box(0, (0.012, 0.003, 0.004), (0.022, 0.012, 0.008)),
+    _box(2, (0.022, 0.0, 0.0), (0.025, 0.008, 0.008)),
+    _box(3, (0.022, 0.008, 0.0), (0.025, 0.015, 0.008)),
+    _box(4, (0.0, 0.0, 0.0), (0.022, 0.003, 0.008)),
+    _box(5, (0.025, 0.0, 0.0), (0.035, 0.003, 0.008)),
+    _box(5, (0.035, 0.0, 0.0), (0.038, 0.025, 0.008)),
+    _box(5, (-0.003, 0.0, 0.0), (0.0, 0.025, 0.008)),
+    _box(4, (-0.003, 0.0, -0.003), (0.038, 0.025, 0.0)),
+    _box(5, (-0.003, 0.0, 0.008), (0.038, 0.025, 0.011)),
+]
+# gate2d's tank: fluid columns of both types side by side and layered on both sides of a gate whose
+# two halves (types 2 and 3) both reach the clamp line, a two-layer floor of types 4 over 5
+_MIX2D = [
+    _flat(1, (0.0, 0.003), (0.025, 0.10)),
+    _flat(0, (0.025, 0.003), (0.05, 0.10)),
+    _flat(1, (0.05, 0.003), (0.1, 0.02)),
+    _flat(0, (0.05, 0.02), (0.1, 0.05)),
+    _flat(0, (0.105, 0.003), (0.13, 0.01)),
+    _flat(1, (0.105, 0.01), (0.13, 0.02)),
+    _flat(2, (0.1, 0.0), (0.102, 0.08)),
+    _flat(3, (0.102, 0.0), (0.105, 0.08)),
+    _flat(4, (0.0, 0.0), (0.1, 0.002)),
+    _flat(5, (0.0, 0.002), (0.1, 0.003)),
+    _flat(4, (0.105, 0.0), (0.2, 0.002)),
+    _flat(5, (0.105, 0.002), (0.2, 0.003)),
+    _flat(5, (0.2, 0.0), (0.203, 0.20)),
+    _flat(4, (-0.003, 0.0), (0.0, 0.20)),
+]
+
+
+def _retyped(cuboids):
+    """The structure cuboids as walls (2 -> 4, 3 -> 5): a case the reference defines with surface
+    tension (beside a structure it reads GravityCenter rows that it never writes)."""
+    return [Cuboid({2: 4, 3: 5}.get(c.type, c.type), c.lower, c.upper, c.space) for c in cuboids]
+
+
+def _mix(name, dim, cuboids, data, jitter, note):
+    b = CASES["gate3d" if dim == 3 else "gate2d"]
+    return _reg(Case(name, dim, "dam", 0.001, b.lower, b.upper, cuboids, data_changes=data, jitter=jitter,
+                     note=note)).name
+
+
+MIX_GOLDEN_CASES = (
+    _mix("mix3d", 3, _MIX3D, _MIX, 0.3, "3-D tank with all six particle types"),
+    _mix("mix3d_st", 3, _retyped(_MIX3D), _MIX_ST, 0.3, "mix3d, structures as walls, surface tension"),
+    _mix("mix2d", 2, _MIX2D, _MIX, 0.3, "2-D tank with all six particle types"),
+    _mix("mix2d_st", 2, _retyped(_MIX2D), _MIX_ST, 0.3, "mix2d, structures as walls, surface tension"),
+)
+# surface tension beside a structure: undefined in the reference (calculateDiffuseInterface reads
+# GravityCenter[j] of structure neighbours, which it allocates and never writes), defined here and
+# in the oracle by zeros on those rows -- oracle-only cases, no golden
+MIX_STGATE_CASES = (
+    _mix("mix3d_stgate", 3, _MIX3D, _MIX_ST, 0.3, "mix3d with surface tension (oracle-defined)"),
+    _mix("mix2d_stgate", 2, _MIX2D, _MIX_ST, 0.3, "mix2d with surface tension (oracle-defined)"),
+)
+MIX_CASES = MIX_GOLDEN_CASES + MIX_STGATE_CASES
+# un-jittered twin for slab-local creation (build_window refuses jitter)
+_mix("mix2d_lat", 2, _MIX2D, _MIX, 0.0, "mix2d on the lattice (slab-local creation)")
+
+
 def d1m_weak(nranks: int) -> Case:
     """Weak-scaling workload of bench.py --gpus N: the D1M tank extended N-fold
     along z (slab axis), so each of N slabs holds about one D1M (N = 1 is D1M itself)."""

@@ -17,7 +17,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SLAB_AXIS = {"channel3d": 2, "channel3d_st": 2, "channel2d": 0, "dam2d": 0, "box3d": 0,
-             "bar2d": 0, "bar3d": 0, "gate2d_sub": 0}
+             "bar2d": 0, "bar3d": 0, "gate2d_sub": 0, "mix3d": 0, "mix2d": 0,
+             "mix2d_lat": 0}
 
 
 def _free_port():

@@ -4,7 +4,8 @@ Runs oracle/_ref/libmphref_<dim>_<module>.so (the reference's src/main.cpp compi
 /root/reference by oracle/Makefile, driven by oracle/ref_harness.inc) on the cases of
 particlemethod_fsi_amd/cases.py and stores snapshots as compressed .npz fixtures:
 
-  <case>.npz   s0/*  after the reference's initialisation (main.cpp:564-570)
+  <case>.npz   (for the cases of PARTS also <case>.1.npz ..., save_parts)
+               s0/*  after the reference's initialisation (main.cpp:564-570)
                s<k>/* after k time steps (main.cpp:597-686 each)
                scalars (the 36 derived constants), meta (json)
   dam2d_output.vtk.gz / dam2d_000.prof.gz   the reference writers' output at step 0
@@ -25,6 +26,7 @@ import os
 import subprocess
 import sys
 import tempfile
+import zlib
 
 import numpy as np
 
@@ -61,6 +63,11 @@ PLAN = {  # case -> steps (cumulative) to snapshot; the first is the full-field 
     # off-lattice (cases.py jitter): the 3-D search and sums away from lattice distances
     "box3d_jit": [1, 10, 100],
     "gate3d_jit": [1, 10, 100],
+    # mixed materials (cases.MIX_GOLDEN_CASES): two fluids, two structures, two wall types
+    "mix3d": [1, 10],      # (20 as well would pass the size of the largest golden, box3d_jit)
+    "mix3d_st": [1, 10],
+    "mix2d": [1, 10, 100],
+    "mix2d_st": [1, 10, 100],
 }
 
 
@@ -112,17 +119,51 @@ def run_case(name: str):
             # only the two virial arrays, so the run continues unchanged
             ref.call("calculateVirialStressAtParticle")
             snap("s%d" % s, ["VirialStressAtParticle", "VirialPressureAtParticle"], True)
-        if k == 0 and name in ("dam2d", "box3d_jit"):
+        if k == 0 and name in ("dam2d", "box3d_jit", "mix3d"):
             rows = [np.sort(ref.neighbors(i)) for i in range(ref.n)]
             out["s%d/nbr_offsets" % s] = np.cumsum([0] + [len(r) for r in rows]).astype(np.int32)
-            out["s%d/nbr_ids" % s] = np.concatenate(rows).astype(np.int32)
+            # mix3d: 16-bit indices (n < 65536), a quarter of the fixture otherwise
+            out["s%d/nbr_ids" % s] = np.concatenate(rows).astype(np.uint16 if name == "mix3d" else np.int32)
     meta = {"case": name, "n": int(ref.n), "dim": c.dim, "module": c.module, "steps": PLAN[name],
             "time": ref.time, "generator": "tests/golden/make_golden.py",
             "init_calls": list(c.init_calls),
             "reference": "oracle/_ref/libmphref_%dd_%s.so" % (c.dim, c.ref_variant)}
-    out["meta"] = np.frombuffer(json.dumps(meta).encode(), np.uint8)
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
-    print(name, "n=%d" % ref.n, "->", os.path.getsize(os.path.join(HERE, name + ".npz")), "bytes")
+    if name in PARTS:
+        paths = save_parts(os.path.join(HERE, name), out, meta)
+    else:
+        out["meta"] = np.frombuffer(json.dumps(meta).encode(), np.uint8)
+        paths = [os.path.join(HERE, name + ".npz")]
+        np.savez_compressed(paths[0], **out)
+    print(name, "n=%d" % ref.n, "->", [os.path.getsize(p) for p in paths], "bytes")
+
+
+# The mixed-material fixtures: off the lattice with all six types, so their arrays hardly compress.
+# Each stays within the size of the largest single golden (box3d_jit.npz, 2,699,447 bytes) in all, its
+# plan trimmed to that, and is written as files of at most PART_LIMIT bytes each.  Every other case is
+# one .npz as before.
+PARTS = ("mix3d", "mix3d_st", "mix2d", "mix2d_st")
+PART_LIMIT = 1000000
+
+
+def save_parts(base: str, out: dict, meta: dict):
+    """<base>.npz, followed by <base>.1.npz, <base>.2.npz ... where one file would pass PART_LIMIT:
+    whole arrays, first fit in the order of `out`, meta["parts"] the number of files
+    (golden_utils.Golden reads them back as one mapping)."""
+    bins, fill = [{}], [4096]   # room for meta in the first
+    for k, v in out.items():
+        size = len(zlib.compress(np.ascontiguousarray(v).tobytes(), 6)) + 256
+        b = next((b for b in range(len(bins)) if fill[b] + size <= PART_LIMIT), len(bins))
+        if b == len(bins):
+            bins.append({})
+            fill.append(0)
+        bins[b][k] = v
+        fill[b] += size
+    meta["parts"] = len(bins)
+    bins[0]["meta"] = np.frombuffer(json.dumps(meta).encode(), np.uint8)
+    paths = [base + (".%d" % b if b else "") + ".npz" for b in range(len(bins))]
+    for path, arrays in zip(paths, bins):
+        np.savez_compressed(path, **arrays)
+    return paths
 
 
 def main(argv):

@@ -10,7 +10,18 @@ import numpy as np
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ["dam2d", "gate2d", "bar2d", "box3d", "gate3d", "dam2d_st", "box3d_st", "gate2d_sub",
          "gate3d_sub", "rolling2d", "rolling3d", "movwall2d", "movwall3d", "turek2d", "gate2d_rolling1",
-         "hydro2d", "bar2d_ivp", "box3d_jit", "gate3d_jit"]
+         "hydro2d", "bar2d_ivp", "box3d_jit", "gate3d_jit", "mix3d", "mix3d_st", "mix2d", "mix2d_st"]
+
+
+class _Parts:
+    """The arrays of several .npz files as one mapping (make_golden.save_parts)."""
+
+    def __init__(self, files):
+        self._of = {k: z for z in files for k in z.files}
+        self.files = list(self._of)
+
+    def __getitem__(self, key):
+        return self._of[key][key]
 
 
 class Golden:
@@ -18,6 +29,10 @@ class Golden:
         self.case = case
         self.z = np.load(os.path.join(GOLDEN, case + ".npz"), allow_pickle=False)
         self.meta = json.loads(bytes(self.z["meta"]).decode())
+        more = [np.load(os.path.join(GOLDEN, "%s.%d.npz" % (case, b)), allow_pickle=False)
+                for b in range(1, self.meta.get("parts", 1))]
+        if more:
+            self.z = _Parts([self.z] + more)
         self.prop = self.z["Property"]
         self.solid = (self.prop >= 2) & (self.prop < 4)
 

@@ -123,21 +123,67 @@ def oracle_rel(parts) -> float:
     return REL_ELASTIC if solid.any() else REL_STEPS
 
 
-def check_fields_against_oracle(s, o, parts, k):
-    """One step's state against the oracle's: NeighborCount bit-exact, every field within
-    bound(f, oracle_rel(parts)) (k: the step, for the failure message)."""
+ORACLE_FIELDS = ["Position", "Velocity", "Force", "PressureP", "VolStrainP", "DivergenceP",
+                 "DensityA", "GravityCenter", "Acceleration"]
+ORACLE_TENSORS = ["DeformGradient", "Stress", "Strain"]
+
+
+def oracle_field_plan(parts):
+    """[(field, rel, rows)]: the float comparisons of one step's state against the oracle's --
+    every field of ORACLE_FIELDS at oracle_rel(parts), DensityA and GravityCenter off the structure
+    rows (the reference never writes them there; left out where no other row exists, bar3d), and the
+    tensors on the structure rows at REL_STEPS."""
     solid = (parts.property >= 2) & (parts.property < 4)
     rel = oracle_rel(parts)
-    assert_close("NeighborCount", s.get("NeighborCount"), o.get("NeighborCount"), rel, context=(k,))
-    for f in ["Position", "Velocity", "Force", "PressureP", "VolStrainP", "DivergenceP",
-              "DensityA", "GravityCenter", "Acceleration"]:
+    plan = []
+    for f in ORACLE_FIELDS:
         rows = ~solid if f in ("DensityA", "GravityCenter") else None
-        if rows is not None and not rows.any():   # an all-solid case (bar3d): no row of these two is defined
+        if rows is not None and not rows.any():
             continue
-        assert_close(f, s.get(f), o.get(f), rel, rows=rows, context=(k,))
+        plan.append((f, rel, rows))
     if solid.any():
-        for f in ["DeformGradient", "Stress", "Strain"]:
-            assert_close(f, s.get(f), o.get(f), REL_STEPS, rows=solid, context=(k,))
+        plan += [(f, REL_STEPS, solid) for f in ORACLE_TENSORS]
+    return plan
+
+
+def check_fields_against_oracle(s, o, parts, k):
+    """One step's state against the oracle's: NeighborCount bit-exact, every comparison of
+    oracle_field_plan(parts) within its bound (k: the step, for the failure message)."""
+    assert_close("NeighborCount", s.get("NeighborCount"), o.get("NeighborCount"), oracle_rel(parts),
+                 context=(k,))
+    for f, rel, rows in oracle_field_plan(parts):
+        assert_close(f, s.get(f), o.get(f), rel, rows=rows, context=(k,))
+
+
+def _check_per_material(pairs, plan, parts, k, worst):
+    for t in np.unique(parts.property):
+        of_type = parts.property == t
+        for f, rel, rows in plan:
+            r = of_type if rows is None else of_type & rows
+            if not r.any():
+                continue
+            got, ref = pairs[f]
+            err = assert_close(f, got, ref, rel, rows=r, context=(k, "type %d" % t))
+            if worst is not None:
+                ratio = err / bound(f, rel, float(np.max(np.abs(ref[r]))))
+                if ratio >= worst.get("ratio", -1.0):
+                    worst.update(ratio=ratio, field=f, type=int(t), step=k, err=err)
+
+
+def check_materials_against_oracle(s, o, parts, k, worst=None):
+    """oracle_field_plan(parts) once more per particle type: the rows of one type against the bound
+    scaled by THAT type's largest magnitude, so that a material whose field is small beside another's
+    (a light fluid under a stiff wall's pressure) cannot hide a wrong table entry under the other's
+    scale.  `worst` (a dict) keeps the largest error / bound seen, with its field, type and step."""
+    plan = oracle_field_plan(parts)
+    _check_per_material({f: (s.get(f), o.get(f)) for f, _, _ in plan}, plan, parts, k, worst)
+
+
+def check_materials_virial_against_oracle(s, o, parts, k, worst=None):
+    """check_virial_against_oracle per particle type (the virial fields as the solver and the oracle
+    hold them: call it after check_virial_against_oracle)."""
+    plan = [(f, oracle_rel(parts), None) for f in VIRIAL]
+    _check_per_material({f: (s.get(f), o.get(f)) for f in VIRIAL}, plan, parts, k, worst)
 
 
 def check_virial_against_oracle(s, o, parts, k):
@@ -149,9 +195,10 @@ def check_virial_against_oracle(s, o, parts, k):
         assert_close(f, s.get(f), o.get(f), rel, context=(k,))
 
 
-def run_against_oracle_every_step(cfg, parts, nsteps):
+def run_against_oracle_every_step(cfg, parts, nsteps, per_material=False, worst=None):
     """Step-by-step against the oracle: NeighborCount and all fields after every step, the virial
-    after the last."""
+    after the last; per_material: each of them per particle type as well
+    (check_materials_against_oracle)."""
     from oracle_bindings import OracleSolver
     from particlemethod_fsi_amd import MphSolver
     o = OracleSolver(cfg, parts)
@@ -161,8 +208,12 @@ def run_against_oracle_every_step(cfg, parts, nsteps):
             s.step(1)
             o.step(1)
             check_fields_against_oracle(s, o, parts, k)
+            if per_material:
+                check_materials_against_oracle(s, o, parts, k, worst)
             if k == nsteps - 1:
                 check_virial_against_oracle(s, o, parts, k)
+                if per_material:
+                    check_materials_virial_against_oracle(s, o, parts, k, worst)
 
 
 def check_rank_files(out_dir, world, n, ref, ref_time, fields, rel=REL_STEPS):

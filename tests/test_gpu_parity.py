@@ -297,7 +297,8 @@ def test_gpu_vtu_matches_state(tmp_path):
         np.testing.assert_array_equal(d["label"], parts.property)
 
 
-@pytest.mark.parametrize("case", ["bar2d", "bar3d", "gate3d_sub", "gate2d_sub", "hydro2d", "turek2d"])
+@pytest.mark.parametrize("case", ["bar2d", "bar3d", "gate3d_sub", "gate2d_sub", "hydro2d", "turek2d", "mix2d",
+                                  "mix3d"])
 def test_gpu_structure_init_equals_host_build(case, monkeypatch):
     """calculateInitialNeighbor + calculateNormalizer run on the device (launch_struct_init) for a
     single context: the counts, Normalizer and Lame constants equal the host build
@@ -355,7 +356,7 @@ def test_gpu_xcd_balanced_map_bitwise(case, monkeypatch):
 
 
 @pytest.mark.parametrize("lanes", ["1", "2", "4", "8"])
-@pytest.mark.parametrize("case", ["bar2d", "gate3d_sub"])
+@pytest.mark.parametrize("case", ["bar2d", "gate3d_sub", "mix2d", "mix3d"])
 def test_gpu_struct_lanes_match_oracle(case, lanes, monkeypatch):
     """The elastic kernels with 1, 2, 4 or 8 lanes per structure slot (MPH_STRUCT_LANES; by
     default the count follows the slot count): each lane sums every G-th list entry, the group adds

@@ -60,10 +60,11 @@ def test_oracle_matches_reference_golden(case):
         pass  # neighbour lists are compared in test_oracle_neighbor_lists
 
 
-@pytest.mark.parametrize("case", ["dam2d", "box3d_jit"])
+@pytest.mark.parametrize("case", ["dam2d", "box3d_jit", "mix3d"])
 def test_oracle_neighbor_lists(case):
     """The oracle's neighbour sets after one step equal the reference's (sorted rows of
-    Neighbor[i][k], main.cpp:1764-1772) -- on the lattice (dam2d) and off it (box3d_jit)."""
+    Neighbor[i][k], main.cpp:1764-1772) -- on the lattice (dam2d), off it (box3d_jit) and with all
+    six particle types (mix3d)."""
     g = Golden(case)
     cfg, parts = cases.get(case).build()
     o = OracleSolver(cfg, parts)
@@ -116,10 +117,11 @@ print("OK")
 # the last four: kernel radii other than 2.5/2.5/2.5 (cases.RADII_CASES, CUTOFF_CASES), which the
 # GPU tests of test_gpu_radii.py take the oracle for -- a fluid case with unequal radii, surface
 # tension with RadiusA the largest, an elastic gate with RadiusP the largest, and the 2.9 lattice
-# whose pairs at 3 dx lie on the search's cutoff
+# whose pairs at 3 dx lie on the search's cutoff; then the mixed-material cases (cases.MIX_CASES), whose
+# per-type tables and asymmetric ratios every stage reads with ti != tj
 @pytest.mark.parametrize("case", ["gate2d", "gate3d", "turek2d", "hydro2d", "movwall3d", "gate3d_jit",
                                   "box3d_r312126", "box3d_st_r312126", "gate3d_sub_r213121",
-                                  "box3d_r292929"])
+                                  "box3d_r292929", "mix3d", "mix3d_st", "mix2d"])
 def test_oracle_per_kernel_against_live_reference(case):
     c = cases.get(case)
     if not ref_available(c.dim, c.ref_variant):

@@ -248,6 +248,71 @@ def test_empty_rows_are_error_zero_scale_zero():
     assert assert_close_golden("Stress", np.zeros((0, 3, 3)), np.zeros((0, 3, 3)), 10) == 0.0
 
 
+# --- the per-step plan and its per-material form (test_gpu_materials.py) ----------------------------
+
+class _State:
+    def __init__(self, fields):
+        self.fields = fields
+
+    def get(self, name):
+        return self.fields[name]
+
+
+def test_oracle_field_plan_is_the_per_step_sites():
+    mixed = types.SimpleNamespace(property=np.array([0, 0, 1, 1, 2, 3, 4, 5], np.int32))
+    solid = np.array([0, 0, 0, 0, 1, 1, 0, 0], bool)
+    plan = parity.oracle_field_plan(mixed)
+    assert [(f, rel) for f, rel, _ in plan] == [(f, 1e-7) for f in (
+        "Position", "Velocity", "Force", "PressureP", "VolStrainP", "DivergenceP", "DensityA", "GravityCenter",
+        "Acceleration")] + [(f, 1e-8) for f in ("DeformGradient", "Stress", "Strain")]
+    for f, _, rows in plan:
+        if f in ("DensityA", "GravityCenter"):
+            assert np.array_equal(rows, ~solid)
+        elif f in ("DeformGradient", "Stress", "Strain"):
+            assert np.array_equal(rows, solid)
+        else:
+            assert rows is None
+    fluid = types.SimpleNamespace(property=np.array([0, 1, 4, 5], np.int32))
+    assert [(f, rel) for f, rel, _ in parity.oracle_field_plan(fluid)] == [(f, 1e-8) for f in parity.ORACLE_FIELDS]
+    bar = types.SimpleNamespace(property=np.array([2, 3], np.int32))
+    assert [f for f, _, _ in parity.oracle_field_plan(bar)] == [
+        f for f in parity.ORACLE_FIELDS if f not in ("DensityA", "GravityCenter")] + parity.ORACLE_TENSORS
+
+
+def test_per_material_check_scales_by_the_types_own_rows():
+    """An error on the light material that the whole field's scale covers: check_fields_against_oracle
+    passes, check_materials_against_oracle names the field and the type.  No new number: the bound
+    is bound(field, rel of the plan, max |reference| over that type's rows)."""
+    parts = types.SimpleNamespace(property=np.array([0, 0, 1, 1, 4, 5], np.int32))
+    n = 6
+    ref = {f: np.zeros((n, 3)) for f in ("Position", "Velocity", "Force", "GravityCenter", "Acceleration")}
+    ref.update({f: np.zeros(n) for f in ("PressureP", "VolStrainP", "DivergenceP", "DensityA")})
+    ref["NeighborCount"] = np.arange(n, dtype=np.int32)
+    ref["PressureP"] = np.array([1.0, -2.0, 1e4, 5e3, 3.0, 4.0])
+    got = {f: a.copy() for f, a in ref.items()}
+    whole, own = bound("PressureP", 1e-8, 1e4), bound("PressureP", 1e-8, 2.0)
+    assert own == 1e-8 * 2.0 + 1e-9
+    got["PressureP"][0] += 0.5 * whole            # far above the type's own bound, below the field's
+    s, o = _State(got), _State(ref)
+    parity.check_fields_against_oracle(s, o, parts, 3)
+    with pytest.raises(AssertionError) as e:
+        parity.check_materials_against_oracle(s, o, parts, 3)
+    assert "PressureP" in str(e.value) and "type 0" in str(e.value) and "%.3e" % own in str(e.value)
+    got["PressureP"][0] = ref["PressureP"][0] + 0.5 * own
+    worst = {}
+    parity.check_materials_against_oracle(s, o, parts, 3, worst)
+    assert worst["field"] == "PressureP" and worst["type"] == 0 and worst["step"] == 3
+    assert worst["ratio"] == pytest.approx(0.5)
+    # the virial form: both fields, every type, the per-step rel
+    vir = {"VirialStressAtParticle": np.ones((n, 3, 3)), "VirialPressureAtParticle": np.ones(n)}
+    bad = {f: a.copy() for f, a in vir.items()}
+    bad["VirialPressureAtParticle"][5] += 2.0 * bound("VirialPressureAtParticle", 1e-8, 1.0)
+    parity.check_materials_virial_against_oracle(_State(vir), _State(vir), parts, 0)
+    with pytest.raises(AssertionError) as e:
+        parity.check_materials_virial_against_oracle(_State(bad), _State(vir), parts, 0)
+    assert "VirialPressureAtParticle" in str(e.value) and "type 5" in str(e.value)
+
+
 # --- the rank launcher ----------------------------------------------------------------------
 
 def _rank_ok(rank, world, port, tag):
