@@ -484,6 +484,30 @@ MIX_CASES = MIX_GOLDEN_CASES + MIX_STGATE_CASES
 _mix("mix2d_lat", 2, _MIX2D, _MIX, 0.0, "mix2d on the lattice (slab-local creation)")
 
 
+# Slab-mode variants of the wall-motion and inlet cases (tests/test_slab_motion_model.py,
+# test_gpu_dist_motion.py) -- oracle-only, no golden.  movwall2d_slab / movwall3d_slab start early
+# enough that the walls move for 30 steps before Time reaches 0.2 and stand still after it;
+# turek2d_fluid is turek2d with fluid where its elastic plate is (no structure particle: the key
+# fold and the second stream's early send carry the inlet profile); turek2d_t07 starts just below
+# Time 0.7, where the outlet band's profile is switched off.
+def _variant(name, base, note, cuboids=None, **changes):
+    b = CASES[base]
+    kw = dict(data_changes=b.data_changes, wall_motion=b.wall_motion, time0=b.time0, init_calls=b.init_calls)
+    kw.update(changes)
+    return _reg(Case(name, b.dim, b.module, b.spacing, b.lower, b.upper, cuboids or b.cuboids, note=note,
+                     **kw)).name
+
+
+SLAB_MOTION_CASES = (
+    _variant("movwall2d_slab", "movwall2d", "movwall2d restarted at Time 0.197 (slab tests)", time0=0.197),
+    _variant("movwall3d_slab", "movwall3d", "movwall3d restarted at Time 0.197 (slab tests)", time0=0.197),
+    _variant("turek2d_fluid", "turek2d", "turek2d with fluid in the plate's place",
+             cuboids=[Cuboid(1, c.lower, c.upper, c.space) if c.type == 2 else c
+                      for c in CASES["turek2d"].cuboids]),
+    _variant("turek2d_t07", "turek2d", "turek2d restarted at Time 0.6995 (the outlet switch)", time0=0.6995),
+)
+
+
 def d1m_weak(nranks: int) -> Case:
     """Weak-scaling workload of bench.py --gpus N: the D1M tank extended N-fold
     along z (slab axis), so each of N slabs holds about one D1M (N = 1 is D1M itself)."""

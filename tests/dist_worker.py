@@ -18,7 +18,18 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SLAB_AXIS = {"channel3d": 2, "channel3d_st": 2, "channel2d": 0, "dam2d": 0, "box3d": 0,
              "bar2d": 0, "bar3d": 0, "gate2d_sub": 0, "mix3d": 0, "mix2d": 0,
-             "mix2d_lat": 0}
+             "mix2d_lat": 0,
+             # wall motion, the inlet profile and the module clamps (test_gpu_dist_motion.py);
+             # movwall3d_slab also runs along z, which a test passes as "<case>@<axis>"
+             "movwall2d_slab": 0, "movwall3d_slab": 0, "rolling2d": 0, "rolling3d": 0, "turek2d": 0,
+             "turek2d_fluid": 0, "turek2d_t07": 0, "hydro2d": 0, "gate2d_rolling1": 0}
+
+
+def case_axis(case):
+    """(registered case name, slab axis) of a run's case argument: "name" (axis from SLAB_AXIS)
+    or "name@axis"."""
+    name, _, axis = case.partition("@")
+    return name, int(axis) if axis else SLAB_AXIS[name]
 
 
 def _free_port():
@@ -58,9 +69,12 @@ def _init(rank, world, port):
 
 def make_cuts(c, world, axis, mode):
     """Slab boundaries of a test run: None (equal slabs), "balanced" (dist.balanced_cuts, as
-    bench.py) or "skew" (equal cuts moved alternately by a tenth of a slab width)."""
+    bench.py), "skew" (equal cuts moved alternately by a tenth of a slab width) or a sequence of
+    world - 1 floats, which are the cuts as they stand."""
     if mode is None:
         return None
+    if not isinstance(mode, str):
+        return np.array([float(x) for x in mode], np.float64)
     from particlemethod_fsi_amd.dist import balanced_cuts
     if mode == "balanced":
         return balanced_cuts(c, world, axis)
@@ -72,12 +86,13 @@ def make_cuts(c, world, axis, mode):
 def gpu_worker(rank, world, port, case, checkpoints, fields, out_path, local=False, cuts_mode=None):
     """Run `case` as rank `rank` of `world` on cuda:0; at every checkpoint (cumulative step
     count) gather `fields` over the ranks; rank 0 saves them to out_path (.npz).  local: the rank
-    is created from its own window of the case only (slab-local creation); cuts_mode: make_cuts."""
+    is created from its own window of the case only (slab-local creation); cuts_mode: make_cuts;
+    case: case_axis.  Every rank's own s.time is recorded at every checkpoint ("s<k>/time")."""
     dist = _init(rank, world, port)
     from particlemethod_fsi_amd import MphSolver, cases
     from particlemethod_fsi_amd.dist import build_local, gather_field, gloo_slab
+    case, axis = case_axis(case)
     c = cases.get(case)
-    axis = SLAB_AXIS[case]
     cuts = make_cuts(c, world, axis, cuts_mode)
     if local:
         cfg, parts, ids, n_glob = build_local(c, rank, world, axis, cuts)
@@ -110,6 +125,9 @@ def gpu_worker(rank, world, port, case, checkpoints, fields, out_path, local=Fal
             for f in fields:
                 res["s%d/%s" % (k, f)] = gather_field(s, f)
             res["s%d/owner" % k] = owner_map()
+            times = [None] * world
+            dist.all_gather_object(times, float(s.time))
+            res["s%d/time" % k] = np.array(times, np.float64)
     if rank == 0:
         np.savez(out_path, **res)
     dist.barrier()

@@ -20,7 +20,6 @@ import pytest
 
 from parity import assert_same, run_calls, snapshot, step_counters as counters, tank
 from particlemethod_fsi_amd import MphSolver, cases
-from particlemethod_fsi_amd.mphio import Cuboid
 
 pytestmark = pytest.mark.gpu
 
@@ -28,14 +27,6 @@ CALLS = (16, 29, 40)
 CASES = ["tank", "box3d_jit", "seam3d", "movwall3d", "rolling3d", "turek2d", "turek2d_fluid", "dam2d", "box3d_st",
          "gate3d"]
 STRUCTURES = {"turek2d", "gate3d"}   # cases with structure particles: the fold stays off
-
-
-def turek_fluid():
-    """turek2d with fluid where its elastic plate is: no structure particle, so the fold is on and the
-    per-step inlet profile (move_and_wrap) runs in pass B's tail."""
-    t = cases.get("turek2d")
-    cuboids = [Cuboid(1, c.lower, c.upper, c.space) if c.type == 2 else c for c in t.cuboids]
-    return cases.Case("turek2d_fluid", 2, "turek_hron", t.spacing, t.lower, t.upper, cuboids).build()
 
 
 ZERO = {"lazy": 0, "lean_search": 0, "lean_pass_a": 0, "folded": 0}
@@ -51,8 +42,9 @@ _built, _single = {}, {}
 
 def build(case):
     if case not in _built:
-        _built[case] = tank() if case == "tank" else turek_fluid() if case == "turek2d_fluid" else \
-            cases.get(case).build()
+        # (turek2d_fluid, cases.SLAB_MOTION_CASES: turek2d with fluid where its elastic plate is -- no
+        # structure particle, so the fold is on and the inlet profile runs in pass B's tail)
+        _built[case] = tank() if case == "tank" else cases.get(case).build()
     return _built[case]
 
 

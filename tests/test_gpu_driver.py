@@ -170,7 +170,8 @@ def test_driver_matches_reference_executable(tmp_path, case):
 
 
 # case -> (MPH_DIM, MPH_MODULE, slab ranks) of the multi-rank driver runs
-SLAB_RUNS = {"dam2d": ("2", "bar", 4), "gate2d_sub": ("2", "dam", 2)}
+# (rolling2d: the Rolling wall motion, which the driver takes from MPH_WALL_MOTION)
+SLAB_RUNS = {"dam2d": ("2", "bar", 4), "gate2d_sub": ("2", "dam", 2), "rolling2d": ("2", "dam", 3)}
 
 
 @pytest.mark.gpu
@@ -189,6 +190,8 @@ def test_driver_slab_ranks_match_single_gpu(tmp_path, case):
     write_case(d1, case)
     write_case(dn, case)
     env = dict(os.environ, MPH_DIM=dim, MPH_MODULE=module)
+    if cases.get(case).wall_motion:
+        env["MPH_WALL_MOTION"] = "rolling"
     files_one = run(DRIVER, d1, env)
     files_n = run(DRIVER, dn, dict(env, MPH_SLABS=str(nslabs), MPH_SLAB_TRANSPORT="host", MPH_SLAB_SHARE_DEVICE="1"))
     assert files_n == files_one and len(files_one) >= 6, files_n
