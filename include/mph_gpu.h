@@ -367,6 +367,43 @@ int mph_monitor_sample_doubles(const MphCtx* ctx);
  * many unread samples were overwritten since the last read.  A flush point, like mph_get.        */
 long long mph_monitor_read(MphCtx* ctx, double* out, long long max_samples, long long* lost);
 
+/* ---- per-step monitors on slab ranks ------------------------------------------------------------ */
+
+/* The monitors of a slab context (mph_create_slab and its kin).  The calls above keep refusing one:
+ * what a rank records is a partial sample, and reading a whole one is a collective call.  With slab
+ * monitors on, every slab step ends with the same kernels over the rank's particles and leaves, on a
+ * sampled step, one rank record of MPH_MONITOR_HEAD + 7 ntrack + 2 nprobe doubles in the rank's ring:
+ *   head      MphMonitorSlot over the particles the rank owns at that step (what mph_get returns from
+ *             it), each through the arithmetic of a single context; STEP and TIME as there;
+ *   tracked k {present, x, y, z, vx, vy, vz}: present = 1 and the row on the rank that owns the
+ *             particle at that step, seven zeros on every other rank (indices are original ones of
+ *             the whole problem, [0, n) of mph_particle_count);
+ *   probe q   {value, count} on the rank whose slab holds the probe's coordinate along the slab axis
+ *             (wrapped like a particle's; mph_slab_owner with the context's cuts), which evaluates it
+ *             over its owned particles and its ghosts; {0, -1} on every other rank.
+ * No exchange is added to a step and no rank waits for another.                                    */
+/* mph_monitor_configure for a slab context; every rank passes the same configuration (cfg == NULL:
+ * off).  The same argument rules.  MPH_ERR_UNSUPPORTED on a single context (mph_monitor_configure). */
+int mph_dist_monitor_configure(MphCtx* ctx, const MphMonitorConfig* cfg);
+/* Doubles per rank record; 0 with slab monitors off.                                               */
+int mph_dist_monitor_record_doubles(const MphCtx* ctx);
+/* This rank's unread rank records, oldest first: mph_monitor_read's ring and *lost, no communication. */
+long long mph_dist_monitor_read_partial(MphCtx* ctx, double* out, long long max_samples, long long* lost);
+/* The ranks' records made samples: records[r] is rank r's [nsamples][32 + 7 ntrack + 2 nprobe], out
+ * receives [nsamples][32 + 6 ntrack + 2 nprobe], the layout of mph_monitor_read.  Host only, no
+ * context.  Every head slot combines by its kind -- sum, minimum, maximum -- from rank 0's value
+ * through ranks 1, 2, ... in order, in plain FP64 (EPOT: the ranks' own negated sums); STEP must be the
+ * same on every rank, TIME is rank 0's; a tracked entry is the row of the one rank with present == 1, a
+ * probe the pair of the one rank with count >= 0.  The result is a function of the records and of the
+ * rank order, bit for bit.  MPH_ERR_ARG: unequal STEP, an entry or a probe on no rank or on several. */
+int mph_monitor_combine(int nranks, int ntrack, int nprobe, long long nsamples, const double* const* records,
+                        double* out);
+/* Collective (every rank, with the same max_samples): each rank reads its unread records, rank 0
+ * gathers and combines them and returns the number of samples in out; every other rank returns 0 and
+ * may pass out == NULL only with max_samples == 0.  *lost is the rank's own.  MPH_ERR_TRANSPORT on
+ * rank 0: the ranks' unread counts differ.                                                          */
+long long mph_dist_monitor_read(MphCtx* ctx, double* out, long long max_samples, long long* lost);
+
 /* ---- lattice sampling ------------------------------------------------------------------------- */
 
 /* Fields on a regular lattice without mph_get: the monitors' probe, evaluated on the device at every

@@ -76,6 +76,10 @@ struct MphCtx {
     double* mon_probes = nullptr;
     double* mon_gauges = nullptr;   // the gauge points (mph_gauge_configure), allocated at its first call
     long long mon_read = 0;
+    // slab monitors (mph_dist_monitor_configure): a slab rank's records through the same arguments,
+    // buffers and read count (mon_on stays false: the single-context calls go on refusing a slab
+    // context)
+    bool dmon_on = false;
     // lattice sampling and the elevation map (mph_sample_grid, mph_gauge_grid): the device result buffer (allocated at the first call,
     // regrown when a larger lattice arrives) and whether the sorted set A and pres are the current
     // state's -- a step has run since creation and no mph_set since

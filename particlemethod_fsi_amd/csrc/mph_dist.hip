@@ -37,6 +37,9 @@
 // (main.cpp:653-660) becomes
 //   7. ghost displacements u -> k_struct_stress on the owned slots -> ghost stresses P ->
 //      k_struct_velocity on the owned slots (the last substep writes the owned B entries).
+// With slab monitors on (mph_dist_monitor_configure) a step ends with
+//   8. the monitor kernels over B and the pass-A pressure: this rank's record of the step
+//      (mph_monitor.hip, the slab forms); nothing is exchanged.
 // Transport: RCCL ncclSend/ncclRecv (xGMI) or a host callback (tests, mph_create_dist_host), behind
 // one interface (mph_dist.h, mph_transport.hip).  The slabs themselves: mph_slab_geom.hip; the
 // collective output: mph_dist_output.hip.
@@ -447,11 +450,19 @@ int dist_enqueue_step(MphCtx* c, Profiler* prof, bool early_in, bool early_out)
     MPH_CK(redistribute(c, true, false, prof, early_in));
     sort_local(c, 2, prof);
     launch_search_pass_a(L);
+    // slab monitors: the rank's record of the state this step leaves (what mph_get returns after it),
+    // so behind the substeps and before an early send, whose classify moves the face waves'
+    // particles of B for the next step; on the main stream, both pass-B streams joined
+    const auto monitors = [&] {
+        if (c->dmon_on) launch_dist_monitor(L, c->mon);
+    };
     if (!D.overlap) {   // MPH_SLAB_OVERLAP=0: halo first, then one pass B over every particle
         MPH_CK(halo_exchange(c, prof, c->stream));
         launch_pass_b(L, 0);
-        if (early_out) MPH_CK(early_send(c, prof, c->stream));
-        return struct_substeps(c, prof);
+        if (early_out) MPH_CK(early_send(c, prof, c->stream));   // (never: early_at needs the overlap)
+        MPH_CK(struct_substeps(c, prof));
+        monitors();
+        return MPH_OK;
     }
     // pass B of the wavefronts without ghost neighbours runs on the main stream while, on the
     // second stream, the pass-A halo travels and the wavefronts near a face follow as soon as it
@@ -467,13 +478,14 @@ int dist_enqueue_step(MphCtx* c, Profiler* prof, bool early_in, bool early_out)
     MPH_CK(halo_exchange(c, prof, D.stream2));
     launch_pass_b(L2, 2);
     // joined by the next step's redistribute (ev_s, ev_x)
-    if (early_out && c->P.n_struct == 0) return early_send(c, prof, D.stream2);
+    if (early_out && c->P.n_struct == 0 && !c->dmon_on) return early_send(c, prof, D.stream2);
     MPH_HIP_OK(c, hipEventRecord(D.ev_h, D.stream2));
     MPH_HIP_OK(c, stream_wait(prof, c->stream, D.ev_h, D.stream2));
     MPH_CK(struct_substeps(c, prof));
-    // elastic particles take their positions from the substeps: their face waves are classified
-    // and packed after them (main stream); the messages still travel on the second stream beside
-    // the next step's partition
+    monitors();
+    // elastic particles take their positions from the substeps, and the monitors read B as the step
+    // leaves it: the face waves are classified and packed after them (main stream); the messages
+    // still travel on the second stream beside the next step's partition
     if (early_out) return early_send(c, prof, c->stream);
     return MPH_OK;
 }

@@ -96,6 +96,17 @@ struct StructHook {
 // mph_monitor_configure, passed to the monitor kernels by value.
 constexpr int kMonFirst = 2;      // head slots [kMonFirst, kMonFirst + kMonPartial) are reduced over particles
 constexpr int kMonPartial = 28;   // entries of a block's partial record
+// How entry k of a partial record (head slot kMonFirst + k) combines: 0 sum, 1 min, 2 max -- over the
+// blocks of a launch (mph_monitor.hip) and over the ranks' records (mph_monitor_combine).
+__host__ __device__ constexpr int mon_op(int k)
+{
+    return k < 18 ? (k % 6 == 5 ? 2 : 0) : (k < 24 ? (k % 2 == 0 ? 1 : 2) : (k == 24 ? 1 : (k < 27 ? 2 : 0)));
+}
+// a slab rank's record (mph_dist_monitor_configure): its tracked row {present, x, y, z, vx, vy, vz}
+// (trk holds rows of either length), and where its flag of probe q lies: probes[kMonProbeOwn + q],
+// behind the coordinates, nonzero where this rank's slab holds the probe
+constexpr int kDistMonRow = 7;
+constexpr int kMonProbeOwn = 3 * MPH_MONITOR_MAX_PROBES;
 struct MonitorDev {
     int stride = 1, capacity = 1, ntrack = 0, nprobe = 0;
     int width = 0;                     // doubles per sample
@@ -107,7 +118,7 @@ struct MonitorDev {
     double* prb = nullptr;             // {value, count} per probe
     const int* track_sorted = nullptr; // the distinct tracked ids ascending, padded with INT_MAX to 64
     const int* track_map = nullptr;    // tracked entry k -> its row of trk
-    const double* probes = nullptr;    // [nprobe][3]
+    const double* probes = nullptr;    // [nprobe][3] (and a slab rank's flags, kMonProbeOwn)
     // free-surface gauges (mph_gauge.hip, mph_gauge_configure), behind every older member: a
     // default-constructed MonitorDev is a configuration without gauges
     int ngauge = 0, gauge_axis = 0;
@@ -360,6 +371,8 @@ void launch_select_totals(const Launch& L, const Soa& X, const SelectDev& D, con
 
 int monitor_blocks(int n);   // blocks (partial records) of k_monitor_partial
 void launch_monitor(const Launch& L, const MonitorDev& M);
+// a slab rank's record of the step that has just run on L (mph_dist.hip)
+void launch_dist_monitor(const Launch& L, const MonitorDev& M);
 // the gauges' records of a sampled step into M.gau (launch_monitor calls it; M.ngauge > 0, L.P->n > 0)
 void launch_monitor_gauge(const Launch& L, const MonitorDev& M);
 // the four channels of every line into out ([nz][ny][nx][4], device); L.P->n > 0

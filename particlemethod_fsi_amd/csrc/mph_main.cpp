@@ -20,7 +20,8 @@
 // along MPH_SLAB_AXIS (default z in 3-D, x in 2-D), the transport is RCCL (rank 0 makes the unique
 // id and hands it to the others through pipes) or, with MPH_SLAB_TRANSPORT=host, neighbour
 // exchanges over socket pairs.  Every output call is collective and rank 0 writes the files the
-// single-GPU run writes, with the same cadence.
+// single-GPU run writes, with the same cadence; MPH_DIST_MONITOR is MPH_MONITOR's time history from
+// the ranks' combined records.
 #include <fcntl.h>
 #include <poll.h>
 #include <signal.h>
@@ -310,7 +311,9 @@ int main(int argc, char** argv)
     const bool host_transport = std::getenv("MPH_SLAB_TRANSPORT") && std::strcmp(std::getenv("MPH_SLAB_TRANSPORT"), "host") == 0;
     if (nslabs > 1 && std::getenv("MPH_MONITOR"))   // (before any rank is started)
         die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_MONITOR with MPH_SLABS > 1 (monitors need a single context; "
-                                         "the cross-rank reduction is not built yet)");
+                                         "the slab ranks' combined samples: MPH_DIST_MONITOR)");
+    if (nslabs <= 1 && std::getenv("MPH_DIST_MONITOR"))
+        die(nullptr, MPH_ERR_ARG, "MPH_DIST_MONITOR needs MPH_SLABS > 1 (a single context: MPH_MONITOR)");
     if (nslabs > 1 && std::getenv("MPH_SAMPLE"))
         die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_SAMPLE with MPH_SLABS > 1 (sampling needs a single context)");
     if (nslabs > 1 && (std::getenv("MPH_OUTPUT_SELECT") || std::getenv("MPH_LOADS"))) {
@@ -413,8 +416,12 @@ int main(int argc, char** argv)
         if (rc) die(ctx, rc, "mph_phase_timing");
     }
     const double dt = cfg.dt;
+    // MPH_DIST_MONITOR=<csv path> with MPH_SLABS > 1: the same file from the slab ranks' records
+    // (include/mph_gpu.h mph_dist_monitor_*) -- every rank configures and makes the collective read
+    // where a single context reads its ring, rank 0 receives the combined samples and writes them
     MonitorCsv mon;
-    if (const char* mp = std::getenv("MPH_MONITOR")) {
+    const bool dmon = nslabs > 1 && std::getenv("MPH_DIST_MONITOR");
+    if (const char* mp = std::getenv(dmon ? "MPH_DIST_MONITOR" : "MPH_MONITOR")) {
         if (const char* e = std::getenv("MPH_MONITOR_STRIDE")) mon.stride = std::atoi(e);
         for (double v : parse_numbers(std::getenv("MPH_MONITOR_TRACK"))) mon.track.push_back((int)v);
         mon.probes = parse_numbers(std::getenv("MPH_MONITOR_PROBES"));
@@ -424,6 +431,8 @@ int main(int argc, char** argv)
         // MPH_MONITOR_GAUGE_RADIUS (default 0: RadiusRatioP dx)
         mon.gauges = parse_numbers(std::getenv("MPH_MONITOR_GAUGES"));
         if (mon.gauges.size() % 3 != 0) die(nullptr, MPH_ERR_ARG, "MPH_MONITOR_GAUGES (x,y,z;x,y,z;...)");
+        if (dmon && !mon.gauges.empty())
+            die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_MONITOR_GAUGES with MPH_DIST_MONITOR (gauges need a single context)");
         // the ring holds the samples of the longest batch the loop below issues: a batch ends at the
         // next .prof or .vtk output step or at EndTime
         const double span = std::fmin(std::fmin(cfg.output_interval, cfg.vtk_output_interval), cfg.end_time - cfg.time);
@@ -435,8 +444,8 @@ int main(int argc, char** argv)
         mc.track = mon.track.data();
         mc.nprobe = (int)(mon.probes.size() / 3);
         mc.probes = mon.probes.data();
-        rc = mph_monitor_configure(ctx, &mc);
-        if (rc) die(ctx, rc, "mph_monitor_configure");
+        rc = dmon ? mph_dist_monitor_configure(ctx, &mc) : mph_monitor_configure(ctx, &mc);
+        if (rc) die(ctx, rc, dmon ? "mph_dist_monitor_configure" : "mph_monitor_configure");
         if (!mon.gauges.empty()) {
             MphGaugeConfig gc{};
             gc.axis = std::getenv("MPH_MONITOR_GAUGE_AXIS") ? std::atoi(std::getenv("MPH_MONITOR_GAUGE_AXIS")) : -1;
@@ -446,11 +455,13 @@ int main(int argc, char** argv)
             rc = mph_gauge_configure(ctx, &gc);
             if (rc) die(ctx, rc, "mph_gauge_configure");
         }
-        mon.width = mph_monitor_sample_doubles(ctx);
+        mon.width = dmon ? MPH_MONITOR_HEAD + 6 * mc.ntrack + 2 * mc.nprobe : mph_monitor_sample_doubles(ctx);
         mon.buf.resize((size_t)mc.capacity * mon.width);
-        mon.f = std::fopen(mp, "w");
-        if (!mon.f) die(nullptr, MPH_ERR_IO, "opening the MPH_MONITOR file");
-        monitor_header(mon);
+        if (root) {
+            mon.f = std::fopen(mp, "w");
+            if (!mon.f) die(nullptr, MPH_ERR_IO, "opening the MPH_MONITOR file");
+            monitor_header(mon);
+        }
     }
     // MPH_SAMPLE="ox,oy,oz;sx,sy,sz;nx,ny,nz": at every VTK output step the fields are sampled on
     // that lattice (include/mph_gpu.h mph_sample_grid; MPH_SAMPLE_RADIUS, MPH_SAMPLE_CLASSES
@@ -563,17 +574,19 @@ int main(int argc, char** argv)
         if (rc) die(ctx, rc, "mph_step");
         mph_synchronize(ctx);
         roctxRangePop();
-        if (mon.f) {
+        if (mon.width) {
             long long lost = 0;
-            const long long got = mph_monitor_read(ctx, mon.buf.data(), (long long)(mon.buf.size() / mon.width), &lost);
-            if (got < 0) die(ctx, (int)got, "mph_monitor_read");
+            const long long most = (long long)(mon.buf.size() / mon.width);
+            const long long got = dmon ? mph_dist_monitor_read(ctx, mon.buf.data(), most, &lost)
+                                       : mph_monitor_read(ctx, mon.buf.data(), most, &lost);
+            if (got < 0) die(ctx, (int)got, dmon ? "mph_dist_monitor_read" : "mph_monitor_read");
             if (lost) logf("error: the monitor ring overwrote %lld unread samples (ring sized too small)\n", lost);
             for (long long r = 0; r < got; ++r) {
                 for (int k = 0; k < mon.width; ++k)
                     std::fprintf(mon.f, k ? ",%.17g" : "%.17g", mon.buf[(size_t)r * mon.width + k]);
                 std::fprintf(mon.f, "\n");
             }
-            std::fflush(mon.f);
+            if (mon.f) std::fflush(mon.f);
         }
         // fault injection for the failure-propagation test (tests/test_gpu_driver.py): this rank
         // fails after its first batch

@@ -9,8 +9,14 @@
 // every block of k_monitor_partial owns a fixed range of particles and stores one partial record;
 // k_monitor_final adds the records in a fixed order.  A sample is therefore a function of the state
 // alone, bit for bit, in any batch shape.
+//
+// On a slab rank (mph_dist_monitor_configure; launched by mph_dist.hip at the end of every slab step)
+// the same three kernels run in their SLAB forms and leave the rank's record: the head over the
+// particles the rank owns, a {present, x, y, z, vx, vy, vz} row per tracked entry, the probes its slab
+// holds; mph_monitor_combine (mph_observe.hip) makes samples of the ranks' records on the host.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 
 #include "mph_device.h"
@@ -28,11 +34,7 @@ static_assert(kGroups * kGroups <= 64, "one lane per stencil column of a probe")
 
 int monitor_blocks(int n) { return blocks(n, kMonBlock); }
 
-// Partial record: entry k is head slot kMonFirst + k.  How entry k combines: 0 sum, 1 min, 2 max.
-__host__ __device__ constexpr int mon_op(int k)
-{
-    return k < 18 ? (k % 6 == 5 ? 2 : 0) : (k < 24 ? (k % 2 == 0 ? 1 : 2) : (k == 24 ? 1 : (k < 27 ? 2 : 0)));
-}
+// Partial record: entry k is head slot kMonFirst + k; mon_op(k) (mph_kernels.h) says how it combines.
 // Identity of entry k (VMAX2 of an empty class is 0: v.v >= 0)
 __device__ __forceinline__ double mon_init(int k)
 {
@@ -75,6 +77,12 @@ __device__ __forceinline__ double mon_block_reduce(double (&sum)[kMonSums], doub
 
 // One partial record per block over its kMonBlock particles of the integrated set B (in the sorted
 // order of this step, as `pres`), and the tracked particles' rows.
+// SLAB, a slab rank's record (launch_dist_monitor): B is [owned | ghosts], n is the capacity the grid
+// is sized for and the live count is read here.  Only the owned particles count: a ghost (id < 0) is
+// skipped like a slot past n, so an owned particle goes through the arithmetic of a single context,
+// in the order of B.  A block past the live count stores the identities (k_monitor_final adds every
+// record of the grid).  A tracked row is {present, x, y, z, vx, vy, vz}.
+template <bool SLAB>
 __global__ __launch_bounds__(kMonThreads) void k_monitor_partial(DevParams P, MonitorDev M, int n, Soa B,
                                                                  const double* __restrict__ pres)
 {
@@ -85,6 +93,13 @@ __global__ __launch_bounds__(kMonThreads) void k_monitor_partial(DevParams P, Mo
     __shared__ double s_mass[kTypes];
     __shared__ double s_red[kMonWaves][kMonPartial];
     const int tid = threadIdx.x;
+    if (SLAB) {
+        n = dev_n(P);
+        if (blockIdx.x * kMonBlock >= n) {
+            if (tid < kMonPartial) M.partial[(size_t)blockIdx.x * kMonPartial + tid] = mon_init(tid);
+            return;
+        }
+    }
     if (tid < MPH_MONITOR_MAX_TRACK) s_ids[tid] = M.track_sorted[tid];
     if (tid < kTypes) s_mass[tid] = P.mass[tid];
     __syncthreads();
@@ -102,6 +117,7 @@ __global__ __launch_bounds__(kMonThreads) void k_monitor_partial(DevParams P, Mo
             pr[it] = pres[p];
             ty[it] = B.type[p];
             id[it] = B.id[p];
+            if (SLAB && id[it] < 0) ty[it] = -1;
         }
     }
     double sum[kMonSums], mn[kMonMins], mx[kMonMaxs];
@@ -146,7 +162,8 @@ __global__ __launch_bounds__(kMonThreads) void k_monitor_partial(DevParams P, Mo
             for (int w = MPH_MONITOR_MAX_TRACK / 2; w > 0; w >>= 1)
                 if (s_ids[lo + w - 1] < id[it]) lo += w;
             if (s_ids[lo] == id[it]) {
-                double* o = M.trk + 6 * lo;
+                double* o = M.trk + (SLAB ? kDistMonRow * lo + 1 : 6 * lo);
+                if (SLAB) o[-1] = 1.0;
                 o[0] = x[it]; o[1] = y[it]; o[2] = z[it];
                 o[3] = vx[it]; o[4] = vy[it]; o[5] = vz[it];
             }
@@ -160,7 +177,11 @@ __global__ __launch_bounds__(kMonThreads) void k_monitor_partial(DevParams P, Mo
 // set A (the positions PressureP was computed at) within M.probe_h of the probe.  Lane c takes
 // stencil column c: along the contiguous axis its cells are one index range of start[], two where
 // the column wraps; the lanes then stride the concatenated runs.
-template <int DIM>
+// SLAB: only on the rank that owns the probe (the flag behind the probes, kMonProbeOwn).  A is the
+// rank's sorted set, owned and ghosts, on its window grid, which is not periodic along the slab axis:
+// there the stencil is clipped at the window's two ends instead of wrapped (a cell past an end would
+// be one from the window's other end, not the domain's).  The distance stays the minimum image.
+template <int DIM, bool SLAB>
 __global__ __launch_bounds__(64) void k_monitor_probe(DevParams P, MonitorDev M, int n, Soa A,
                                                       const int* __restrict__ start,
                                                       const double* __restrict__ pres)
@@ -171,14 +192,33 @@ __global__ __launch_bounds__(64) void k_monitor_probe(DevParams P, MonitorDev M,
     constexpr int kSeg = 128;   // two runs per lane
     __shared__ int s_off[kSeg], s_beg[kSeg];
     const int q = blockIdx.x, lane = threadIdx.x;
+    if (SLAB) {
+        if (M.probes[kMonProbeOwn + q] == 0.0) return;
+        n = dev_n(P);
+    }
     // the probe, wrapped into the periodic domain like a particle
     const double pq[3] = {M.probes[3 * q], M.probes[3 * q + 1], DIM == 3 ? M.probes[3 * q + 2] : 0.0};
     double p[3];
     wrap_point(P, DIM, pq, p);
     // lane c's column of the probe's stencil: one run of start[], two where the column wraps
-    const PointStencil<DIM> S(P, p);
+    PointStencil<DIM> S(P, p);
+    bool column = lane < PointStencil<DIM>::ncol;
+    if (SLAB) {
+        const int ax = P.slab_axis, g = ax == 0 ? P.gc[0] : (ax == 1 ? P.gc[1] : P.gc[2]);
+        const int cc = ax == 0 ? S.c[0] : (ax == 1 ? S.c[1] : S.c[2]);
+        if (ax == S.ca) {
+            S.lo = max(cc - P.sa, 0);
+            S.hi = min(cc + P.sa, g - 1);
+            S.lo1 = 0;
+            S.hi1 = -1;
+        } else {
+            // (the column's offset along the slab axis, as PointStencil::column takes it)
+            const int d = (ax == S.a0 ? (DIM == 3 ? lane / kGroups : lane) : lane % kGroups) - kReach;
+            column = column && cc + d >= 0 && cc + d < g;
+        }
+    }
     int b0 = 0, len0 = 0, b1 = 0, len1 = 0;
-    if (lane < PointStencil<DIM>::ncol) {
+    if (column) {
         const int cell0 = S.column(P, lane);
         b0 = start[cell0 + S.lo];
         len0 = start[cell0 + S.hi + 1] - b0;
@@ -235,7 +275,14 @@ __global__ __launch_bounds__(64) void k_monitor_probe(DevParams P, MonitorDev M,
 // the counters advanced.  Thread (g, k) of 32 groups of 32 takes entry k of the records g, g + 32,
 // ... (a record's 28 entries are one contiguous read), then thread k the 32 groups' results in
 // order.  The only writer of the counters, on every step.
+// SLAB: the rank record -- the head over the owned particles (nb: every block of the capacity-sized
+// grid; those past the live count hold the identities, so a record's place in the order is the one it
+// has among the live blocks), {present, x, y, z, vx, vy, vz} per tracked entry, all zero unless the
+// particle is owned here at this step (the rows are cleared behind the read), {value, count} per probe
+// owned here and {0, -1} per other probe.
 constexpr int kMonFinalThreads = 1024, kMonGroups = kMonFinalThreads / 32;
+static_assert(kDistMonRow * MPH_MONITOR_MAX_TRACK <= kMonFinalThreads, "one thread per double of the tracked rows");
+template <bool SLAB>
 __global__ __launch_bounds__(kMonFinalThreads) void k_monitor_final(MonitorDev M, int nb,
                                                                     const DevState* __restrict__ st)
 {
@@ -273,16 +320,18 @@ __global__ __launch_bounds__(kMonFinalThreads) void k_monitor_final(MonitorDev M
             out[1] = st->time;
             for (int e = kMonFirst + kMonPartial; e < MPH_MONITOR_HEAD; ++e) out[e] = 0.0;
         }
+        constexpr int row = SLAB ? kDistMonRow : 6;
         if (tid < M.ntrack) {
-            const double* r = M.trk + 6 * M.track_map[tid];
-            for (int e = 0; e < 6; ++e) out[MPH_MONITOR_HEAD + 6 * tid + e] = r[e];
+            const double* r = M.trk + row * M.track_map[tid];
+            for (int e = 0; e < row; ++e) out[MPH_MONITOR_HEAD + row * tid + e] = r[e];
         }
         if (tid < M.nprobe) {
-            out[MPH_MONITOR_HEAD + 6 * M.ntrack + 2 * tid] = M.prb[2 * tid];
-            out[MPH_MONITOR_HEAD + 6 * M.ntrack + 2 * tid + 1] = M.prb[2 * tid + 1];
+            const bool mine = !SLAB || M.probes[kMonProbeOwn + tid] != 0.0;
+            out[MPH_MONITOR_HEAD + row * M.ntrack + 2 * tid] = mine ? M.prb[2 * tid] : 0.0;
+            out[MPH_MONITOR_HEAD + row * M.ntrack + 2 * tid + 1] = mine ? M.prb[2 * tid + 1] : -1.0;
         }
         // the gauges' records (k_monitor_gauge, mph_gauge.hip) behind the probes
-        if (tid < MPH_GAUGE_CHANNELS * M.ngauge)
+        if (!SLAB && tid < MPH_GAUGE_CHANNELS * M.ngauge)
             out[MPH_MONITOR_HEAD + 6 * M.ntrack + 2 * M.nprobe + tid] = M.gau[tid];
     }
     __syncthreads();   // every thread has read the counters
@@ -290,6 +339,8 @@ __global__ __launch_bounds__(kMonFinalThreads) void k_monitor_final(MonitorDev M
         M.counters[0] = step;
         if (sampled) M.counters[1] += 1;
     }
+    // (and the tracked rows: a particle that has left the rank leaves no row behind)
+    if (SLAB && sampled && tid < kDistMonRow * MPH_MONITOR_MAX_TRACK) M.trk[tid] = 0.0;
 }
 
 void launch_monitor(const Launch& L, const MonitorDev& M)
@@ -298,15 +349,33 @@ void launch_monitor(const Launch& L, const MonitorDev& M)
     const int n = P.n;
     if (n == 0) return;
     const int nb = monitor_blocks(n);
-    launch(L.prof, "monitor_partial", L.stream, k_monitor_partial, dim3(nb), dim3(kMonThreads), P, M, n, L.B,
+    launch(L.prof, "monitor_partial", L.stream, k_monitor_partial<false>, dim3(nb), dim3(kMonThreads), P, M, n, L.B,
            L.pres);
     if (M.nprobe > 0)
         by_dim(P.dim, [&](auto D) {
-            launch(L.prof, "monitor_probe", L.stream, k_monitor_probe<decltype(D)::value>, dim3(M.nprobe), dim3(64),
-                   P, M, n, L.A, L.start, L.pres);
+            launch(L.prof, "monitor_probe", L.stream, k_monitor_probe<decltype(D)::value, false>, dim3(M.nprobe),
+                   dim3(64), P, M, n, L.A, L.start, L.pres);
         });
     if (M.ngauge > 0) launch_monitor_gauge(L, M);
-    launch(L.prof, "monitor_final", L.stream, k_monitor_final, dim3(1), dim3(kMonFinalThreads), M, nb, L.st);
+    launch(L.prof, "monitor_final", L.stream, k_monitor_final<false>, dim3(1), dim3(kMonFinalThreads), M, nb, L.st);
+}
+
+// A slab rank's record of the step that has just run on L (mph_dist_monitor_configure): the same
+// three launches in their slab forms.  The grids are sized for the capacity L.P->n (at least one
+// block); the kernels read the live count.  k_monitor_final, the only writer of the counters, runs on
+// every step, whatever the rank holds.
+void launch_dist_monitor(const Launch& L, const MonitorDev& M)
+{
+    const DevParams& P = *L.P;
+    const int n = P.n, nb = std::max(monitor_blocks(n), 1);
+    launch(L.prof, "monitor_partial", L.stream, k_monitor_partial<true>, dim3(nb), dim3(kMonThreads), P, M, n, L.B,
+           L.pres);
+    if (M.nprobe > 0)
+        by_dim(P.dim, [&](auto D) {
+            launch(L.prof, "monitor_probe", L.stream, k_monitor_probe<decltype(D)::value, true>, dim3(M.nprobe),
+                   dim3(64), P, M, n, L.A, L.start, L.pres);
+        });
+    launch(L.prof, "monitor_final", L.stream, k_monitor_final<true>, dim3(1), dim3(kMonFinalThreads), M, nb, L.st);
 }
 
 }  // namespace mph

@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "mph_ctx.h"
+#include "mph_dist.h"
 #include "mph_env.h"
 
 using namespace mph;
@@ -65,83 +65,9 @@ static int gauge_resolve(MphCtx* c, int axis, double radius, int* ax, double* h,
     return MPH_OK;
 }
 
-extern "C" {
-
-// ---- per-step monitors (kernels: mph_monitor.hip) ----------------------------------------------
-
-int mph_monitor_configure(MphCtx* c, const MphMonitorConfig* m)
+// the unread samples of the ring, oldest first (mph_monitor_read, mph_dist_monitor_read_partial)
+static long long monitor_read_ring(MphCtx* c, double* out, long long max_samples, long long* lost)
 {
-    if (!c) return MPH_ERR_ARG;
-    MPH_CK(ctx_flush(c));
-    if (c->dist)
-        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "monitors are not available in slab mode (no cross-rank reduction yet)");
-    MPH_HIP_OK(c, hipSetDevice(c->device));
-    if (!m) {
-        if (c->mon_on) MPH_CK(drop_graphs(c));
-        c->mon_on = false;
-        c->L.mon = nullptr;
-        return MPH_OK;
-    }
-    if (m->stride < 1 || m->capacity < 1) return ctx_fail(c, MPH_ERR_ARG, "monitors: stride and capacity must be >= 1");
-    if (m->ntrack < 0 || m->ntrack > MPH_MONITOR_MAX_TRACK || (m->ntrack > 0 && !m->track))
-        return ctx_fail(c, MPH_ERR_ARG, "monitors: 0.." + std::to_string(MPH_MONITOR_MAX_TRACK) + " tracked particles");
-    if (m->nprobe < 0 || m->nprobe > MPH_MONITOR_MAX_PROBES || (m->nprobe > 0 && !m->probes))
-        return ctx_fail(c, MPH_ERR_ARG, "monitors: 0.." + std::to_string(MPH_MONITOR_MAX_PROBES) + " probes");
-    for (int k = 0; k < m->ntrack; ++k)
-        if (m->track[k] < 0 || m->track[k] >= c->n_glob)
-            return ctx_fail(c, MPH_ERR_ARG, "monitors: tracked index " + std::to_string(m->track[k]) + " outside [0, n)");
-    const double reach = c->h.max_radius + 0.1 * c->h.dx;   // MaxRadius + MARGIN (make_dev_params)
-    if (!(m->probe_radius >= 0.0) || m->probe_radius > reach)
-        return ctx_fail(c, MPH_ERR_ARG, "monitors: probe radius outside [0, MaxRadius + MARGIN = " + std::to_string(reach) + "]");
-    MPH_CK(drop_graphs(c));
-    MonitorDev& D = c->mon;
-    if (!D.counters) {   // once, for the maxima
-        MPH_CK(ctx_dalloc(c, &D.counters, 2));
-        MPH_CK(ctx_dalloc(c, &D.partial, (size_t)kMonPartial * monitor_blocks(c->n)));
-        MPH_CK(ctx_dalloc(c, &D.trk, 6 * (size_t)MPH_MONITOR_MAX_TRACK));
-        MPH_CK(ctx_dalloc(c, &D.prb, 2 * (size_t)MPH_MONITOR_MAX_PROBES));
-        MPH_CK(ctx_dalloc(c, &c->mon_sorted, MPH_MONITOR_MAX_TRACK));
-        MPH_CK(ctx_dalloc(c, &c->mon_map, MPH_MONITOR_MAX_TRACK));
-        MPH_CK(ctx_dalloc(c, &c->mon_probes, 3 * (size_t)MPH_MONITOR_MAX_PROBES));
-        D.track_sorted = c->mon_sorted;
-        D.track_map = c->mon_map;
-        D.probes = c->mon_probes;
-    }
-    // (the whole configuration is replaced: no gauges until the next mph_gauge_configure)
-    MPH_CK(monitor_ring(c, m->capacity, MPH_MONITOR_HEAD + 6 * m->ntrack + 2 * m->nprobe));
-    D.ngauge = 0;
-    // the distinct tracked ids ascending (the kernel's search), and each entry's row among them
-    std::vector<int> sorted(m->track, m->track + m->ntrack);
-    std::sort(sorted.begin(), sorted.end());
-    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
-    std::vector<int> map(MPH_MONITOR_MAX_TRACK, 0);
-    for (int k = 0; k < m->ntrack; ++k)
-        map[k] = (int)(std::lower_bound(sorted.begin(), sorted.end(), m->track[k]) - sorted.begin());
-    sorted.resize(MPH_MONITOR_MAX_TRACK, 0x7fffffff);
-    std::vector<double> probes(3 * (size_t)MPH_MONITOR_MAX_PROBES, 0.0);
-    std::copy(m->probes, m->probes + 3 * (size_t)m->nprobe, probes.begin());
-    MPH_HIP_OK(c, hipMemcpy(c->mon_sorted, sorted.data(), sizeof(int) * sorted.size(), hipMemcpyHostToDevice));
-    MPH_HIP_OK(c, hipMemcpy(c->mon_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
-    MPH_HIP_OK(c, hipMemcpy(c->mon_probes, probes.data(), sizeof(double) * probes.size(), hipMemcpyHostToDevice));
-    MPH_HIP_OK(c, hipMemset(D.trk, 0, sizeof(double) * 6 * MPH_MONITOR_MAX_TRACK));
-    MPH_HIP_OK(c, hipMemset(D.prb, 0, sizeof(double) * 2 * MPH_MONITOR_MAX_PROBES));
-    D.stride = m->stride;
-    D.ntrack = m->ntrack;
-    D.nprobe = m->nprobe;
-    D.probe_h = m->probe_radius > 0.0 ? m->probe_radius : c->h.rp;
-    c->mon_on = true;
-    c->L.mon = &c->mon;
-    return MPH_OK;
-}
-
-int mph_monitor_sample_doubles(const MphCtx* c) { return c && c->mon_on ? c->mon.width : 0; }
-
-long long mph_monitor_read(MphCtx* c, double* out, long long max_samples, long long* lost)
-{
-    if (!c || max_samples < 0 || (max_samples > 0 && !out)) return MPH_ERR_ARG;
-    if (lost) *lost = 0;
-    MPH_CK(ctx_flush(c));
-    if (!c->mon_on) return 0;
     MPH_HIP_OK(c, hipSetDevice(c->device));
     MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
     const MonitorDev& D = c->mon;
@@ -160,6 +86,228 @@ long long mph_monitor_read(MphCtx* c, double* out, long long max_samples, long l
         i += run;
     }
     c->mon_read = first + k;
+    return k;
+}
+
+// What mph_monitor_configure and mph_dist_monitor_configure share: the argument rules, then the
+// buffers (once, for the maxima of either), the emptied ring of `capacity` samples of head + `row`
+// doubles per tracked entry + 2 per probe, and the uploaded configuration in c->mon.
+static int monitor_setup(MphCtx* c, const MphMonitorConfig* m, int row)
+{
+    if (m->stride < 1 || m->capacity < 1) return ctx_fail(c, MPH_ERR_ARG, "monitors: stride and capacity must be >= 1");
+    if (m->ntrack < 0 || m->ntrack > MPH_MONITOR_MAX_TRACK || (m->ntrack > 0 && !m->track))
+        return ctx_fail(c, MPH_ERR_ARG, "monitors: 0.." + std::to_string(MPH_MONITOR_MAX_TRACK) + " tracked particles");
+    if (m->nprobe < 0 || m->nprobe > MPH_MONITOR_MAX_PROBES || (m->nprobe > 0 && !m->probes))
+        return ctx_fail(c, MPH_ERR_ARG, "monitors: 0.." + std::to_string(MPH_MONITOR_MAX_PROBES) + " probes");
+    for (int k = 0; k < m->ntrack; ++k)
+        if (m->track[k] < 0 || m->track[k] >= c->n_glob)
+            return ctx_fail(c, MPH_ERR_ARG, "monitors: tracked index " + std::to_string(m->track[k]) + " outside [0, n)");
+    const double reach = c->h.max_radius + 0.1 * c->h.dx;   // MaxRadius + MARGIN (make_dev_params)
+    if (!(m->probe_radius >= 0.0) || m->probe_radius > reach)
+        return ctx_fail(c, MPH_ERR_ARG, "monitors: probe radius outside [0, MaxRadius + MARGIN = " + std::to_string(reach) + "]");
+    MPH_CK(drop_graphs(c));
+    MonitorDev& D = c->mon;
+    if (!D.counters) {   // once, for the maxima
+        MPH_CK(ctx_dalloc(c, &D.counters, 2));
+        // (a slab rank's launches are sized for its capacity; its tracked rows are the longer ones)
+        MPH_CK(ctx_dalloc(c, &D.partial, (size_t)kMonPartial * monitor_blocks(c->dist ? c->dist->cap : c->n)));
+        MPH_CK(ctx_dalloc(c, &D.trk, kDistMonRow * (size_t)MPH_MONITOR_MAX_TRACK));
+        MPH_CK(ctx_dalloc(c, &D.prb, 2 * (size_t)MPH_MONITOR_MAX_PROBES));
+        MPH_CK(ctx_dalloc(c, &c->mon_sorted, MPH_MONITOR_MAX_TRACK));
+        MPH_CK(ctx_dalloc(c, &c->mon_map, MPH_MONITOR_MAX_TRACK));
+        MPH_CK(ctx_dalloc(c, &c->mon_probes, kMonProbeOwn + (size_t)MPH_MONITOR_MAX_PROBES));
+        D.track_sorted = c->mon_sorted;
+        D.track_map = c->mon_map;
+        D.probes = c->mon_probes;
+    }
+    // (the whole configuration is replaced: no gauges until the next mph_gauge_configure)
+    MPH_CK(monitor_ring(c, m->capacity, MPH_MONITOR_HEAD + row * m->ntrack + 2 * m->nprobe));
+    D.ngauge = 0;
+    // the distinct tracked ids ascending (the kernel's search), and each entry's row among them
+    std::vector<int> sorted(m->track, m->track + m->ntrack);
+    std::sort(sorted.begin(), sorted.end());
+    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+    std::vector<int> map(MPH_MONITOR_MAX_TRACK, 0);
+    for (int k = 0; k < m->ntrack; ++k)
+        map[k] = (int)(std::lower_bound(sorted.begin(), sorted.end(), m->track[k]) - sorted.begin());
+    sorted.resize(MPH_MONITOR_MAX_TRACK, 0x7fffffff);
+    std::vector<double> probes(3 * (size_t)MPH_MONITOR_MAX_PROBES, 0.0);
+    std::copy(m->probes, m->probes + 3 * (size_t)m->nprobe, probes.begin());
+    MPH_HIP_OK(c, hipMemcpy(c->mon_sorted, sorted.data(), sizeof(int) * sorted.size(), hipMemcpyHostToDevice));
+    MPH_HIP_OK(c, hipMemcpy(c->mon_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
+    MPH_HIP_OK(c, hipMemcpy(c->mon_probes, probes.data(), sizeof(double) * probes.size(), hipMemcpyHostToDevice));
+    MPH_HIP_OK(c, hipMemset(D.trk, 0, sizeof(double) * kDistMonRow * MPH_MONITOR_MAX_TRACK));
+    MPH_HIP_OK(c, hipMemset(D.prb, 0, sizeof(double) * 2 * MPH_MONITOR_MAX_PROBES));
+    D.stride = m->stride;
+    D.ntrack = m->ntrack;
+    D.nprobe = m->nprobe;
+    D.probe_h = m->probe_radius > 0.0 ? m->probe_radius : c->h.rp;
+    return MPH_OK;
+}
+
+extern "C" {
+
+// ---- per-step monitors (kernels: mph_monitor.hip) ----------------------------------------------
+
+int mph_monitor_configure(MphCtx* c, const MphMonitorConfig* m)
+{
+    if (!c) return MPH_ERR_ARG;
+    MPH_CK(ctx_flush(c));
+    if (c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "monitors are not available in slab mode: a rank's record is a partial "
+                                                "one (mph_dist_monitor_configure)");
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    if (!m) {
+        if (c->mon_on) MPH_CK(drop_graphs(c));
+        c->mon_on = false;
+        c->L.mon = nullptr;
+        return MPH_OK;
+    }
+    MPH_CK(monitor_setup(c, m, 6));
+    c->mon_on = true;
+    c->L.mon = &c->mon;
+    return MPH_OK;
+}
+
+int mph_monitor_sample_doubles(const MphCtx* c) { return c && c->mon_on ? c->mon.width : 0; }
+
+long long mph_monitor_read(MphCtx* c, double* out, long long max_samples, long long* lost)
+{
+    if (!c || max_samples < 0 || (max_samples > 0 && !out)) return MPH_ERR_ARG;
+    if (lost) *lost = 0;
+    MPH_CK(ctx_flush(c));
+    if (!c->mon_on) return 0;
+    return monitor_read_ring(c, out, max_samples, lost);
+}
+
+// ---- slab monitors: rank records and their combine (kernels: mph_monitor.hip, the slab forms) -----
+
+int mph_dist_monitor_configure(MphCtx* c, const MphMonitorConfig* m)
+{
+    if (!c) return MPH_ERR_ARG;
+    MPH_CK(ctx_flush(c));
+    if (!c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "slab monitors need a slab context (a single context: mph_monitor_configure)");
+    MPH_HIP_OK(c, hipSetDevice(c->device));
+    if (!m) {
+        if (c->dmon_on) MPH_CK(drop_graphs(c));
+        c->dmon_on = false;
+        return MPH_OK;
+    }
+    // (a probe's radius is at most MaxRadius + MARGIN = sqrt(rc2) up to its rounding, below the halo
+    // sqrt(rc2) (1 + 1e-6): the owner's ghosts hold every particle within it of a point of its slab)
+    MPH_CK(monitor_setup(c, m, kDistMonRow));
+    // who evaluates a probe: the rank whose slab holds its coordinate, wrapped like a particle's --
+    // decided here, once, with the context's cuts; the kernels take the verdict as a flag
+    const MphDist& D = *c->dist;
+    std::vector<double> own(MPH_MONITOR_MAX_PROBES, 0.0);
+    for (int q = 0; q < m->nprobe; ++q)
+        own[q] = owner_rank(c->h, D.g.axis, D.nranks, dist_cuts(D), m->probes[3 * q + D.g.axis]) == D.rank ? 1.0 : 0.0;
+    MPH_HIP_OK(c, hipMemcpy(c->mon_probes + kMonProbeOwn, own.data(), sizeof(double) * own.size(), hipMemcpyHostToDevice));
+    c->dmon_on = true;
+    return MPH_OK;
+}
+
+int mph_dist_monitor_record_doubles(const MphCtx* c) { return c && c->dmon_on ? c->mon.width : 0; }
+
+long long mph_dist_monitor_read_partial(MphCtx* c, double* out, long long max_samples, long long* lost)
+{
+    if (!c || max_samples < 0 || (max_samples > 0 && !out)) return MPH_ERR_ARG;
+    if (lost) *lost = 0;
+    MPH_CK(ctx_flush(c));
+    if (!c->dmon_on) return 0;
+    return monitor_read_ring(c, out, max_samples, lost);
+}
+
+int mph_monitor_combine(int nranks, int ntrack, int nprobe, long long nsamples, const double* const* records,
+                        double* out)
+{
+#pragma clang fp contract(off)
+    if (nranks < 1 || ntrack < 0 || ntrack > MPH_MONITOR_MAX_TRACK || nprobe < 0 || nprobe > MPH_MONITOR_MAX_PROBES ||
+        nsamples < 0 || !records || (nsamples > 0 && !out))
+        return MPH_ERR_ARG;
+    for (int r = 0; r < nranks && nsamples > 0; ++r)
+        if (!records[r]) return MPH_ERR_ARG;
+    const size_t wr = MPH_MONITOR_HEAD + (size_t)kDistMonRow * ntrack + 2 * (size_t)nprobe;
+    const size_t wo = MPH_MONITOR_HEAD + 6 * (size_t)ntrack + 2 * (size_t)nprobe;
+    for (long long s = 0; s < nsamples; ++s) {
+        const auto rec = [&](int r) { return records[r] + (size_t)s * wr; };
+        double* o = out + (size_t)s * wo;
+        for (int r = 1; r < nranks; ++r)
+            if (rec(r)[MPH_MON_STEP] != rec(0)[MPH_MON_STEP]) return MPH_ERR_ARG;
+        o[MPH_MON_STEP] = rec(0)[MPH_MON_STEP];
+        o[MPH_MON_TIME] = rec(0)[MPH_MON_TIME];
+        // rank 0's value, then ranks 1, 2, ... in order (EPOT: each rank's own negated sum)
+        for (int k = 0; k < kMonPartial; ++k) {
+            double v = rec(0)[kMonFirst + k];
+            for (int r = 1; r < nranks; ++r) {
+                const double a = rec(r)[kMonFirst + k];
+                v = mon_op(k) == 0 ? v + a : (mon_op(k) == 1 ? std::fmin(v, a) : std::fmax(v, a));
+            }
+            o[kMonFirst + k] = v;
+        }
+        for (int e = kMonFirst + kMonPartial; e < MPH_MONITOR_HEAD; ++e) o[e] = 0.0;
+        // a tracked entry from the one rank that holds the particle, a probe from the one that owns it
+        for (int k = 0; k < ntrack; ++k) {
+            int from = -1, count = 0;
+            for (int r = 0; r < nranks; ++r)
+                if (rec(r)[MPH_MONITOR_HEAD + kDistMonRow * k] == 1.0) {
+                    from = r;
+                    ++count;
+                }
+            if (count != 1) return MPH_ERR_ARG;
+            for (int e = 0; e < 6; ++e) o[MPH_MONITOR_HEAD + 6 * k + e] = rec(from)[MPH_MONITOR_HEAD + kDistMonRow * k + 1 + e];
+        }
+        for (int q = 0; q < nprobe; ++q) {
+            int from = -1, count = 0;
+            for (int r = 0; r < nranks; ++r)
+                if (rec(r)[MPH_MONITOR_HEAD + kDistMonRow * ntrack + 2 * q + 1] >= 0.0) {
+                    from = r;
+                    ++count;
+                }
+            if (count != 1) return MPH_ERR_ARG;
+            for (int e = 0; e < 2; ++e)
+                o[MPH_MONITOR_HEAD + 6 * ntrack + 2 * q + e] = rec(from)[MPH_MONITOR_HEAD + kDistMonRow * ntrack + 2 * q + e];
+        }
+    }
+    return MPH_OK;
+}
+
+long long mph_dist_monitor_read(MphCtx* c, double* out, long long max_samples, long long* lost)
+{
+    if (!c || max_samples < 0 || (max_samples > 0 && !out)) return MPH_ERR_ARG;
+    if (lost) *lost = 0;
+    MPH_CK(ctx_flush(c));
+    if (!c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "slab monitors need a slab context (a single context: mph_monitor_read)");
+    if (!c->dmon_on) return 0;
+    MphDist& D = *c->dist;
+    const size_t w = (size_t)c->mon.width;
+    // this rank's message: its count, then its records
+    std::vector<double> rows((size_t)std::min<long long>(max_samples, c->mon.capacity) * w + 1);
+    const long long k = monitor_read_ring(c, rows.data() + 1, max_samples, lost);
+    if (k < 0) return k;
+    static_assert(sizeof(long long) == sizeof(double), "the count travels in a record's slot");
+    std::memcpy(rows.data(), &k, sizeof(k));
+    const char* b = reinterpret_cast<const char*>(rows.data());
+    std::vector<char> mine(b, b + sizeof(double) * (1 + (size_t)k * w)), all;
+    MPH_CK(D.tr->gather_root(c, c->stream, mine, all));
+    if (D.rank != 0) return 0;
+    std::vector<double> recs(all.size() / sizeof(double));
+    if (!all.empty()) std::memcpy(recs.data(), all.data(), recs.size() * sizeof(double));
+    std::vector<const double*> of(D.nranks);
+    size_t at = 0;
+    for (int r = 0; r < D.nranks; ++r) {
+        long long kr = -1;
+        if (at < recs.size()) std::memcpy(&kr, &recs[at], sizeof(kr));
+        if (kr != k || at + 1 + (size_t)k * w > recs.size())
+            return ctx_fail(c, MPH_ERR_TRANSPORT, "slab monitors: rank " + std::to_string(r) + " holds " + std::to_string(kr) +
+                                                      " unread records, rank 0 " + std::to_string(k));
+        of[r] = recs.data() + at + 1;
+        at += 1 + (size_t)k * w;
+    }
+    const int rc = mph_monitor_combine(D.nranks, c->mon.ntrack, c->mon.nprobe, k, of.data(), out);
+    if (rc != MPH_OK) return ctx_fail(c, rc, "slab monitors: the ranks' records do not combine (a tracked particle or a probe on no rank or on several, or unequal steps)");
     return k;
 }
 

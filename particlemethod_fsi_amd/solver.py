@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = [
     "mph_write_vtu_kinematics_arrays", "mph_compute_kinematics", "mph_compute_kinematics_timed",
     "mph_get_kinematics", "mph_get_kinematics_selected", "mph_write_vtu_kinematics",
     "mph_write_vtu_kinematics_selected",
+    "mph_dist_monitor_configure", "mph_dist_monitor_record_doubles", "mph_dist_monitor_read_partial",
+    "mph_monitor_combine", "mph_dist_monitor_read",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -287,6 +289,21 @@ def monitor_gauges(row: np.ndarray, ntrack: int, nprobe: int, ngauge: int):
     return row[..., b:].reshape(row.shape[:-1] + (ngauge, len(GAUGE_CHANNELS)))
 
 
+def monitor_combine(records, ntrack: int, nprobe: int) -> np.ndarray:
+    """mph_monitor_combine: the slab ranks' records (records[r]: rank r's [k, 32 + 7 ntrack + 2 nprobe],
+    MphSolver.dist_monitor_read_partial) -> the samples [k, 32 + 6 ntrack + 2 nprobe] that
+    monitor_split reads.  Host only; a function of the records and of the rank order, bit for bit."""
+    recs = [np.ascontiguousarray(r, np.float64) for r in records]
+    w = MONITOR_HEAD + 7 * ntrack + 2 * nprobe
+    if not recs or any(r.ndim != 2 or r.shape != (recs[0].shape[0], w) for r in recs):
+        raise ValueError("every rank's records must be [k, %d] with the same k" % w)
+    k = recs[0].shape[0]
+    out = np.zeros((k, MONITOR_HEAD + 6 * ntrack + 2 * nprobe))
+    ptrs = (ctypes.c_void_p * len(recs))(*[r.ctypes.data for r in recs])
+    _check(load_library().mph_monitor_combine(len(recs), int(ntrack), int(nprobe), k, ptrs, out.ctypes.data))
+    return out
+
+
 class MphError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__("%s (%d): %s" % (STATUS.get(code, "?"), code, msg))
@@ -404,6 +421,12 @@ def load_library() -> ctypes.CDLL:
         "mph_get_kinematics_selected": (ip, [vp, vp]),
         "mph_write_vtu_kinematics": (ip, [vp, ctypes.c_char_p]),
         "mph_write_vtu_kinematics_selected": (ip, [vp, ctypes.c_char_p]),
+        "mph_dist_monitor_configure": (ip, [vp, ctypes.POINTER(MphMonitorConfig)]),
+        "mph_dist_monitor_record_doubles": (ip, [vp]),
+        "mph_dist_monitor_read_partial": (ctypes.c_longlong, [vp, vp, ctypes.c_longlong,
+                                                              ctypes.POINTER(ctypes.c_longlong)]),
+        "mph_monitor_combine": (ip, [ip, ip, ip, ctypes.c_longlong, vp, vp]),
+        "mph_dist_monitor_read": (ctypes.c_longlong, [vp, vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
@@ -418,7 +441,9 @@ def load_library() -> ctypes.CDLL:
                 "mph_kinematics_layout", "mph_kinematics_parse", "mph_kinematics_n0", "mph_kinematics_arrays",
                 "mph_write_vtu_kinematics_arrays", "mph_compute_kinematics", "mph_compute_kinematics_timed",
                 "mph_get_kinematics", "mph_get_kinematics_selected", "mph_write_vtu_kinematics",
-                "mph_write_vtu_kinematics_selected"}
+                "mph_write_vtu_kinematics_selected",
+                "mph_dist_monitor_configure", "mph_dist_monitor_record_doubles", "mph_dist_monitor_read_partial",
+                "mph_monitor_combine", "mph_dist_monitor_read"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -787,6 +812,49 @@ class MphSolver:
         lost = ctypes.c_longlong(0)
         k = _check(self._L.mph_monitor_read(self._h, out.ctypes.data, cap, ctypes.byref(lost)), self._h)
         return out[:k].copy(), int(lost.value)
+
+    # -- monitors on a slab rank --------------------------------------------------------------------
+    def dist_monitor(self, stride=1, capacity: int = 4096, track=(), probes=(), probe_radius: float = 0.0):
+        """mph_dist_monitor_configure: monitor() for a slab context, with the same configuration on
+        every rank.  From the next step on every `stride`-th step leaves this rank's record -- the head
+        over its owned particles, {present, x, y, z, vx, vy, vz} per tracked particle (original indices
+        of the whole problem), {value, count} per probe its slab holds and {0, -1} per other probe --
+        in its device ring; dist_monitor_read() makes samples of the ranks' records.
+        dist_monitor(None): off."""
+        self._mon_gauges = 0
+        if stride is None:
+            _check(self._L.mph_dist_monitor_configure(self._h, None), self._h)
+            self._mon_shape = None
+            return
+        tr = np.ascontiguousarray(track, np.int32).reshape(-1)
+        pr = np.ascontiguousarray(probes, np.float64).reshape(-1, 3)
+        m = MphMonitorConfig(int(stride), int(capacity), len(tr), tr.ctypes.data if len(tr) else None,
+                             len(pr), pr.ctypes.data if len(pr) else None, float(probe_radius))
+        _check(self._L.mph_dist_monitor_configure(self._h, ctypes.byref(m)), self._h)
+        self._mon_shape = (len(tr), len(pr))
+        self._mon_cap = int(capacity)
+
+    def _dist_monitor_read(self, fn, width, max_samples):
+        if self._L.mph_dist_monitor_record_doubles(self._h) == 0:
+            return np.zeros((0, 0)), 0
+        cap = int(max_samples) if max_samples is not None else self._mon_cap
+        out = np.zeros((max(cap, 1), width))
+        lost = ctypes.c_longlong(0)
+        k = _check(fn(self._h, out.ctypes.data, cap, ctypes.byref(lost)), self._h)
+        return out[:k].copy(), int(lost.value)
+
+    def dist_monitor_read_partial(self, max_samples: int | None = None):
+        """(records [k, 32 + 7 ntrack + 2 nprobe], lost): this rank's unread records, oldest first; no
+        communication.  monitor_combine() makes samples of all ranks' records."""
+        return self._dist_monitor_read(self._L.mph_dist_monitor_read_partial,
+                                       self._L.mph_dist_monitor_record_doubles(self._h), max_samples)
+
+    def dist_monitor_read(self, max_samples: int | None = None):
+        """(samples [k, 32 + 6 ntrack + 2 nprobe], lost), collective: every rank calls it with the same
+        max_samples; rank 0 receives the combined samples (monitor_split reads them), every other
+        rank none; lost is the rank's own."""
+        nt, npr = self._mon_shape if self._mon_shape else (0, 0)
+        return self._dist_monitor_read(self._L.mph_dist_monitor_read, MONITOR_HEAD + 6 * nt + 2 * npr, max_samples)
 
     def monitor_split(self, rows: np.ndarray):
         """monitor_split(rows, ...) with this solver's tracked-particle and probe counts."""

@@ -8,7 +8,7 @@ did moving code between translation units change any kernel?
 Each listing is split at its kernel symbols (the .amdhsa_kernel names).  A kernel is its instruction
 stream (from its label to .Lfunc_end) and its descriptor (.amdhsa_* lines, and the .set lines the
 descriptor's expressions refer to: VGPRs, SGPRs, LDS, scratch).  Before comparing, what depends only on
-a kernel's place in its file is normalised: `;` comments are dropped, the function number in local
+a kernel's place in its file is normalised: `;` comments and section switches are dropped, the function number in local
 labels (.LBB<n>_, .Lfunc_*<n>, .LJTI<n>_, .LCPI<n>_) is blanked, and the per-unit __hip_cuid_* symbol is
 masked.  Prints SAME or DIFF per kernel, and ONLY-OLD / ONLY-NEW for a kernel of one side; exits 1
 unless every kernel is SAME.  --show adds a unified diff of every DIFF.  --rename RE REPL (repeatable)
@@ -61,7 +61,8 @@ def kernels(path, renames=()):
             if state == 3 and s.startswith(".Lfunc_end"):
                 break
             n = normalise(raw)
-            if not n or n.startswith(".section") or n.startswith(".p2align"):
+            # (.text: the section switch behind a plain kernel; a template's instance has .section there)
+            if not n or n.startswith(".section") or n.startswith(".p2align") or n == ".text":
                 continue
             (desc if state == 2 else body).append(n)
         assert state == 3, "no descriptor found for " + sym
