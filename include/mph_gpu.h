@@ -512,6 +512,57 @@ typedef struct MphGaugeGrid {        /* 72 bytes: origin 0, spacing 24, count 48
  * context without particles gives {0, -inf, +inf, 0} for every line.                              */
 int mph_gauge_grid(MphCtx* ctx, const MphGaugeGrid* g, double* out);
 
+/* ---- lattice sampling and elevation maps on slab ranks ----------------------------------------- */
+
+/* mph_sample_grid and mph_gauge_grid for a slab context (mph_create_slab and its kin); the calls above
+ * keep refusing one.  A lattice is axis-aligned, so the rank that evaluates a point -- the one whose
+ * slab holds the point's coordinate along the slab axis, wrapped like a particle's -- depends only on
+ * the point's index along that axis: a rank owns planes of the lattice (mph_slab_lattice_owner with the
+ * context's cuts), several runs of them where the lattice crosses the periodic seam or is longer than
+ * the domain.  The owner evaluates a point over its sorted set, owned particles and ghosts: the radius
+ * limit MaxRadius + MARGIN is below the halo width, so that set holds every contributor.  Additive: no
+ * change of MPH_ABI_VERSION.  All of these return MPH_ERR_UNSUPPORTED on a single context and follow
+ * the argument rules of the single-context calls, "no step since creation or since the last mph_set"
+ * included; none changes the state or touches a step graph.
+ *
+ * This rank's part of the lattice *g, no communication: out has the layout of mph_sample_grid for the
+ * whole lattice, and the rank writes the rows of the planes it owns and leaves every other row
+ * untouched (the convention of mph_get in slab mode); only those planes are computed on the device
+ * and copied from it.  *owned_points (may be NULL) receives the number of points written; 0 is legal.
+ * The definition is mph_sample_grid's: COUNT is exact, the sums are taken in the rank's own cell order
+ * (they differ from a single context's by reassociation only), the same call gives the same bits.   */
+int mph_dist_sample_grid_partial(MphCtx* ctx, const MphSampleGrid* g, double* out, long long* owned_points);
+/* Collective: every rank calls it with the same *g; the ranks' planes travel to rank 0, which receives
+ * the whole lattice in out -- bit for bit the merge of the partial calls.  The other ranks may pass
+ * out == NULL.  MPH_ERR_TRANSPORT where the gather fails.                                           */
+int mph_dist_sample_grid(MphCtx* ctx, const MphSampleGrid* g, double* out);
+
+/* A rank's record of a line: {COUNT, TOP, BOTTOM, WET, LOBIN, HIBIN}, LOBIN and HIBIN the lowest and
+ * highest occupied bin (-1 with none).
+ *   A line not parallel to the slab axis lies in one plane: the owner of the plane computes it over
+ *   its owned particles and its ghosts (every particle within the radius across is among them); every
+ *   other rank's record is {-1, -inf, +inf, 0, -1, -1}.
+ *   A line parallel to the slab axis runs through every rank (count[axis] is 1 there): every rank
+ *   computes every line over the fluid particles it owns, along the whole extent of its window.      */
+#define MPH_DIST_GAUGE_RECORD 6
+/* This rank's records of every line of *g, records [count[2]][count[1]][count[0]][MPH_DIST_GAUGE_RECORD];
+ * no communication.                                                                                  */
+int mph_dist_gauge_grid_partial(MphCtx* ctx, const MphGaugeGrid* g, double* records);
+/* The ranks' records made a map: records[r] is rank r's [nlines][MPH_DIST_GAUGE_RECORD], out receives
+ * [nlines][MPH_GAUGE_CHANNELS], the layout of mph_gauge_grid.  Host only, no context.  Per line, over
+ * the ranks with COUNT >= 0 in rank order: COUNT is the sum, TOP the maximum, BOTTOM the minimum; WET is
+ * the sum of the ranks' WET minus one for every pair of consecutive non-empty ranks (COUNT > 0) whose
+ * HIBIN == LOBIN.  An owned fluid particle lies in its rank's slab and the bin does not decrease with
+ * the coordinate, so the ranks' bins are ordered and only such a pair can share one (a bin shared by
+ * three ranks is counted three times and subtracted twice).  Every channel is an integer count, an
+ * extremum or a population: the map is a bit-exact function of the state, the same as a single
+ * context's.  MPH_ERR_ARG: a line with no rank at COUNT >= 0, nranks < 1, nlines < 0, a null pointer. */
+int mph_gauge_combine(int nranks, long long nlines, const double* const* records, double* out);
+/* Collective: every rank calls it with the same *g; rank 0 gathers the ranks' records, combines them
+ * and receives the map in out ([count[2]][count[1]][count[0]][MPH_GAUGE_CHANNELS]); the other ranks may
+ * pass out == NULL.  MPH_ERR_TRANSPORT where the gather fails.                                      */
+int mph_dist_gauge_grid(MphCtx* ctx, const MphGaugeGrid* g, double* out);
+
 /* ---- particle selections ---------------------------------------------------------------------- */
 
 /* A selection is a subset of the particles, built on the device on demand: read any field for the
@@ -897,6 +948,14 @@ int mph_owned_ids(MphCtx* ctx, int* out_ids);
  * MphSlabOptions (NULL: equal slabs).                                                         */
 int mph_slab_bounds(const MphConfig* cfg, int rank, int nranks, int axis, const double* cuts, double* out3);
 int mph_slab_owner(const MphConfig* cfg, int nranks, int axis, const double* cuts, double c);
+/* Host-only: the owners of the planes of an axis-aligned lattice along the slab axis.  owner[i], i <
+ * count_a, is mph_slab_owner of origin_a + (double)i * spacing_a -- the product and the sum each
+ * rounded, no contraction: the kernels' own expression -- wrapped into the periodic domain like a
+ * particle's coordinate.  A lattice that crosses the periodic seam or is longer than the domain gives
+ * a rank several runs of planes.  MPH_ERR_ARG: what mph_slab_owner refuses, count_a < 1, spacing_a <= 0,
+ * a non-finite origin_a or spacing_a, owner NULL.  Additive: no change of MPH_ABI_VERSION.        */
+int mph_slab_lattice_owner(const MphConfig* cfg, int nranks, int axis, const double* cuts, double origin_a,
+                           double spacing_a, int count_a, int* owner);
 
 #ifdef __cplusplus
 }

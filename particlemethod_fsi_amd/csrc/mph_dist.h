@@ -120,6 +120,10 @@ int check_cuts(const HostDerived& h, int axis, int nranks, const double* cuts, s
 SlabGeom make_geom(const HostDerived& h, int axis, int rank, int nranks, const double* cuts, double halo);
 double wrap_coord(const HostDerived& h, int axis, double x);
 int owner_rank(const HostDerived& h, int axis, int nranks, const double* cuts, double x);
+// owner[i] = owner_rank of origin_a + (double)i * spacing_a, each rounded: who owns plane i of an
+// axis-aligned lattice along the slab axis (mph_slab_lattice_owner, the mph_dist_* lattice calls)
+void lattice_owners(const HostDerived& h, int axis, int nranks, const double* cuts, double origin_a, double spacing_a,
+                    int count_a, int* owner);
 // signed periodic offset of x from the centre of rank r's slab
 double slab_offset(const HostDerived& h, int axis, int r, int nranks, const double* cuts, double x);
 int check_geometry(const MphConfig& cfg, int nranks, int axis, std::string& err);

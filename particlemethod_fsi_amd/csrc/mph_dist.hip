@@ -543,7 +543,9 @@ int dist_step_batch(MphCtx* c, int nsteps, Profiler* prof)
             MPH_CK(dist_enqueue_step(c, prof, early_at(c, k, nsteps, 0), early_at(c, k, nsteps, 1)));
     }
     MPH_HIP_OK(c, hipGetLastError());
-    ctx_stepped(c, nsteps, false);   // (a slab context has no reader of a_current: no lattice sampling)
+    // (a batch ends joined, early_at: the sorted set A, its ghosts' PressureP included, is the last
+    // step's -- what the slab ranks' lattice calls read, mph_dist_sample_grid)
+    ctx_stepped(c, nsteps, true);
     return dist_sync(c);
 }
 

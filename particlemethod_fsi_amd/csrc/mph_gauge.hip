@@ -11,6 +11,10 @@
 // they do not depend on the order the wave meets the particles in: a record is a function of the
 // state, the line and the radius alone, bit for bit, whichever kernel computes it.  No global
 // atomics, no floating-point atomics.
+//
+// On a slab rank (mph_dist_gauge_grid, mph_dist_gauge_grid_partial) gauge_line and k_gauge_grid run in
+// their SLAB forms and leave the rank's record {COUNT, TOP, BOTTOM, WET, LOBIN, HIBIN} of a line;
+// mph_gauge_combine (mph_observe.hip) makes the map of the ranks' records on the host.
 #include <hip/hip_runtime.h>
 
 #include "mph_device.h"
@@ -79,10 +83,13 @@ __device__ __forceinline__ void gauge_term(GaugeAcc& acc, const DevParams& P, in
 // The candidates j0, j0 + step, ... below je.  A line's walk is a chain of trips to memory, so
 // kGaugeLoads candidates' loads -- type and position together -- are in flight before the first is
 // tested (a candidate past je repeats j0's loads and counts as none).
+// SLAB with `own` (a line parallel to the slab axis): only the particles the rank owns count, A.id >=
+// 0, the test of k_monitor_partial<true>; a ghost counts as no candidate.
 constexpr int kGaugeLoads = 4;
-template <int DIM>
+template <int DIM, bool SLAB>
 __device__ __forceinline__ void gauge_range(GaugeAcc& acc, const DevParams& P, const Soa& A, int j0, int je, int step,
-                                            int axis, const double (&p)[3], double h, int nbins, unsigned* bits)
+                                            int axis, const double (&p)[3], double h, int nbins, unsigned* bits,
+                                            bool own)
 {
     for (int j = j0; j < je; j += kGaugeLoads * step) {
         int t[kGaugeLoads];
@@ -93,6 +100,7 @@ __device__ __forceinline__ void gauge_range(GaugeAcc& acc, const DevParams& P, c
             const int jc = ok ? j + u * step : j;
             const int tt = A.type[jc];
             t[u] = ok ? tt : -1;
+            if (SLAB && own && A.id[jc] < 0) t[u] = -1;
             x[u] = A.x[jc];
             y[u] = A.y[jc];
             z[u] = DIM == 3 ? A.z[jc] : 0.0;
@@ -105,13 +113,19 @@ __device__ __forceinline__ void gauge_range(GaugeAcc& acc, const DevParams& P, c
 // The stencil of a line across one axis d: the cells within `reach` of the line's cell cc, each once.
 // n cells; cell i is at(i).  Where the stencil covers the whole axis (2 reach + 1 >= g, as the
 // hi - lo + 1 >= g case of PointStencil) the cells are 0 .. g - 1; otherwise cc - reach + i, wrapped.
+// clip (the slab axis of a slab rank's window grid, which is not periodic along it): the cells of
+// cc - reach .. cc + reach inside 0 .. g - 1, none wrapped.
 struct GaugeSpan {
     int n, first, g;
-    __device__ __forceinline__ GaugeSpan(int cc, int reach, int g_) : g(g_)
+    __device__ __forceinline__ GaugeSpan(int cc, int reach, int g_, bool clip = false) : g(g_)
     {
         const bool whole = 2 * reach + 1 >= g_;
         n = whole ? g_ : 2 * reach + 1;
         first = whole ? 0 : cc - reach;
+        if (clip) {
+            first = max(cc - reach, 0);
+            n = min(cc + reach, g_ - 1) - first + 1;
+        }
     }
     __device__ __forceinline__ int at(int i) const { return wrap_cell(first + i, g); }
 };
@@ -128,10 +142,17 @@ struct GaugeSpan {
 //   axis != ca: ca is an across axis, so the cells of one cell index along `axis` and one offset
 //     across the other axis are a run of 2 P.sa + 1 cells of start[], two where it wraps.  The
 //     lanes take the runs.
-template <int DIM>
+// SLAB, a slab rank's record {COUNT, TOP, BOTTOM, WET, LOBIN, HIBIN} over its sorted set A on its
+// window grid (n: the live count).  A line parallel to the slab axis runs through every rank: the rank
+// counts the particles it owns alone, over the whole extent of its window along the axis.  Any other
+// line is computed by the rank that owns its plane, over owned particles and ghosts; the slab axis is
+// then an across axis, and its span -- the GaugeSpan, or the run along the contiguous axis -- is
+// clipped at the window's two ends instead of wrapped, as in k_monitor_probe<DIM, true>.  LOBIN and
+// HIBIN: the lowest and highest occupied bin, -1 with none (mph_gauge_combine's overlap term).
+template <int DIM, bool SLAB>
 __device__ __forceinline__ void gauge_line(const DevParams& P, const Soa& A, const int* __restrict__ start, int n,
                                            int axis, const double (&point)[3], double h, int nbins,
-                                           unsigned* bits, double (&rec)[4])
+                                           unsigned* bits, double (&rec)[SLAB ? kDistGaugeRec : MPH_GAUGE_CHANNELS])
 {
     const int lane = threadIdx.x & 63;
     const int nwords = (nbins + 31) >> 5;
@@ -147,12 +168,15 @@ __device__ __forceinline__ void gauge_line(const DevParams& P, const Soa& A, con
     const auto cell = [&](int a) { return gauge_ipick(a, c0, c1, c2); };
     const auto grid = [&](int a) { return gauge_ipick(a, g0, g1, g2); };
     const int ca = contig_axis(DIM, P.perm);
+    // (sl: the slab axis where it is an across axis of the line, else -1)
+    const bool own = SLAB && axis == P.slab_axis;
+    const int sl = SLAB && !own ? P.slab_axis : -1;
     GaugeAcc acc;
     if (axis == ca) {
         // the across axes (a0, a1), both column axes; 2-D: a0 = 0 alone
         const int a0 = DIM == 3 ? (ca == 0 ? 1 : 0) : 0, a1 = DIM == 3 ? (ca == 2 ? 1 : 2) : -1;
-        const GaugeSpan s0(cell(a0), kReach, grid(a0));
-        const GaugeSpan s1 = DIM == 3 ? GaugeSpan(cell(a1), kReach, grid(a1)) : GaugeSpan(0, 0, 1);
+        const GaugeSpan s0(cell(a0), kReach, grid(a0), SLAB && sl == a0);
+        const GaugeSpan s1 = DIM == 3 ? GaugeSpan(cell(a1), kReach, grid(a1), SLAB && sl == a1) : GaugeSpan(0, 0, 1);
         const int ncol = s0.n * s1.n;
         int b = 0, e = 0;
         if (lane < ncol) {
@@ -166,16 +190,17 @@ __device__ __forceinline__ void gauge_line(const DevParams& P, const Soa& A, con
         }
         for (int col = 0; col < ncol; ++col) {
             const int cb = __shfl(b, col, 64), ce = __shfl(e, col, 64);
-            gauge_range<DIM>(acc, P, A, cb + lane, ce, 64, axis, p, h, nbins, bits);
+            gauge_range<DIM, SLAB>(acc, P, A, cb + lane, ce, 64, axis, p, h, nbins, bits, own);
         }
     } else {
         // the across axes: ca and, in 3-D, the third axis o
         const int o = DIM == 3 ? 3 - axis - ca : -1;
-        const GaugeSpan so = DIM == 3 ? GaugeSpan(cell(o), kReach, grid(o)) : GaugeSpan(0, 0, 1);
+        const GaugeSpan so = DIM == 3 ? GaugeSpan(cell(o), kReach, grid(o), SLAB && sl == o) : GaugeSpan(0, 0, 1);
         // the run along ca, the same for every cell index along the line (PointStencil's ranges)
         const int cc = cell(ca), g = grid(ca);
         int lo = cc - P.sa, hi = cc + P.sa, lo1 = 0, hi1 = -1;
-        if (hi - lo + 1 >= g) { lo = 0; hi = g - 1; }
+        if (SLAB && sl == ca) { lo = max(lo, 0); hi = min(hi, g - 1); }
+        else if (hi - lo + 1 >= g) { lo = 0; hi = g - 1; }
         else if (lo < 0) { lo1 = lo + g; hi1 = g - 1; lo = 0; }
         else if (hi >= g) { lo1 = 0; hi1 = hi - g; hi = g - 1; }
         const int nrun = grid(axis) * so.n;
@@ -186,27 +211,45 @@ __device__ __forceinline__ void gauge_line(const DevParams& P, const Soa& A, con
             for (int d = 0; d < 3; ++d) q[d] = d == axis ? m : (d == o ? qo : 0);
             const int cell0 = cell_index(P, q[0], q[1], q[2]);
             const int b0 = max(start[cell0 + lo], 0), e0 = min(start[cell0 + hi + 1], n);
-            gauge_range<DIM>(acc, P, A, b0, e0, 1, axis, p, h, nbins, bits);
+            gauge_range<DIM, SLAB>(acc, P, A, b0, e0, 1, axis, p, h, nbins, bits, own);
             if (hi1 >= lo1) {
                 const int b1 = max(start[cell0 + lo1], 0), e1 = min(start[cell0 + hi1 + 1], n);
-                gauge_range<DIM>(acc, P, A, b1, e1, 1, axis, p, h, nbins, bits);
+                gauge_range<DIM, SLAB>(acc, P, A, b1, e1, 1, axis, p, h, nbins, bits, own);
             }
         }
     }
     __syncthreads();
     int wet = 0;
-    for (int w = lane; w < nwords; w += 64) wet += __popc(bits[w]);
+    // (SLAB) the lane's lowest and highest set bit: its words ascend, so the first one with a bit
+    // gives the lowest and the last one the highest
+    int lob = 0x7fffffff, hib = -1;
+    for (int w = lane; w < nwords; w += 64) {
+        const unsigned b = bits[w];
+        wet += __popc(b);
+        if (SLAB && b) {
+            lob = min(lob, 32 * w + __ffs(b) - 1);
+            hib = 32 * w + 31 - __clz(b);
+        }
+    }
 #pragma unroll
     for (int m = 32; m > 0; m >>= 1) {
         acc.cnt += __shfl_xor(acc.cnt, m, 64);
         wet += __shfl_xor(wet, m, 64);
         acc.top = fmax(acc.top, __shfl_xor(acc.top, m, 64));
         acc.bot = fmin(acc.bot, __shfl_xor(acc.bot, m, 64));
+        if (SLAB) {
+            lob = min(lob, __shfl_xor(lob, m, 64));
+            hib = max(hib, __shfl_xor(hib, m, 64));
+        }
     }
     rec[0] = (double)acc.cnt;
     rec[1] = acc.top;
     rec[2] = acc.bot;
     rec[3] = (double)wet;
+    if constexpr (SLAB) {
+        rec[4] = hib < 0 ? -1.0 : (double)lob;
+        rec[5] = (double)hib;
+    }
 }
 
 // One wave per gauge of the monitors: M.gau[4 q ..] on a sampled step.
@@ -220,7 +263,7 @@ __global__ __launch_bounds__(64) void k_monitor_gauge(DevParams P, MonitorDev M,
     const int q = blockIdx.x;
     const double point[3] = {M.gauges[3 * q], M.gauges[3 * q + 1], DIM == 3 ? M.gauges[3 * q + 2] : 0.0};
     double rec[4];
-    gauge_line<DIM>(P, A, start, n, M.gauge_axis, point, M.gauge_h, M.gauge_nbins, s_bits, rec);
+    gauge_line<DIM, false>(P, A, start, n, M.gauge_axis, point, M.gauge_h, M.gauge_nbins, s_bits, rec);
     if (threadIdx.x < MPH_GAUGE_CHANNELS) {
         const int k = threadIdx.x;
         M.gau[MPH_GAUGE_CHANNELS * q + k] = k == 0 ? rec[0] : (k == 1 ? rec[1] : (k == 2 ? rec[2] : rec[3]));
@@ -230,8 +273,14 @@ __global__ __launch_bounds__(64) void k_monitor_gauge(DevParams P, MonitorDev M,
 // One wave per line of the lattice, W lines to a block (the last block's spare waves take its last
 // line again and store nothing).  Line l = (k count[1] + j) count[0] + i passes through origin +
 // (i, j, k) spacing, each product and sum rounded.
-template <int DIM, int W>
-__global__ __launch_bounds__(64 * W) void k_gauge_grid(DevParams P, GaugeGridDev G, int n, Soa A,
+// SLAB, a slab rank's records (mph_dist_gauge_grid_partial): G is the rank's lines (GaugeRunDev: a run
+// of the planes it owns, line l the l-th of the run and its point computed from its indices in the
+// whole lattice; or, for lines parallel to the slab axis, the whole lattice), n the capacity -- the
+// live count is read here -- and a record has kDistGaugeRec doubles.
+template <bool SLAB> struct GaugeArg { using type = GaugeGridDev; };
+template <> struct GaugeArg<true> { using type = GaugeRunDev; };
+template <int DIM, int W, bool SLAB>
+__global__ __launch_bounds__(64 * W) void k_gauge_grid(DevParams P, typename GaugeArg<SLAB>::type G, int n, Soa A,
                                                        const int* __restrict__ start, double* __restrict__ out)
 {
 #pragma clang fp contract(off)
@@ -239,13 +288,24 @@ __global__ __launch_bounds__(64 * W) void k_gauge_grid(DevParams P, GaugeGridDev
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int line = blockIdx.x * W + wave;
     const int l = min(line, G.nlines - 1);
-    const int i = l % G.count[0], j = (l / G.count[0]) % G.count[1], k = l / (G.count[0] * G.count[1]);
+    int i = l % G.count[0], j = (l / G.count[0]) % G.count[1], k = l / (G.count[0] * G.count[1]);
+    if constexpr (SLAB) {
+        n = dev_n(P);
+        const int first = G.first;
+        i += P.slab_axis == 0 ? first : 0;
+        j += P.slab_axis == 1 ? first : 0;
+        k += P.slab_axis == 2 ? first : 0;
+    }
     const double point[3] = {G.origin[0] + (double)i * G.spacing[0], G.origin[1] + (double)j * G.spacing[1],
                              G.origin[2] + (double)k * G.spacing[2]};
-    double rec[4];
-    gauge_line<DIM>(P, A, start, n, G.axis, point, G.h, G.nbins, s_bits[wave], rec);
-    if (line < G.nlines && lane < MPH_GAUGE_CHANNELS)
-        out[(size_t)MPH_GAUGE_CHANNELS * l + lane] = lane == 0 ? rec[0] : (lane == 1 ? rec[1] : (lane == 2 ? rec[2] : rec[3]));
+    constexpr int R = SLAB ? kDistGaugeRec : MPH_GAUGE_CHANNELS;
+    double rec[R];
+    gauge_line<DIM, SLAB>(P, A, start, n, G.axis, point, G.h, G.nbins, s_bits[wave], rec);
+    if (line < G.nlines && lane < R) {
+        double v = lane == 0 ? rec[0] : (lane == 1 ? rec[1] : (lane == 2 ? rec[2] : rec[3]));
+        if constexpr (SLAB) v = lane == 4 ? rec[4] : (lane == 5 ? rec[5] : v);
+        out[(size_t)R * l + lane] = v;
+    }
 }
 
 void launch_monitor_gauge(const Launch& L, const MonitorDev& M)
@@ -263,11 +323,25 @@ void launch_gauge_grid(const Launch& L, const GaugeGridDev& G, double* out)
     by_dim(P.dim, [&](auto D) {
         constexpr int DIM = decltype(D)::value;
         if (G.waves == 4)
-            launch(L.prof, "gauge_grid", L.stream, k_gauge_grid<DIM, 4>, dim3((G.nlines + 3) / 4), dim3(256), P, G, P.n,
+            launch(L.prof, "gauge_grid", L.stream, k_gauge_grid<DIM, 4, false>, dim3((G.nlines + 3) / 4), dim3(256), P, G, P.n,
                    L.A, L.start, out);
         else
-            launch(L.prof, "gauge_grid", L.stream, k_gauge_grid<DIM, 1>, dim3(G.nlines), dim3(64), P, G, P.n, L.A,
+            launch(L.prof, "gauge_grid", L.stream, k_gauge_grid<DIM, 1, false>, dim3(G.nlines), dim3(64), P, G, P.n, L.A,
                    L.start, out);
+    });
+}
+
+void launch_dist_gauge_grid(const Launch& L, const GaugeRunDev& G, double* out)
+{
+    const DevParams& P = *L.P;
+    by_dim(P.dim, [&](auto D) {
+        constexpr int DIM = decltype(D)::value;
+        if (G.waves == 4)
+            launch(L.prof, "dist_gauge_grid", L.stream, k_gauge_grid<DIM, 4, true>, dim3((G.nlines + 3) / 4), dim3(256),
+                   P, G, P.n, L.A, L.start, out);
+        else
+            launch(L.prof, "dist_gauge_grid", L.stream, k_gauge_grid<DIM, 1, true>, dim3(G.nlines), dim3(64), P, G, P.n,
+                   L.A, L.start, out);
     });
 }
 

@@ -294,6 +294,13 @@ struct SampleDev {
     int mask;        // classes summed: bit 0 fluid, 1 structure, 2 walls
     double h;        // radius
 };
+// A slab rank's run of lattice planes (mph_dist_sample_grid_partial): count[slab axis] is the run's
+// number of planes (tile / tiles chosen for the run), `first` the index of its first plane in the
+// whole lattice, which a point's coordinates are computed from.  Behind SampleDev, so the
+// single-context kernel keeps its argument layout.
+struct SampleRunDev : SampleDev {
+    int first;
+};
 
 // The elevation map (mph_gauge.hip, mph_gauge_grid): the lattice of lines with the resolved axis, bin
 // count and radius, passed to the kernel by value.
@@ -305,6 +312,14 @@ struct GaugeGridDev {
     int waves;       // lines (waves) per block: 1 or 4
     double h;        // radius
 };
+// A slab rank's lines (mph_dist_gauge_grid_partial).  Lines not parallel to the slab axis: a run of
+// the planes the rank owns, as SampleRunDev (count[slab axis] the run's, nlines its lines, `first`
+// its first plane).  Lines parallel to it: the whole lattice, first = 0.
+struct GaugeRunDev : GaugeGridDev {
+    int first;
+};
+// doubles of a slab rank's line record {COUNT, TOP, BOTTOM, WET, LOBIN, HIBIN} (MPH_DIST_GAUGE_RECORD)
+constexpr int kDistGaugeRec = MPH_DIST_GAUGE_RECORD;
 
 // Particle selections (mph_select.hip, mph_select): the device buffers of a context's selection,
 // passed to the kernels by value.  Index spaces: i an original particle index (< n), q an index
@@ -377,11 +392,15 @@ void launch_dist_monitor(const Launch& L, const MonitorDev& M);
 void launch_monitor_gauge(const Launch& L, const MonitorDev& M);
 // the four channels of every line into out ([nz][ny][nx][4], device); L.P->n > 0
 void launch_gauge_grid(const Launch& L, const GaugeGridDev& G, double* out);
+// a slab rank's records of the G.nlines lines of G into out ([G.nlines][kDistGaugeRec], device)
+void launch_dist_gauge_grid(const Launch& L, const GaugeRunDev& G, double* out);
 // fills G.tile / G.tiles from G.count / G.spacing (run_axis: the contiguous cell axis); returns the
 // number of tiles (waves)
 long long sample_tiling(SampleDev& G, int run_axis);
 // the six channels of every lattice point into out ([nz][ny][nx][6], device); L.P->n > 0
 void launch_sample_grid(const Launch& L, const SampleDev& G, double* out);
+// a slab rank's run of planes into out ([run's points][6], device); recorded as "dist_sample_grid"
+void launch_dist_sample_grid(const Launch& L, const SampleRunDev& G, double* out);
 void launch_sort(const Launch& L, int mode);   // mode 0 init, 1 step, 2 step (motion done)
 void launch_neighbors(const Launch& L);
 void launch_pass_a(const Launch& L);

@@ -315,7 +315,10 @@ int main(int argc, char** argv)
     if (nslabs <= 1 && std::getenv("MPH_DIST_MONITOR"))
         die(nullptr, MPH_ERR_ARG, "MPH_DIST_MONITOR needs MPH_SLABS > 1 (a single context: MPH_MONITOR)");
     if (nslabs > 1 && std::getenv("MPH_SAMPLE"))
-        die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_SAMPLE with MPH_SLABS > 1 (sampling needs a single context)");
+        die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_SAMPLE with MPH_SLABS > 1 (sampling needs a single context; "
+                                         "the slab ranks' planes gathered: MPH_DIST_SAMPLE)");
+    if (nslabs <= 1 && std::getenv("MPH_DIST_SAMPLE"))
+        die(nullptr, MPH_ERR_ARG, "MPH_DIST_SAMPLE needs MPH_SLABS > 1 (a single context: MPH_SAMPLE)");
     if (nslabs > 1 && (std::getenv("MPH_OUTPUT_SELECT") || std::getenv("MPH_LOADS"))) {
         const std::string what = std::string(std::getenv("MPH_OUTPUT_SELECT") ? "MPH_OUTPUT_SELECT " : "") +
                                  (std::getenv("MPH_LOADS") ? "MPH_LOADS " : "") +
@@ -466,14 +469,17 @@ int main(int argc, char** argv)
     // MPH_SAMPLE="ox,oy,oz;sx,sy,sz;nx,ny,nz": at every VTK output step the fields are sampled on
     // that lattice (include/mph_gpu.h mph_sample_grid; MPH_SAMPLE_RADIUS, MPH_SAMPLE_CLASSES
     // optional) and written as VTK ImageData to MPH_SAMPLE_FILE, a printf pattern taking the .vtk
-    // files' index (default sample%03d.vti)
+    // files' index (default sample%03d.vti).  MPH_DIST_SAMPLE with MPH_SLABS > 1: the same grammar,
+    // options, file and cadence from the slab ranks (include/mph_gpu.h mph_dist_sample_grid) -- every
+    // rank samples the lattice planes it owns, rank 0 receives the lattice and writes the file
     MphSampleGrid sgrid{};
     std::vector<double> sbuf;
     std::string sfile = "sample%03d.vti";
-    const bool sampling = std::getenv("MPH_SAMPLE") != nullptr;
+    const bool dsample = nslabs > 1 && std::getenv("MPH_DIST_SAMPLE");
+    const bool sampling = dsample || std::getenv("MPH_SAMPLE") != nullptr;
     if (sampling) {
-        const std::vector<double> v = parse_numbers(std::getenv("MPH_SAMPLE"));
-        if (v.size() != 9) die(nullptr, MPH_ERR_ARG, "MPH_SAMPLE (ox,oy,oz;sx,sy,sz;nx,ny,nz)");
+        const std::vector<double> v = parse_numbers(std::getenv(dsample ? "MPH_DIST_SAMPLE" : "MPH_SAMPLE"));
+        if (v.size() != 9) die(nullptr, MPH_ERR_ARG, "MPH_SAMPLE / MPH_DIST_SAMPLE (ox,oy,oz;sx,sy,sz;nx,ny,nz)");
         double points = 1.0;
         for (int d = 0; d < 3; ++d) {
             sgrid.origin[d] = v[d];
@@ -486,7 +492,7 @@ int main(int argc, char** argv)
         if (const char* e = std::getenv("MPH_SAMPLE_RADIUS")) sgrid.radius = std::atof(e);
         if (const char* e = std::getenv("MPH_SAMPLE_CLASSES")) sgrid.classes = std::atoi(e);
         if (const char* e = std::getenv("MPH_SAMPLE_FILE")) sfile = e;
-        sbuf.resize((size_t)points * MPH_SAMPLE_CHANNELS);
+        if (!dsample || root) sbuf.resize((size_t)points * MPH_SAMPLE_CHANNELS);
     }
     // MPH_OUTPUT_SELECT=<spec> (include/mph_gpu.h mph_selection_parse): every VTK-step file, .vtk or
     // .vtu, holds only that selection, evaluated at that step (written before the loop goes on: the
@@ -607,11 +613,14 @@ int main(int argc, char** argv)
         }
         for (int s = 0; s < k; ++s) {
             if (vtk_after && s == k - 1 && sampling) {
-                rc = mph_sample_grid(ctx, &sgrid, sbuf.data());
-                if (rc) die(ctx, rc, "mph_sample_grid");
+                rc = dsample ? mph_dist_sample_grid(ctx, &sgrid, sbuf.empty() ? nullptr : sbuf.data())
+                             : mph_sample_grid(ctx, &sgrid, sbuf.data());
+                if (rc) die(ctx, rc, dsample ? "mph_dist_sample_grid" : "mph_sample_grid");
                 std::snprintf(name, sizeof(name), sfile.c_str(), istep);
-                rc = mph_write_vti_arrays(name, &sgrid, sbuf.data());
-                if (rc) die(ctx, rc, "writing a .vti file");
+                if (!dsample || root) {
+                    rc = mph_write_vti_arrays(name, &sgrid, sbuf.data());
+                    if (rc) die(ctx, rc, "writing a .vti file");
+                }
             }
             if (vtk_after && s == k - 1 && kinematics) {
                 rc = mph_compute_kinematics(ctx, &kin);

@@ -14,6 +14,10 @@
 // L1 then serves.  Points many cells apart (every lane in another region) or many to a cell change
 // only which of the two ways a wave takes and what the caches see.  DESIGN.md section 11 has the
 // measurements, with the version that only walks.
+//
+// On a slab rank (mph_dist_sample_grid, mph_dist_sample_grid_partial) the same kernel runs in its SLAB
+// form over the runs of lattice planes the rank owns, one launch per run, on the rank's sorted set --
+// owned particles and ghosts -- and its window grid: see k_sample_grid.
 #include <hip/hip_runtime.h>
 
 #include "mph_device.h"
@@ -55,9 +59,13 @@ struct SampleAcc {
 };
 
 // the lane's lattice point: its indices and its position wrapped into the periodic domain like a
-// particle (2-D: z is ignored); false for a lane without a point
-__device__ __forceinline__ bool sample_point(const SampleDev& G, const DevParams& P, int dim, long long tile, int lane,
-                                             size_t& pt, double (&p)[3])
+// particle (2-D: z is ignored); false for a lane without a point.  SLAB: G.count holds the planes of
+// one run along the slab axis, the first of them plane `first` of the whole lattice: pt is the
+// point's place in the run, its coordinates come from its indices in the whole lattice.
+// (GRID: the kernel's own argument type, so that no copy of it is made)
+template <bool SLAB, typename GRID>
+__device__ __forceinline__ bool sample_point(const GRID& G, const DevParams& P, int dim, long long tile, int lane,
+                                             int first, size_t& pt, double (&p)[3])
 {
 #pragma clang fp contract(off)
     const int t0 = (int)(tile % G.tiles[0]);
@@ -69,8 +77,10 @@ __device__ __forceinline__ bool sample_point(const SampleDev& G, const DevParams
     const int k = t2 * G.tile[2] + l2;
     if (l2 >= G.tile[2] || i >= G.count[0] || j >= G.count[1] || k >= G.count[2]) return false;
     pt = ((size_t)k * G.count[1] + j) * G.count[0] + i;
-    const double q[3] = {G.origin[0] + (double)i * G.spacing[0], G.origin[1] + (double)j * G.spacing[1],
-                         G.origin[2] + (double)k * G.spacing[2]};
+    const int gi = SLAB && P.slab_axis == 0 ? i + first : i, gj = SLAB && P.slab_axis == 1 ? j + first : j;
+    const int gk = SLAB && P.slab_axis == 2 ? k + first : k;
+    const double q[3] = {G.origin[0] + (double)gi * G.spacing[0], G.origin[1] + (double)gj * G.spacing[1],
+                         G.origin[2] + (double)gk * G.spacing[2]};
     wrap_point(P, dim, q, p);
     return true;
 }
@@ -102,13 +112,47 @@ __device__ __forceinline__ void sample_store(double2* __restrict__ out, size_t p
     out[3 * pt + 2] = make_double2(any ? a.sv1 / a.sw : 0.0, any ? a.sv2 / a.sw : 0.0);
 }
 
-// a lane walks its point's whole stencil through global memory
+// component `axis` of three values, by selects on the values (a chain of conditional member reads
+// becomes a runtime-indexed load, and the stencil then lives in scratch)
+__device__ __forceinline__ int sample_ipick(int axis, int v0, int v1, int v2)
+{
+    return axis == 0 ? v0 : (axis == 1 ? v1 : v2);
+}
+// A slab rank's window grid is not periodic along the slab axis: a stencil is clipped at the window's
+// two ends there instead of wrapped, as in k_monitor_probe<DIM, true> (a cell past an end would be one
+// from the window's other end, not the domain's).  The slab axis the contiguous one: one clamped run.
 template <int DIM>
+__device__ __forceinline__ void sample_slab_clip(const DevParams& P, PointStencil<DIM>& S)
+{
+    if (P.slab_axis != S.ca) return;
+    const int g = sample_ipick(P.slab_axis, P.gc[0], P.gc[1], P.gc[2]);
+    const int cc = sample_ipick(P.slab_axis, S.c[0], S.c[1], S.c[2]);
+    S.lo = max(cc - P.sa, 0);
+    S.hi = min(cc + P.sa, g - 1);
+    S.lo1 = 0;
+    S.hi1 = -1;
+}
+// The slab axis a column axis: is column col's cell along it (its offset as PointStencil::column takes
+// it) inside the window?
+template <int DIM>
+__device__ __forceinline__ bool sample_slab_column(const DevParams& P, const PointStencil<DIM>& S, int col)
+{
+    const int ax = P.slab_axis;
+    if (ax == S.ca) return true;
+    const int g = sample_ipick(ax, P.gc[0], P.gc[1], P.gc[2]);
+    const int cc = sample_ipick(ax, S.c[0], S.c[1], S.c[2]);
+    const int d = (ax == S.a0 ? (DIM == 3 ? col / kGroups : col) : col % kGroups) - kReach;
+    return cc + d >= 0 && cc + d < g;
+}
+
+// a lane walks its point's whole stencil through global memory
+template <int DIM, bool SLAB>
 __device__ __forceinline__ void sample_walk(SampleAcc& acc, const DevParams& P, const PointStencil<DIM>& S,
                                             const double (&p)[3], double h, int mask, int n, const Soa& A,
                                             const int* __restrict__ start, const double* __restrict__ pres)
 {
     for (int col = 0; col < PointStencil<DIM>::ncol; ++col) {
+        if (SLAB && !sample_slab_column<DIM>(P, S, col)) continue;
         const int cell0 = S.column(P, col);
         for (int run = 0; run < 2; ++run) {
             if (run == 1 && S.hi1 < S.lo1) break;
@@ -127,9 +171,15 @@ __device__ __forceinline__ void sample_walk(SampleAcc& acc, const DevParams& P, 
 // at a time with coalesced loads, as k_neighbors stages its windows, and every lane tests its own
 // sub-range of what is staged, in index order.  The lanes of any other wave walk their stencils
 // themselves.  Both ways add the same terms in the same order.
+// SLAB, a slab rank's planes (mph_dist_sample_grid_partial): one launch per run of planes the rank
+// owns, G the run (SampleRunDev), out the run's points alone; n is the capacity and the live count is
+// read here; A is the rank's sorted set, owned and ghosts, and the stencil is clipped at the window's
+// ends along the slab axis in both ways through a wave.  The distance stays the minimum image.
 constexpr int kSampleStage = 64;   // records staged at a time: one per lane
-template <int DIM>
-__global__ __launch_bounds__(64) void k_sample_grid(DevParams P, SampleDev G, int n, Soa A,
+template <bool SLAB> struct SampleArg { using type = SampleDev; };
+template <> struct SampleArg<true> { using type = SampleRunDev; };
+template <int DIM, bool SLAB>
+__global__ __launch_bounds__(64) void k_sample_grid(DevParams P, typename SampleArg<SLAB>::type G, int n, Soa A,
                                                     const int* __restrict__ start, const double* __restrict__ pres,
                                                     double2* __restrict__ out)
 {
@@ -140,9 +190,13 @@ __global__ __launch_bounds__(64) void k_sample_grid(DevParams P, SampleDev G, in
     const long long tile = blockIdx.x;
     size_t pt = 0;
     double p[3] = {0.0, 0.0, 0.0};
-    const bool active = sample_point(G, P, DIM, tile, lane, pt, p);
+    if (SLAB) n = dev_n(P);
+    int plane0 = 0;   // the run's first plane
+    if constexpr (SLAB) plane0 = G.first;
+    const bool active = sample_point<SLAB>(G, P, DIM, tile, lane, plane0, pt, p);
     if (!__any(active)) return;
-    const PointStencil<DIM> S(P, p);
+    PointStencil<DIM> S(P, p);
+    if (SLAB) sample_slab_clip<DIM>(P, S);
     SampleAcc acc;
     // the first active lane's column cells; do all active lanes share them, none wrapping along ca?
     const int first = __ffsll((unsigned long long)__ballot(active)) - 1;
@@ -150,7 +204,7 @@ __global__ __launch_bounds__(64) void k_sample_grid(DevParams P, SampleDev G, in
     const bool same = k0 == __shfl(k0, first, 64) && k1 == __shfl(k1, first, 64) && S.hi1 < S.lo1;
     if (!__all(same || !active)) {
         if (active) {
-            sample_walk<DIM>(acc, P, S, p, G.h, G.mask, n, A, start, pres);
+            sample_walk<DIM, SLAB>(acc, P, S, p, G.h, G.mask, n, A, start, pres);
             sample_store(out, pt, acc);
         }
         return;
@@ -168,6 +222,7 @@ __global__ __launch_bounds__(64) void k_sample_grid(DevParams P, SampleDev G, in
 #pragma unroll
     for (int d = 0; d < 3; ++d) W.c[d] = __shfl(S.c[d], first, 64);
     for (int col = 0; col < PointStencil<DIM>::ncol; ++col) {
+        if (SLAB && !sample_slab_column<DIM>(P, W, col)) continue;
         const int cell0 = W.column(P, col);
         const int wb = max(start[cell0 + wlo], 0), we = min(start[cell0 + whi + 1], n);
         int b = 0, e = 0;
@@ -202,8 +257,18 @@ void launch_sample_grid(const Launch& L, const SampleDev& G, double* out)
     const DevParams& P = *L.P;
     const long long ntiles = (long long)G.tiles[0] * G.tiles[1] * G.tiles[2];
     by_dim(P.dim, [&](auto D) {
-        launch(L.prof, "sample_grid", L.stream, k_sample_grid<decltype(D)::value>, dim3((unsigned)ntiles), dim3(64), P,
-               G, P.n, L.A, L.start, L.pres, (double2*)out);
+        launch(L.prof, "sample_grid", L.stream, k_sample_grid<decltype(D)::value, false>, dim3((unsigned)ntiles),
+               dim3(64), P, G, P.n, L.A, L.start, L.pres, (double2*)out);
+    });
+}
+
+void launch_dist_sample_grid(const Launch& L, const SampleRunDev& G, double* out)
+{
+    const DevParams& P = *L.P;
+    const long long ntiles = (long long)G.tiles[0] * G.tiles[1] * G.tiles[2];
+    by_dim(P.dim, [&](auto D) {
+        launch(L.prof, "dist_sample_grid", L.stream, k_sample_grid<decltype(D)::value, true>, dim3((unsigned)ntiles),
+               dim3(64), P, G, P.n, L.A, L.start, L.pres, (double2*)out);
     });
 }
 

@@ -72,6 +72,18 @@ int owner_rank(const HostDerived& h, int axis, int nranks, const double* cuts, d
     return nranks - 1;
 }
 
+void lattice_owners(const HostDerived& h, int axis, int nranks, const double* cuts, double origin_a, double spacing_a,
+                    int count_a, int* owner)
+{
+#pragma clang fp contract(off)
+    for (int i = 0; i < count_a; ++i) {
+        // (the kernels' expression: sample_point, k_gauge_grid)
+        const double prod = (double)i * spacing_a;
+        const double x = origin_a + prod;
+        owner[i] = owner_rank(h, axis, nranks, cuts, x);
+    }
+}
+
 double slab_offset(const HostDerived& h, int axis, int r, int nranks, const double* cuts, double x)
 {
     double lo, hi;
@@ -293,6 +305,19 @@ int mph_slab_owner(const MphConfig* cfg, int nranks, int axis, const double* cut
         if (slab_owns(a, lo, hi, r == 0, r == nranks - 1)) return r;
     }
     return MPH_ERR_DOMAIN;
+}
+
+int mph_slab_lattice_owner(const MphConfig* cfg, int nranks, int axis, const double* cuts, double origin_a,
+                           double spacing_a, int count_a, int* owner)
+{
+    if (!cfg || !owner || nranks < 1 || axis < 0 || axis > 2 || count_a < 1) return MPH_ERR_ARG;
+    if (!std::isfinite(origin_a) || !std::isfinite(spacing_a) || !(spacing_a > 0.0)) return MPH_ERR_ARG;
+    HostDerived h{};
+    derive_constants(*cfg, h);
+    std::string err;
+    if (check_cuts(h, axis, nranks, cuts, err) != MPH_OK) return MPH_ERR_ARG;
+    lattice_owners(h, axis, nranks, cuts, origin_a, spacing_a, count_a, owner);
+    return MPH_OK;
 }
 
 }  // extern "C"

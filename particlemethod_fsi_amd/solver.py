@@ -71,6 +71,8 @@ EXPORTED_SYMBOLS = [
     "mph_write_vtu_kinematics_selected",
     "mph_dist_monitor_configure", "mph_dist_monitor_record_doubles", "mph_dist_monitor_read_partial",
     "mph_monitor_combine", "mph_dist_monitor_read",
+    "mph_slab_lattice_owner", "mph_dist_sample_grid_partial", "mph_dist_sample_grid",
+    "mph_dist_gauge_grid_partial", "mph_gauge_combine", "mph_dist_gauge_grid",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -133,6 +135,9 @@ GAUGE_CHANNELS = {"COUNT": 0, "TOP": 1, "BOTTOM": 2, "WET": 3}
 GAUGE_MAX = 64
 GAUGE_MAX_BINS = 8192
 GAUGE_GRID_MAX_LINES = 1 << 20
+# a slab rank's record of a line (MPH_DIST_GAUGE_RECORD): the four channels, then the lowest and highest
+# occupied bin
+DIST_GAUGE_RECORD = {"COUNT": 0, "TOP": 1, "BOTTOM": 2, "WET": 3, "LOBIN": 4, "HIBIN": 5}
 
 
 class MphSelection(ctypes.Structure):
@@ -304,6 +309,21 @@ def monitor_combine(records, ntrack: int, nprobe: int) -> np.ndarray:
     return out
 
 
+def gauge_combine(records) -> np.ndarray:
+    """mph_gauge_combine: the slab ranks' line records (records[r]: rank r's [..., 6],
+    MphSolver.dist_gauge_grid(partial=True)) -> the map [..., 4] that MphSolver.gauge_grid gives on a
+    single context.  Host only; every channel is a count, an extremum or a population, so the map is a
+    bit-exact function of the state."""
+    recs = [np.ascontiguousarray(r, np.float64) for r in records]
+    w = len(DIST_GAUGE_RECORD)
+    if not recs or any(r.ndim < 1 or r.shape != recs[0].shape or r.shape[-1] != w for r in recs):
+        raise ValueError("every rank's records must have the same shape [..., %d]" % w)
+    out = np.zeros(recs[0].shape[:-1] + (len(GAUGE_CHANNELS),))
+    ptrs = (ctypes.c_void_p * len(recs))(*[r.ctypes.data for r in recs])
+    _check(load_library().mph_gauge_combine(len(recs), recs[0].size // w, ptrs, out.ctypes.data))
+    return out
+
+
 class MphError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__("%s (%d): %s" % (STATUS.get(code, "?"), code, msg))
@@ -427,6 +447,12 @@ def load_library() -> ctypes.CDLL:
                                                               ctypes.POINTER(ctypes.c_longlong)]),
         "mph_monitor_combine": (ip, [ip, ip, ip, ctypes.c_longlong, vp, vp]),
         "mph_dist_monitor_read": (ctypes.c_longlong, [vp, vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
+        "mph_slab_lattice_owner": (ip, [cfgp, ip, ip, vp, dp, dp, ip, vp]),
+        "mph_dist_sample_grid_partial": (ip, [vp, ctypes.POINTER(MphSampleGrid), vp, ctypes.POINTER(ctypes.c_longlong)]),
+        "mph_dist_sample_grid": (ip, [vp, ctypes.POINTER(MphSampleGrid), vp]),
+        "mph_dist_gauge_grid_partial": (ip, [vp, ctypes.POINTER(MphGaugeGrid), vp]),
+        "mph_gauge_combine": (ip, [ip, ctypes.c_longlong, vp, vp]),
+        "mph_dist_gauge_grid": (ip, [vp, ctypes.POINTER(MphGaugeGrid), vp]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
@@ -443,7 +469,9 @@ def load_library() -> ctypes.CDLL:
                 "mph_get_kinematics", "mph_get_kinematics_selected", "mph_write_vtu_kinematics",
                 "mph_write_vtu_kinematics_selected",
                 "mph_dist_monitor_configure", "mph_dist_monitor_record_doubles", "mph_dist_monitor_read_partial",
-                "mph_monitor_combine", "mph_dist_monitor_read"}
+                "mph_monitor_combine", "mph_dist_monitor_read",
+                "mph_slab_lattice_owner", "mph_dist_sample_grid_partial", "mph_dist_sample_grid",
+                "mph_dist_gauge_grid_partial", "mph_gauge_combine", "mph_dist_gauge_grid"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -585,6 +613,17 @@ def slab_window(cfg: mphio.MphConfig, rank: int, nranks: int, axis: int, cuts=No
 def slab_owner(cfg: mphio.MphConfig, nranks: int, axis: int, x: float, cuts=None) -> int:
     c, p = _cuts(cuts, nranks)
     return _check(load_library().mph_slab_owner(ctypes.byref(cfg), nranks, axis, p, float(x)))
+
+
+def slab_lattice_owner(cfg: mphio.MphConfig, nranks: int, axis: int, origin_a: float, spacing_a: float,
+                       count_a: int, cuts=None) -> np.ndarray:
+    """mph_slab_lattice_owner: the rank that owns each of the count_a planes of an axis-aligned lattice
+    along the slab axis -- slab_owner of origin_a + i spacing_a, the kernels' expression -> int32 [count_a]."""
+    c, p = _cuts(cuts, nranks)
+    owner = np.zeros(max(int(count_a), 1), np.int32)
+    _check(load_library().mph_slab_lattice_owner(ctypes.byref(cfg), nranks, axis, p, float(origin_a), float(spacing_a),
+                                                 int(count_a), owner.ctypes.data))
+    return owner
 
 
 class Slab:
@@ -909,6 +948,49 @@ class MphSolver:
         _check(self._L.mph_sample_grid_timed(self._h, ctypes.byref(g), out.ctypes.data, ctypes.byref(ms),
                                              ctypes.addressof(name)), self._h)
         return out, ms.value, name.value.decode()
+
+    # -- lattice sampling and elevation maps on slab ranks ------------------------------------------
+    def dist_sample_grid(self, origin, spacing, count, radius: float = 0.0, classes: int = 0, partial: bool = False,
+                         out: np.ndarray | None = None):
+        """mph_dist_sample_grid: sample_grid() for a slab context, collective -- every rank calls it with
+        the same lattice; rank 0 returns the whole lattice (nz, ny, nx, 6), every other rank None.
+        partial (mph_dist_sample_grid_partial, no communication): (array, owned points) -- the rows of
+        the lattice planes this rank owns (slab_lattice_owner) written into `out`, or into a new array
+        filled with NaN, every other row left as it is."""
+        g = _sample_grid(origin, spacing, count, radius, classes)
+        shape = (max(int(count[2]), 0), max(int(count[1]), 0), max(int(count[0]), 0), len(SAMPLE_CHANNELS))
+        n = shape[0] * shape[1] * shape[2]
+        if out is None:
+            out = np.full(shape if 0 < n <= SAMPLE_MAX_POINTS else (1, 1, 1, len(SAMPLE_CHANNELS)),
+                          np.nan if partial else 0.0)
+        elif out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError("dist_sample_grid: out must be a C-contiguous float64 array of shape %r" % (shape,))
+        if partial:
+            owned = ctypes.c_longlong(0)
+            _check(self._L.mph_dist_sample_grid_partial(self._h, ctypes.byref(g), out.ctypes.data, ctypes.byref(owned)),
+                   self._h)
+            return out, owned.value
+        _check(self._L.mph_dist_sample_grid(self._h, ctypes.byref(g), out.ctypes.data), self._h)
+        return out if self.dist_info()["rank"] == 0 else None
+
+    def dist_gauge_grid(self, origin, spacing, count, axis: int = -1, radius: float = 0.0, partial: bool = False):
+        """mph_dist_gauge_grid: gauge_grid() for a slab context, collective -- rank 0 returns the map
+        (nz, ny, nx, 4), every other rank None.  partial (mph_dist_gauge_grid_partial, no
+        communication): this rank's records (nz, ny, nx, 6), the channels DIST_GAUGE_RECORD;
+        gauge_combine() makes the map of all ranks' records."""
+        g = MphGaugeGrid()
+        for d in range(3):
+            g.origin[d], g.spacing[d], g.count[d] = float(origin[d]), float(spacing[d]), int(count[d])
+        g.axis, g.radius = int(axis), float(radius)
+        w = len(DIST_GAUGE_RECORD) if partial else len(GAUGE_CHANNELS)
+        shape = (max(int(count[2]), 0), max(int(count[1]), 0), max(int(count[0]), 0), w)
+        n = shape[0] * shape[1] * shape[2]
+        out = np.zeros(shape if 0 < n <= GAUGE_GRID_MAX_LINES else (1, 1, 1, w))
+        if partial:
+            _check(self._L.mph_dist_gauge_grid_partial(self._h, ctypes.byref(g), out.ctypes.data), self._h)
+            return out
+        _check(self._L.mph_dist_gauge_grid(self._h, ctypes.byref(g), out.ctypes.data), self._h)
+        return out if self.dist_info()["rank"] == 0 else None
 
     # -- particle selections ----------------------------------------------------------------------
     def select(self, types=None, box=None, on: str = "position", every: int = 1, phase: int = 0, spec=None) -> int:
