@@ -571,8 +571,8 @@ int mph_dist_gauge_grid(MphCtx* ctx, const MphGaugeGrid* g, double* out);
  * and each one's place in the sorted device arrays.  It is a snapshot of the current state: the next
  * mph_step, mph_set or mph_set_initial_velocity_profile makes it stale, and every consumer below
  * then returns MPH_ERR_ARG until the next mph_select (as it does before the first one).  Single
- * contexts only: every context entry point returns MPH_ERR_UNSUPPORTED in slab mode.  Additive: no
- * change of MPH_ABI_VERSION.
+ * contexts only: every context entry point returns MPH_ERR_UNSUPPORTED in slab mode (slab ranks:
+ * the mph_dist_* calls below).  Additive: no change of MPH_ABI_VERSION.
  *
  * Particle i of type t is selected iff all of: type_mask is 0 or has bit t; i % every == phase; box
  * is 0, or lo[d] <= x[d] < hi[d] on every axis d < dim (2-D: z is ignored) for x the particle's
@@ -653,6 +653,64 @@ int mph_write_vtu_selected(MphCtx* ctx, const char* path);
  * The selection it made stays the context's.                                                       */
 int mph_select_profile(MphCtx* ctx, const MphSelection* s, const double center[3], int max, double* ms,
                        char* names32);
+
+/* ---- particle selections on slab ranks ---------------------------------------------------------- */
+
+/* Selections for a slab context (mph_create_slab and its kin); the calls above keep refusing one.  A
+ * rank's selection is the subset of the particles IT OWNS NOW -- what mph_owned_ids lists; a ghost is
+ * never selected -- that the predicate of MphSelection accepts, held as ascending original indices of
+ * the whole problem ([0, n) of mph_particle_count).  Position is what mph_get returns on the rank.
+ * Ownership is a partition, so the ranks' selections partition the whole problem's: a box that spans a
+ * cut or the periodic face selects each particle exactly once, on the rank that owns it.  The argument
+ * rules, the snapshot rule (stale after mph_step, mph_set or mph_set_initial_velocity_profile: the
+ * consumers then return MPH_ERR_ARG) and the legality before the first step are the single context's.
+ * Additive: no change of MPH_ABI_VERSION.  Every context call below returns MPH_ERR_UNSUPPORTED on a
+ * single context; none changes the state or touches a step graph, and no rank waits for another except
+ * inside the calls named collective.
+ *
+ * Make *s this rank's selection and return its size in *count (may be NULL; 0 is legal).  No
+ * communication; a flush point.  A refused call leaves the selection made before it as it was.
+ * Property comes from the device, so a rank created from its own window (MphSlabOptions.ids) selects a
+ * particle that came from outside it like any other; only a box on InitialPosition (box 2) needs the
+ * static inputs: MPH_ERR_ARG where the rank owns a particle without them that the rest of *s accepts.
+ * Memory: 12 bytes per particle of the WHOLE problem per rank (the flags and the two slot maps are
+ * indexed by original index, which keeps the rows ascending without a sort on the device).         */
+int mph_dist_select(MphCtx* ctx, const MphSelection* s, int* count);
+/* This rank's selected original indices, ascending: `count` ints.  No communication.               */
+int mph_dist_selected_ids(MphCtx* ctx, int* out);
+/* Row r of out is, bit for bit, row ids[r] of what mph_get(field) fills on this rank, with the same
+ * widths; the sorted device arrays are gathered on the device and only `count` rows are copied.
+ * Property, Mass, Lambda, Mu and Kappa's modulus follow the device's type array.  MPH_ERR_ARG for
+ * InitialPosition where a selected particle has no static inputs on this rank.  No communication.  */
+int mph_dist_get_selected(MphCtx* ctx, int field, void* out);
+/* mph_selection_totals over this rank's selection: the same terms in the same fixed order (blocks of
+ * 1,024 ranks over ascending original index, the wave fold, the records in order), so a rank's record
+ * is a bit-exact function of the state, the selection, the centre and the cuts.  An empty selection
+ * gives the identities (sums 0, minima +inf, maxima -inf, VMAX2 0).  No communication.             */
+int mph_dist_selection_totals_partial(MphCtx* ctx, const double center[3], double out[MPH_TOTALS]);
+/* The ranks' records made one: records[r] is rank r's MPH_TOTALS doubles.  Host only, no context.
+ * Rank 0's record is combined with ranks 1, 2, ... in order, in plain FP64 without contraction: COUNT
+ * and the sums (MASS, P*, KE, F*, T*, M*) add, the minima take the minimum, the maxima and VMAX2 the
+ * maximum, the reserved slots are 0.  The result is a function of the records and of the rank order,
+ * bit for bit.  MPH_ERR_ARG: nranks < 1, a null pointer.                                           */
+int mph_totals_combine(int nranks, const double* const* records, double out[MPH_TOTALS]);
+/* Collective (every rank calls it with the same centre): rank 0 gathers the partial records and
+ * receives mph_totals_combine of them in out, bit for bit; the other ranks may pass out == NULL.
+ * MPH_ERR_TRANSPORT where the gather fails.                                                        */
+int mph_dist_selection_totals(MphCtx* ctx, const double center[3], double out[MPH_TOTALS]);
+/* Collective (every rank, the same field): rank 0 receives every rank's rows of
+ * mph_dist_get_selected(field) merged by ascending original index in out, the indices in ids, and
+ * returns the number of rows; MPH_ERR_ARG on rank 0 when cap_rows (the rows out and ids hold) is too
+ * small -- mph_particle_count always suffices.  The other ranks return 0 and may pass NULL with
+ * cap_rows == 0.  Only selected rows travel.  MPH_ERR_TRANSPORT where the gather fails, or on rank 0
+ * where another rank could not read its rows.                                                       */
+long long mph_dist_gather_selected(MphCtx* ctx, int field, void* out, int* ids, long long cap_rows);
+/* Collective: rank 0 writes exactly what mph_write_vtk_arrays / mph_write_vtu_arrays give for the
+ * merged selected rows, n the total count.  Every rank gathers its selected rows on the device; none
+ * fetches a whole array, and rank 0 builds no array of the whole problem's length (unlike
+ * mph_write_vtk on a slab context).  Needs static inputs for every selected particle (InitialPosition). */
+int mph_dist_write_vtk_selected(MphCtx* ctx, const char* path);
+int mph_dist_write_vtu_selected(MphCtx* ctx, const char* path);
 
 /* ---- velocity gradient, vorticity and free-surface fields ------------------------------------- */
 

@@ -347,11 +347,16 @@ int sel_grow(MphCtx* c, T** p, size_t* cap, size_t need)
     return MPH_OK;
 }
 
-// the entry of a consumer of the selection: flush, single contexts, a current selection
-int sel_enter(MphCtx* c, const char* who)
+// the entry of a consumer of the selection: flush, single contexts (slab: slab contexts, the
+// mph_dist_* calls), a current selection
+int sel_enter(MphCtx* c, const char* who, bool slab = false)
 {
     MPH_CK(ctx_enter(c));
-    if (c->dist) return ctx_fail(c, MPH_ERR_UNSUPPORTED, std::string(who) + ": selections are not available in slab mode");
+    if (slab && !c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, std::string(who) + ": slab selections need a slab context (a single context: "
+                                                    "mph_select and its readers)");
+    if (!slab && c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, std::string(who) + ": selections are not available in slab mode");
     if (!c->sel_current)
         return ctx_fail(c, MPH_ERR_ARG, std::string(who) + ": no current selection (none was made, or the state has changed "
                                             "since: mph_select again after mph_step / mph_set)");
@@ -396,6 +401,177 @@ int sel_struct_m33(MphCtx* c, const double* d, double* out)
         for (int e = 0; e < 9; ++e) out[9 * (size_t)r + e] = h[e * fes + s];
     }
     return MPH_OK;
+}
+
+// What follows the flags of mph_select and mph_dist_select: the count of the scan over nidx original
+// indices, the rank arrays regrown for it, the fill (fill(): its launch) and the host copy of the ids
+template <typename Fill>
+int sel_collect(MphCtx* c, int nidx, const char* who, Fill fill)
+{
+    SelectDev& D = c->sel;
+    int cnt = 0;
+    MPH_HIP_OK(c, hipMemcpyAsync(&cnt, D.bsum + select_blocks(nidx), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    if (cnt < 0 || cnt > nidx) return ctx_fail(c, MPH_ERR_HIP, std::string(who) + ": the scan returned " + std::to_string(cnt));
+    if ((size_t)cnt > c->sel_rank_cap || !D.ids) {
+        size_t cap = 0;
+        for (int** p : {&D.ids, &D.slot_a, &D.slot_b}) {
+            cap = 0;
+            MPH_CK(sel_grow(c, p, &cap, (size_t)std::max(cnt, 1)));
+        }
+        c->sel_rank_cap = cap;
+    }
+    D.count = cnt;
+    if (cnt > 0) {
+        fill();
+        MPH_HIP_OK(c, hipGetLastError());
+        MPH_CK(fetch(c, (const int*)D.ids, c->sel_ids, (size_t)cnt));
+        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    }
+    return MPH_OK;
+}
+
+// host index of the static inputs of original index i (prop, pos0), or -1: this rank was created
+// without them (slab-local creation, a particle from outside its window)
+long sel_input(const MphCtx* c, int i)
+{
+    if (c->gid.empty()) return i;
+    const auto it = std::lower_bound(c->gid.begin(), c->gid.end(), i);
+    return it != c->gid.end() && *it == i ? (long)(it - c->gid.begin()) : -1;
+}
+
+// mph_get_selected and mph_dist_get_selected behind their entries.  What mph_get takes from the host's
+// static inputs comes, on a slab rank, from where every owned particle has it: Property is the device's
+// type (gathered through slot_b), and Mass, Lambda, Mu and Kappa's modulus follow from it through the
+// per-type tables -- a rank created from its window alone (slab-local creation) has no inputs for a
+// particle that came from outside it.  InitialPosition has no such source.
+int sel_get(MphCtx* c, int field, void* out)
+{
+    const std::vector<int>& ids = c->sel_ids;
+    const size_t m = ids.size();
+    if (field < 0 || field >= MPH_FIELD_COUNT) return ctx_fail(c, MPH_ERR_ARG, "unknown field " + std::to_string(field));
+    if (m == 0) return MPH_OK;
+    if (!out) return MPH_ERR_ARG;
+    double* o = (double*)out;
+    int* oi = (int*)out;
+    const Launch& L = c->L;
+    const SelectDev& D = c->sel;
+    // the sorted arrays through the slot maps, as mph_get reads them: Position and Velocity from
+    // the set B in B.id order, everything else in A.id order
+    auto planes = [&](const double* x, const double* y, const double* z, const int* slot) {
+        const double* const src[3] = {x, y, z};
+        return sel_gather(c, src, 3, 1, slot, o);
+    };
+    auto xyz4 = [&](const double4* d) {
+        const double* b = (const double*)d;
+        const double* const src[3] = {b, b + 1, b + 2};
+        return sel_gather(c, src, 3, 4, D.slot_a, o);
+    };
+    auto scalar = [&](const double* d, double* to) {
+        const double* const src[1] = {d};
+        return sel_gather(c, src, 1, 1, D.slot_a, to);
+    };
+    // the structure's host tables: row k of S belongs to original index S.orig[k] (slab mode: of the
+    // lists built here, sl_s, as mph_get; a ghost slot's particle is never selected)
+    auto struct_rows = [&](auto put) {
+        const size_t ns = c->dist ? c->sl_s.size() : c->S.orig.size();
+        for (size_t j = 0; j < ns; ++j) {
+            const size_t k = c->dist ? (size_t)c->sl_s[j] : j;
+            const long r = sel_row(c, glob_id(c, c->S.orig[k]));
+            if (r >= 0) put((size_t)r, k);
+        }
+    };
+    // the selected particles' types
+    std::vector<int> ty;
+    auto types = [&]() {
+        ty.resize(m);
+        if (!c->dist) {
+            for (size_t r = 0; r < m; ++r) ty[r] = c->prop[ids[r]];
+            return (int)MPH_OK;
+        }
+        MPH_CK(sel_grow(c, &c->sel_out, &c->sel_out_cap, m));
+        launch_select_gather_int(L, L.B.type, D.slot_b, (int)m, (int*)c->sel_out);
+        MPH_HIP_OK(c, hipGetLastError());
+        MPH_HIP_OK(c, hipMemcpyAsync(ty.data(), c->sel_out, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
+        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+        for (size_t r = 0; r < m; ++r)
+            if (ty[r] < 0 || ty[r] >= kTypes) return ctx_fail(c, MPH_ERR_HIP, "selection: a particle of type " + std::to_string(ty[r]));
+        return (int)MPH_OK;
+    };
+    switch (field) {
+    case MPH_FIELD_POSITION: return planes(L.B.x, L.B.y, L.B.z, D.slot_b);
+    case MPH_FIELD_VELOCITY: return planes(L.B.vx, L.B.vy, L.B.vz, D.slot_b);
+    case MPH_FIELD_INITIAL_POSITION:
+        for (size_t r = 0; r < m; ++r)
+            if (sel_input(c, ids[r]) < 0)
+                return ctx_fail(c, MPH_ERR_ARG, "slab selection: an owned particle without static inputs");
+        for (size_t r = 0; r < m; ++r) std::memcpy(o + 3 * r, &c->pos0[3 * (size_t)sel_input(c, ids[r])], 3 * sizeof(double));
+        return MPH_OK;
+    case MPH_FIELD_FORCE: return xyz4(L.force);
+    case MPH_FIELD_ACCELERATION: return xyz4(L.acc);
+    case MPH_FIELD_GRAVITY_CENTER: return planes(L.gx, L.gy, L.gz, D.slot_a);
+    case MPH_FIELD_PRESSURE_P: return scalar(L.pres, o);
+    case MPH_FIELD_PRESSURE_A: return scalar(L.pa, o);
+    case MPH_FIELD_DENSITY_A: return scalar(L.dens_a, o);
+    case MPH_FIELD_VOL_STRAIN_P: return scalar(L.vstrain, o);
+    case MPH_FIELD_DIVERGENCE_P: return scalar(L.divp, o);
+    case MPH_FIELD_NEIGHBOR_COUNT:
+        MPH_CK(sel_grow(c, &c->sel_out, &c->sel_out_cap, m));
+        launch_select_gather_int(L, L.nbcount, D.slot_a, (int)m, (int*)c->sel_out);
+        MPH_HIP_OK(c, hipGetLastError());
+        MPH_HIP_OK(c, hipMemcpyAsync(oi, c->sel_out, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
+        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+        return MPH_OK;
+    case MPH_FIELD_MASS:
+        MPH_CK(types());
+        for (size_t r = 0; r < m; ++r) o[r] = c->cfg.density[ty[r]] * c->h.vol;
+        return MPH_OK;
+    case MPH_FIELD_KAPPA: {
+        std::vector<double> vs(c->stepped ? m : 0, 0.0);
+        if (c->stepped) MPH_CK(scalar(L.vstrain, vs.data()));
+        MPH_CK(types());
+        for (size_t r = 0; r < m; ++r) o[r] = (c->stepped && vs[r] < 0.0) ? 0.0 : c->cfg.bulk_modulus[ty[r]];
+        return MPH_OK;
+    }
+    case MPH_FIELD_LAMBDA:
+        MPH_CK(types());
+        for (size_t r = 0; r < m; ++r) o[r] = c->cfg.bulk_viscosity[ty[r]];
+        return MPH_OK;
+    case MPH_FIELD_MU:
+        MPH_CK(types());
+        for (size_t r = 0; r < m; ++r) o[r] = c->cfg.shear_viscosity[ty[r]];
+        return MPH_OK;
+    case MPH_FIELD_PROPERTY:
+        MPH_CK(types());
+        std::memcpy(oi, ty.data(), sizeof(int) * m);
+        return MPH_OK;
+    case MPH_FIELD_INITIAL_STRUCTURE_NEIGHBOR_COUNT:
+        std::memset(oi, 0, sizeof(int) * m);
+        struct_rows([&](size_t r, size_t k) { oi[r] = c->S.count[k]; });
+        return MPH_OK;
+    case MPH_FIELD_DEFORM_GRADIENT: return sel_struct_m33(c, c->Sd.F, o);
+    case MPH_FIELD_STRAIN: return sel_struct_m33(c, c->Sd.E, o);
+    case MPH_FIELD_STRESS: return sel_struct_m33(c, c->Sd.S, o);
+    case MPH_FIELD_NORMALIZER:
+        std::memset(o, 0, sizeof(double) * 9 * m);
+        struct_rows([&](size_t r, size_t k) { std::memcpy(o + 9 * r, &c->S.normalizer[9 * k], sizeof(double) * 9); });
+        return MPH_OK;
+    case MPH_FIELD_VIRIAL_STRESS:
+    case MPH_FIELD_VIRIAL_PRESSURE: {
+        const int w = field == MPH_FIELD_VIRIAL_STRESS ? 9 : 1;
+        std::memset(o, 0, sizeof(double) * w * m);
+        if (!c->vir) return MPH_OK;   // never computed: zeros, as mph_get
+        const double* src[9];
+        for (int e = 0; e < w; ++e) src[e] = (w == 9 ? c->vir : c->vpres) + e;
+        return sel_gather(c, src, w, w, D.slot_a, o);
+    }
+    case MPH_FIELD_LAMBDA_LAMES:
+    case MPH_FIELD_MU_LAMES:
+        for (size_t r = 0; r < m; ++r) o[r] = 0.0;
+        struct_rows([&](size_t r, size_t k) { o[r] = field == MPH_FIELD_LAMBDA_LAMES ? c->S.lame_l[k] : c->S.lame_m[k]; });
+        return MPH_OK;
+    default: return ctx_fail(c, MPH_ERR_ARG, "unknown field " + std::to_string(field));
+    }
 }
 
 int write_selected(MphCtx* c, const char* path, bool xml)
@@ -462,25 +638,7 @@ int mph_select(MphCtx* c, const MphSelection* s, int* count)
         // Position as mph_get reads it: the integrated set B in the order of B.id
         launch_select_scan(c->L, c->L.B, *s, with_mask, D);
         MPH_HIP_OK(c, hipGetLastError());
-        int cnt = 0;
-        MPH_HIP_OK(c, hipMemcpyAsync(&cnt, D.bsum + nb, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
-        if (cnt < 0 || cnt > n) return ctx_fail(c, MPH_ERR_HIP, "mph_select: the scan returned " + std::to_string(cnt));
-        if ((size_t)cnt > c->sel_rank_cap || !D.ids) {
-            size_t cap = 0;
-            for (int** p : {&D.ids, &D.slot_a, &D.slot_b}) {
-                cap = 0;
-                MPH_CK(sel_grow(c, p, &cap, (size_t)std::max(cnt, 1)));
-            }
-            c->sel_rank_cap = cap;
-        }
-        D.count = cnt;
-        if (cnt > 0) {
-            launch_select_fill(c->L, D);
-            MPH_HIP_OK(c, hipGetLastError());
-            MPH_CK(fetch(c, (const int*)D.ids, c->sel_ids, (size_t)cnt));
-            MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
-        }
+        MPH_CK(sel_collect(c, n, "mph_select", [&] { launch_select_fill(c->L, D); }));
     }
     c->sel_current = true;
     if (count) *count = D.count;
@@ -498,104 +656,7 @@ int mph_selected_ids(MphCtx* c, int* out)
 int mph_get_selected(MphCtx* c, int field, void* out)
 {
     MPH_CK(sel_enter(c, "mph_get_selected"));
-    const std::vector<int>& ids = c->sel_ids;
-    const size_t m = ids.size();
-    if (field < 0 || field >= MPH_FIELD_COUNT) return ctx_fail(c, MPH_ERR_ARG, "unknown field " + std::to_string(field));
-    if (m == 0) return MPH_OK;
-    if (!out) return MPH_ERR_ARG;
-    double* o = (double*)out;
-    int* oi = (int*)out;
-    const Launch& L = c->L;
-    const SelectDev& D = c->sel;
-    // the sorted arrays through the slot maps, as mph_get reads them: Position and Velocity from
-    // the set B in B.id order, everything else in A.id order
-    auto planes = [&](const double* x, const double* y, const double* z, const int* slot) {
-        const double* const src[3] = {x, y, z};
-        return sel_gather(c, src, 3, 1, slot, o);
-    };
-    auto xyz4 = [&](const double4* d) {
-        const double* b = (const double*)d;
-        const double* const src[3] = {b, b + 1, b + 2};
-        return sel_gather(c, src, 3, 4, D.slot_a, o);
-    };
-    auto scalar = [&](const double* d, double* to) {
-        const double* const src[1] = {d};
-        return sel_gather(c, src, 1, 1, D.slot_a, to);
-    };
-    // the structure's host tables: row k of S belongs to original index S.orig[k]
-    auto struct_rows = [&](auto put) {
-        for (size_t k = 0; k < c->S.orig.size(); ++k) {
-            const long r = sel_row(c, c->S.orig[k]);
-            if (r >= 0) put((size_t)r, k);
-        }
-    };
-    switch (field) {
-    case MPH_FIELD_POSITION: return planes(L.B.x, L.B.y, L.B.z, D.slot_b);
-    case MPH_FIELD_VELOCITY: return planes(L.B.vx, L.B.vy, L.B.vz, D.slot_b);
-    case MPH_FIELD_INITIAL_POSITION:
-        for (size_t r = 0; r < m; ++r) std::memcpy(o + 3 * r, &c->pos0[3 * (size_t)ids[r]], 3 * sizeof(double));
-        return MPH_OK;
-    case MPH_FIELD_FORCE: return xyz4(L.force);
-    case MPH_FIELD_ACCELERATION: return xyz4(L.acc);
-    case MPH_FIELD_GRAVITY_CENTER: return planes(L.gx, L.gy, L.gz, D.slot_a);
-    case MPH_FIELD_PRESSURE_P: return scalar(L.pres, o);
-    case MPH_FIELD_PRESSURE_A: return scalar(L.pa, o);
-    case MPH_FIELD_DENSITY_A: return scalar(L.dens_a, o);
-    case MPH_FIELD_VOL_STRAIN_P: return scalar(L.vstrain, o);
-    case MPH_FIELD_DIVERGENCE_P: return scalar(L.divp, o);
-    case MPH_FIELD_NEIGHBOR_COUNT:
-        MPH_CK(sel_grow(c, &c->sel_out, &c->sel_out_cap, m));
-        launch_select_gather_int(L, L.nbcount, D.slot_a, (int)m, (int*)c->sel_out);
-        MPH_HIP_OK(c, hipGetLastError());
-        MPH_HIP_OK(c, hipMemcpyAsync(oi, c->sel_out, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
-        MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
-        return MPH_OK;
-    case MPH_FIELD_MASS:
-        for (size_t r = 0; r < m; ++r) o[r] = c->cfg.density[c->prop[ids[r]]] * c->h.vol;
-        return MPH_OK;
-    case MPH_FIELD_KAPPA: {
-        std::vector<double> vs(c->stepped ? m : 0, 0.0);
-        if (c->stepped) MPH_CK(scalar(L.vstrain, vs.data()));
-        for (size_t r = 0; r < m; ++r)
-            o[r] = (c->stepped && vs[r] < 0.0) ? 0.0 : c->cfg.bulk_modulus[c->prop[ids[r]]];
-        return MPH_OK;
-    }
-    case MPH_FIELD_LAMBDA:
-        for (size_t r = 0; r < m; ++r) o[r] = c->cfg.bulk_viscosity[c->prop[ids[r]]];
-        return MPH_OK;
-    case MPH_FIELD_MU:
-        for (size_t r = 0; r < m; ++r) o[r] = c->cfg.shear_viscosity[c->prop[ids[r]]];
-        return MPH_OK;
-    case MPH_FIELD_PROPERTY:
-        for (size_t r = 0; r < m; ++r) oi[r] = c->prop[ids[r]];
-        return MPH_OK;
-    case MPH_FIELD_INITIAL_STRUCTURE_NEIGHBOR_COUNT:
-        std::memset(oi, 0, sizeof(int) * m);
-        struct_rows([&](size_t r, size_t k) { oi[r] = c->S.count[k]; });
-        return MPH_OK;
-    case MPH_FIELD_DEFORM_GRADIENT: return sel_struct_m33(c, c->Sd.F, o);
-    case MPH_FIELD_STRAIN: return sel_struct_m33(c, c->Sd.E, o);
-    case MPH_FIELD_STRESS: return sel_struct_m33(c, c->Sd.S, o);
-    case MPH_FIELD_NORMALIZER:
-        std::memset(o, 0, sizeof(double) * 9 * m);
-        struct_rows([&](size_t r, size_t k) { std::memcpy(o + 9 * r, &c->S.normalizer[9 * k], sizeof(double) * 9); });
-        return MPH_OK;
-    case MPH_FIELD_VIRIAL_STRESS:
-    case MPH_FIELD_VIRIAL_PRESSURE: {
-        const int w = field == MPH_FIELD_VIRIAL_STRESS ? 9 : 1;
-        std::memset(o, 0, sizeof(double) * w * m);
-        if (!c->vir) return MPH_OK;   // never computed: zeros, as mph_get
-        const double* src[9];
-        for (int e = 0; e < w; ++e) src[e] = (w == 9 ? c->vir : c->vpres) + e;
-        return sel_gather(c, src, w, w, D.slot_a, o);
-    }
-    case MPH_FIELD_LAMBDA_LAMES:
-    case MPH_FIELD_MU_LAMES:
-        for (size_t r = 0; r < m; ++r) o[r] = 0.0;
-        struct_rows([&](size_t r, size_t k) { o[r] = field == MPH_FIELD_LAMBDA_LAMES ? c->S.lame_l[k] : c->S.lame_m[k]; });
-        return MPH_OK;
-    default: return ctx_fail(c, MPH_ERR_ARG, "unknown field " + std::to_string(field));
-    }
+    return sel_get(c, field, out);
 }
 
 int mph_selection_totals(MphCtx* c, const double center[3], double out[MPH_TOTALS])
@@ -644,6 +705,99 @@ int mph_select_profile(MphCtx* c, const MphSelection* s, const double center[3],
 int mph_write_vtk_selected(MphCtx* c, const char* path) { return write_selected(c, path, false); }
 
 int mph_write_vtu_selected(MphCtx* c, const char* path) { return write_selected(c, path, true); }
+
+// ---- selections on slab ranks: the calls without communication (collective ones: mph_dist_select.hip)
+
+int mph_dist_select(MphCtx* c, const MphSelection* s, int* count)
+{
+    if (!s) return MPH_ERR_ARG;
+    MPH_CK(ctx_enter(c));
+    if (!c->dist)
+        return ctx_fail(c, MPH_ERR_UNSUPPORTED, "mph_dist_select: slab selections need a slab context (a single context: mph_select)");
+    if (!sel_valid(*s, c->cfg.dim))
+        return ctx_fail(c, MPH_ERR_ARG, "mph_dist_select: every must be >= 1, phase in [0, every), box in 0..2, type_mask "
+                                        "within 0x3f and lo <= hi on every axis of a box");
+    // the flush has left the held count and the owned count current (dist_sync)
+    const int n = c->n, ng = c->n_glob, nb = select_blocks(ng);
+    const size_t words = ((size_t)ng + 31) / 32;
+    // a box on InitialPosition: the host's verdict over the particles this rank has static inputs
+    // for, by original index.  Created from its window alone, the rank may own a particle without
+    // them; one the rest of the selection accepts cannot be decided, and the call is refused before
+    // anything of the earlier selection is touched.
+    const bool with_mask = s->box == 2;
+    std::vector<unsigned> mask;
+    if (with_mask) {
+        if (!c->gid.empty()) {
+            std::vector<int> id, ty;
+            MPH_CK(fetch(c, (const int*)c->L.B.id, id, (size_t)n));
+            MPH_CK(fetch(c, (const int*)c->L.B.type, ty, (size_t)n));
+            MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+            MphSelection rest = *s;
+            rest.box = 0;
+            for (int q = 0; q < n; ++q)
+                if (id[q] >= 0 && sel_input(c, id[q]) < 0 && sel_accepts(rest, c->cfg.dim, id[q], ty[q], nullptr))
+                    return ctx_fail(c, MPH_ERR_ARG, "mph_dist_select: a box on InitialPosition and an owned particle without "
+                                                    "static inputs");
+        }
+        mask.assign(words, 0u);
+        for (size_t k = 0; k < c->prop.size(); ++k) {
+            const int i = glob_id(c, (int)k);
+            if (sel_accepts(*s, c->cfg.dim, i, c->prop[k], &c->pos0[3 * k])) mask[i >> 5] |= 1u << (i & 31);
+        }
+    }
+    SelectDev& D = c->sel;
+    if (!D.flag) {   // once: these are sized by the whole problem's particle count
+        const size_t n4 = 4 * (((size_t)ng + 3) / 4);   // (k_sel_clear stores int4)
+        MPH_CK(ctx_dalloc(c, &D.flag, n4));
+        MPH_CK(ctx_dalloc(c, &D.slot_a_of, (size_t)ng));
+        MPH_CK(ctx_dalloc(c, &D.slot_b_of, (size_t)ng));
+        MPH_CK(ctx_dalloc(c, &D.mask, words));
+        MPH_CK(ctx_dalloc(c, &D.bsum, (size_t)nb + 1));
+        // an index this rank has never held maps to slot 0 (never read: its flag is 0)
+        MPH_HIP_OK(c, hipMemsetAsync(D.slot_a_of, 0, sizeof(int) * (size_t)ng, c->stream));
+        MPH_HIP_OK(c, hipMemsetAsync(D.slot_b_of, 0, sizeof(int) * (size_t)ng, c->stream));
+    }
+    c->sel_current = false;
+    c->sel_ids.clear();
+    D.count = 0;
+    if (with_mask)
+        MPH_HIP_OK(c, hipMemcpyAsync(D.mask, mask.data(), sizeof(unsigned) * words, hipMemcpyHostToDevice, c->stream));
+    // Position as mph_get reads it: the integrated set B in the order of B.id, ghosts skipped
+    launch_dist_select_scan(c->L, n, ng, c->L.B, *s, with_mask, D);
+    MPH_HIP_OK(c, hipGetLastError());
+    MPH_CK(sel_collect(c, ng, "mph_dist_select", [&] { launch_dist_select_fill(c->L, ng, D); }));
+    c->sel_current = true;
+    if (count) *count = D.count;
+    return MPH_OK;
+}
+
+int mph_dist_selected_ids(MphCtx* c, int* out)
+{
+    MPH_CK(sel_enter(c, "mph_dist_selected_ids", true));
+    if (!out && !c->sel_ids.empty()) return MPH_ERR_ARG;
+    if (!c->sel_ids.empty()) std::memcpy(out, c->sel_ids.data(), sizeof(int) * c->sel_ids.size());
+    return MPH_OK;
+}
+
+int mph_dist_get_selected(MphCtx* c, int field, void* out)
+{
+    MPH_CK(sel_enter(c, "mph_dist_get_selected", true));
+    return sel_get(c, field, out);
+}
+
+int mph_dist_selection_totals_partial(MphCtx* c, const double center[3], double out[MPH_TOTALS])
+{
+    if (!center || !out) return MPH_ERR_ARG;
+    MPH_CK(sel_enter(c, "mph_dist_selection_totals_partial", true));
+    // (an empty selection: no partial record, and k_sel_totals_final leaves the identities)
+    const size_t nb = (size_t)select_total_blocks(c->sel.count);
+    MPH_CK(sel_grow(c, &c->sel_out, &c->sel_out_cap, (size_t)kSelTotals * (nb + 1)));
+    launch_select_totals(c->L, c->L.B, c->sel, center, c->sel_out + kSelTotals, c->sel_out);
+    MPH_HIP_OK(c, hipGetLastError());
+    MPH_HIP_OK(c, hipMemcpyAsync(out, c->sel_out, sizeof(double) * kSelTotals, hipMemcpyDeviceToHost, c->stream));
+    MPH_HIP_OK(c, hipStreamSynchronize(c->stream));
+    return MPH_OK;
+}
 
 }  // extern "C"
 

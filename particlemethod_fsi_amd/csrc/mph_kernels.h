@@ -341,6 +341,13 @@ int select_total_blocks(int count);// partial records of the totals
 void launch_select_scan(const Launch& L, const Soa& X, const MphSelection& s, bool with_mask, const SelectDev& D);
 // D.ids / slot_a / slot_b of the D.count selected; D.count > 0
 void launch_select_fill(const Launch& L, const SelectDev& D);
+// The same on a slab rank (mph_dist_select): X holds n slots, ghosts (id < 0) among them; D.flag and the
+// two maps are indexed by the whole problem's original index, [n_glob] -- flag rounded up to a multiple
+// of 4 ints, cleared here first (only the owned indices are visited) -- and D.bsum has
+// select_blocks(n_glob) + 1 entries; n_glob > 0, n >= 0
+void launch_dist_select_scan(const Launch& L, int n, int n_glob, const Soa& X, const MphSelection& s, bool with_mask,
+                             const SelectDev& D);
+void launch_dist_select_fill(const Launch& L, int n_glob, const SelectDev& D);
 // out[r][e] = src[e][slot[r] * stride] for r < count, e < nc (1, 3 or 9; ints: 1)
 void launch_select_gather(const Launch& L, const double* const* src, int nc, int stride, const int* slot, int count,
                           double* out);

@@ -10,7 +10,8 @@
 // in ".vtu" writes binary VTK XML files instead (mph_write_vtu).  MPH_MONITOR and
 // MPH_SAMPLE add a time history and, per VTK output step, the fields on a lattice (below);
 // MPH_OUTPUT_SELECT crops the VTK-step files to a particle selection and MPH_LOADS appends the
-// totals of a selection -- the load on a body -- to a CSV every MPH_LOADS_STRIDE-th step (below);
+// totals of a selection -- the load on a body -- to a CSV every MPH_LOADS_STRIDE-th step (below;
+// from slab ranks: MPH_DIST_OUTPUT_SELECT, MPH_DIST_LOADS);
 // MPH_KINEMATICS writes the velocity gradient, vorticity and free-surface fields beside every VTK-step
 // file (below).
 //
@@ -322,9 +323,14 @@ int main(int argc, char** argv)
     if (nslabs > 1 && (std::getenv("MPH_OUTPUT_SELECT") || std::getenv("MPH_LOADS"))) {
         const std::string what = std::string(std::getenv("MPH_OUTPUT_SELECT") ? "MPH_OUTPUT_SELECT " : "") +
                                  (std::getenv("MPH_LOADS") ? "MPH_LOADS " : "") +
-                                 "with MPH_SLABS > 1 (selections need a single context)";
+                                 "with MPH_SLABS > 1 (selections need a single context; the slab ranks' selections "
+                                 "merged: MPH_DIST_OUTPUT_SELECT, MPH_DIST_LOADS)";
         die(nullptr, MPH_ERR_UNSUPPORTED, what.c_str());
     }
+    if (nslabs <= 1 && std::getenv("MPH_DIST_OUTPUT_SELECT"))
+        die(nullptr, MPH_ERR_ARG, "MPH_DIST_OUTPUT_SELECT needs MPH_SLABS > 1 (a single context: MPH_OUTPUT_SELECT)");
+    if (nslabs <= 1 && std::getenv("MPH_DIST_LOADS"))
+        die(nullptr, MPH_ERR_ARG, "MPH_DIST_LOADS needs MPH_SLABS > 1 (a single context: MPH_LOADS)");
     if (nslabs > 1 && std::getenv("MPH_KINEMATICS"))
         die(nullptr, MPH_ERR_UNSUPPORTED, "MPH_KINEMATICS with MPH_SLABS > 1 (kinematics need a single context)");
     if (nslabs > 1 && spawn_ranks(R, nslabs, host_transport) < 0) {
@@ -497,10 +503,16 @@ int main(int argc, char** argv)
     // MPH_OUTPUT_SELECT=<spec> (include/mph_gpu.h mph_selection_parse): every VTK-step file, .vtk or
     // .vtu, holds only that selection, evaluated at that step (written before the loop goes on: the
     // background writer takes whole frames only); the .prof restart files stay whole.
+    // MPH_DIST_OUTPUT_SELECT with MPH_SLABS > 1: the same grammar and files from the slab ranks
+    // (include/mph_gpu.h mph_dist_select, mph_dist_write_vtk_selected) -- every rank selects among the
+    // particles it owns at that step and sends its selected rows, rank 0 merges them and writes the
+    // file; the .prof files and output.vtk stay whole.
     MphSelection out_sel{};
-    const bool out_select = std::getenv("MPH_OUTPUT_SELECT") != nullptr;
-    if (out_select && mph_selection_parse(std::getenv("MPH_OUTPUT_SELECT"), &out_sel) != MPH_OK)
-        die(nullptr, MPH_ERR_ARG, "MPH_OUTPUT_SELECT (types=..;box=x0,y0,z0,x1,y1,z1;on=position|initial;every=..;phase=..)");
+    const bool dout_select = nslabs > 1 && std::getenv("MPH_DIST_OUTPUT_SELECT");
+    const bool out_select = dout_select || std::getenv("MPH_OUTPUT_SELECT") != nullptr;
+    if (out_select && mph_selection_parse(std::getenv(dout_select ? "MPH_DIST_OUTPUT_SELECT" : "MPH_OUTPUT_SELECT"), &out_sel) != MPH_OK)
+        die(nullptr, MPH_ERR_ARG, "MPH_OUTPUT_SELECT / MPH_DIST_OUTPUT_SELECT "
+                                  "(types=..;box=x0,y0,z0,x1,y1,z1;on=position|initial;every=..;phase=..)");
     // MPH_KINEMATICS="radius=..;classes=..;beta=..;det=.." (include/mph_gpu.h mph_kinematics_parse; any
     // subset of the keys, empty text: the defaults): at every VTK output step the velocity gradient,
     // vorticity and free-surface fields are computed (mph_compute_kinematics) and written as a .vtu to
@@ -520,12 +532,20 @@ int main(int argc, char** argv)
     // origin) as %.17g -- the summed Force and its torque among them.  Force is stored by the last
     // step of an mph_step call, so the loop below ends its call on every such step: a loads row is a
     // flush point (DESIGN.md section 13 has its cost).
+    // MPH_DIST_LOADS=<csv path> with MPH_SLABS > 1: the same options, header, rows and cadence from the
+    // slab ranks (include/mph_gpu.h mph_dist_select, mph_dist_selection_totals) -- every rank reduces
+    // its own selection, rank 0 combines the records in rank order and writes the row.  A slab step
+    // stores Force on every step, but a row is evaluated on the state at its step, so the call ends
+    // there all the same.
+    const bool dloads = nslabs > 1 && std::getenv("MPH_DIST_LOADS");
+    bool loads_on = false;
     FILE* loads_f = nullptr;
     MphSelection loads_sel{};
     loads_sel.every = 1;
     int loads_stride = 10;
     double loads_center[3] = {0.0, 0.0, 0.0};
-    if (const char* lp = std::getenv("MPH_LOADS")) {
+    if (const char* lp = std::getenv(dloads ? "MPH_DIST_LOADS" : "MPH_LOADS")) {
+        loads_on = true;
         if (const char* e = std::getenv("MPH_LOADS_SELECT"))
             if (mph_selection_parse(e, &loads_sel) != MPH_OK) die(nullptr, MPH_ERR_ARG, "MPH_LOADS_SELECT (a selection spec)");
         if (const char* e = std::getenv("MPH_LOADS_STRIDE")) loads_stride = std::atoi(e);
@@ -535,14 +555,16 @@ int main(int argc, char** argv)
             if (v.size() != 3) die(nullptr, MPH_ERR_ARG, "MPH_LOADS_CENTER (x,y,z)");
             for (int d = 0; d < 3; ++d) loads_center[d] = v[d];
         }
-        loads_f = std::fopen(lp, "w");
-        if (!loads_f) die(nullptr, MPH_ERR_IO, "opening the MPH_LOADS file");
+        if (root) loads_f = std::fopen(lp, "w");
+        if (root && !loads_f) die(nullptr, MPH_ERR_IO, "opening the MPH_LOADS file");
         static const char* cols[MPH_TOTALS] = {"count", "mass", "px", "py", "pz", "ke", "fx", "fy", "fz", "tx", "ty", "tz",
                                                "mx", "my", "mz", "xmin", "xmax", "ymin", "ymax", "zmin", "zmax", "vmax2",
                                                "reserved0", "reserved1"};
-        std::fprintf(loads_f, "step,time");
-        for (int k = 0; k < MPH_TOTALS; ++k) std::fprintf(loads_f, ",%s", cols[k]);
-        std::fprintf(loads_f, "\n");
+        if (loads_f) {
+            std::fprintf(loads_f, "step,time");
+            for (int k = 0; k < MPH_TOTALS; ++k) std::fprintf(loads_f, ",%s", cols[k]);
+            std::fprintf(loads_f, "\n");
+        }
     }
     const auto loop_t0 = std::chrono::steady_clock::now();
     double time_now = cfg.time;
@@ -571,9 +593,9 @@ int main(int argc, char** argv)
             if (t + 1.0e-5 * dt >= vtk_next) { vtk_after = true; break; }
             t += dt;
             if (t + 1.0e-5 * dt >= out_next || !(t < cfg.end_time + 1.0e-5 * dt)) break;
-            if (loads_f && (steps_run + k) % loads_stride == 0) break;   // (that step stores Force)
+            if (loads_on && (steps_run + k) % loads_stride == 0) break;   // (that step stores Force)
         }
-        const bool loads_after = loads_f && (steps_run + k) % loads_stride == 0;
+        const bool loads_after = loads_on && (steps_run + k) % loads_stride == 0;
         const auto t0 = std::chrono::steady_clock::now();
         roctxRangePushA("mph_step");
         rc = mph_step(ctx, k);
@@ -602,14 +624,16 @@ int main(int argc, char** argv)
         steps_run += k;
         if (loads_after) {
             double tot[MPH_TOTALS];
-            rc = mph_select(ctx, &loads_sel, nullptr);
-            if (rc) die(ctx, rc, "mph_select (MPH_LOADS_SELECT)");
-            rc = mph_selection_totals(ctx, loads_center, tot);
-            if (rc) die(ctx, rc, "mph_selection_totals");
-            std::fprintf(loads_f, "%lld,%.17g", steps_run, mph_time(ctx));
-            for (int q = 0; q < MPH_TOTALS; ++q) std::fprintf(loads_f, ",%.17g", tot[q]);
-            std::fprintf(loads_f, "\n");
-            std::fflush(loads_f);
+            rc = dloads ? mph_dist_select(ctx, &loads_sel, nullptr) : mph_select(ctx, &loads_sel, nullptr);
+            if (rc) die(ctx, rc, dloads ? "mph_dist_select (MPH_LOADS_SELECT)" : "mph_select (MPH_LOADS_SELECT)");
+            rc = dloads ? mph_dist_selection_totals(ctx, loads_center, tot) : mph_selection_totals(ctx, loads_center, tot);
+            if (rc) die(ctx, rc, dloads ? "mph_dist_selection_totals" : "mph_selection_totals");
+            if (loads_f) {
+                std::fprintf(loads_f, "%lld,%.17g", steps_run, mph_time(ctx));
+                for (int q = 0; q < MPH_TOTALS; ++q) std::fprintf(loads_f, ",%.17g", tot[q]);
+                std::fprintf(loads_f, "\n");
+                std::fflush(loads_f);
+            }
         }
         for (int s = 0; s < k; ++s) {
             if (vtk_after && s == k - 1 && sampling) {
@@ -643,7 +667,11 @@ int main(int argc, char** argv)
                 if (rc) die(ctx, rc, "mph_compute_virial");
                 std::snprintf(name, sizeof(name), vtk.c_str(), istep);
                 // formatted and written by a background thread while the next steps run
-                if (out_select) {
+                if (dout_select) {
+                    rc = mph_dist_select(ctx, &out_sel, nullptr);
+                    if (rc) die(ctx, rc, "mph_dist_select (MPH_DIST_OUTPUT_SELECT)");
+                    rc = vtu ? mph_dist_write_vtu_selected(ctx, name) : mph_dist_write_vtk_selected(ctx, name);
+                } else if (out_select) {
                     rc = mph_select(ctx, &out_sel, nullptr);
                     if (rc) die(ctx, rc, "mph_select (MPH_OUTPUT_SELECT)");
                     rc = vtu ? mph_write_vtu_selected(ctx, name) : mph_write_vtk_selected(ctx, name);

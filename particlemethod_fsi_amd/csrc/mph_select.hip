@@ -5,7 +5,10 @@
 // kernel of a step is touched.
 //
 //   k_sel_flag            over the sorted arrays: flag[i] (the shared predicate sel_accepts, or the
-//                         host's bit mask for a box on InitialPosition) and the two maps i -> q
+//                         host's bit mask for a box on InitialPosition) and the two maps i -> q.
+//                         The slab form (mph_dist_select) runs over the slots a rank holds, skips its
+//                         ghosts and indexes flag and the maps by the whole problem's original index;
+//                         only owned indices are visited, so k_sel_clear zeroes the flags before it
 //   k_sel_count           selected per block of kSelBlock original indices
 //   k_sel_scan_blocks     one block: exclusive scan of the block counts, and the count
 //   k_sel_fill            ids[r] = i, slot_a[r], slot_b[r]: each block scans its own flags again and
@@ -32,11 +35,22 @@ int select_total_blocks(int count) { return blocks(count, kSelBlock); }
 
 // ------------------------------------------------------------------------------- flag, scan ---
 
-__global__ __launch_bounds__(kSelThreads) void k_sel_flag(int n, int dim, MphSelection s, int with_mask, Soa X,
+// How many: the slots q the kernel visits (n) and the original indices i it may meet.  A single
+// context holds every particle, so both are n; a slab rank holds n of the whole problem's ng.
+template <bool SLAB> struct SelFlagN { int n; };
+template <> struct SelFlagN<true> { int n, ng; };
+__device__ __forceinline__ int sel_indices(const SelFlagN<false>& N) { return N.n; }
+__device__ __forceinline__ int sel_indices(const SelFlagN<true>& N) { return N.ng; }
+
+// SLAB: a ghost (id < 0) is skipped like any index out of range, and an index no slot holds keeps the
+// flag k_sel_clear left
+template <bool SLAB>
+__global__ __launch_bounds__(kSelThreads) void k_sel_flag(SelFlagN<SLAB> N, int dim, MphSelection s, int with_mask, Soa X,
                                                           const int* __restrict__ a_id, SelectDev D)
 {
+    const int n = sel_indices(N);
     const int q = blockIdx.x * kSelThreads + threadIdx.x;
-    if (q >= n) return;
+    if (q >= N.n) return;
     const int ia = a_id[q];
     if (ia >= 0 && ia < n) D.slot_a_of[ia] = q;
     const int i = X.id[q];
@@ -50,6 +64,13 @@ __global__ __launch_bounds__(kSelThreads) void k_sel_flag(int n, int dim, MphSel
         in = sel_accepts(s, dim, i, X.type[q], x);
     }
     D.flag[i] = in ? 1 : 0;
+}
+
+// flag[0, 4 n4) = 0 (the allocation is a whole number of int4)
+__global__ __launch_bounds__(kSelThreads) void k_sel_clear(int n4, int4* __restrict__ flag)
+{
+    const int k = blockIdx.x * kSelThreads + threadIdx.x;
+    if (k < n4) flag[k] = make_int4(0, 0, 0, 0);
 }
 
 // the four flags of thread t of block b: original indices b kSelBlock + 4 t + (0..3), 0 past n
@@ -135,19 +156,43 @@ __global__ __launch_bounds__(kSelThreads) void k_sel_fill(int n, SelectDev D)
     }
 }
 
-void launch_select_scan(const Launch& L, const Soa& X, const MphSelection& s, bool with_mask, const SelectDev& D)
+// count and scan over the n original indices of D.flag
+static void select_scan(const Launch& L, int n, const SelectDev& D)
 {
-    const int n = L.P->n, nb = select_blocks(n);
-    launch(L.prof, "sel_flag", L.stream, k_sel_flag, dim3(blocks(n, kSelThreads)), dim3(kSelThreads), n, L.P->dim, s,
-           with_mask ? 1 : 0, X, L.A.id, D);
+    const int nb = select_blocks(n);
     launch(L.prof, "sel_count", L.stream, k_sel_count, dim3(nb), dim3(kSelThreads), n, D);
     launch(L.prof, "sel_scan_blocks", L.stream, k_sel_scan_blocks, dim3(1), dim3(kSelScanThreads), nb, D.bsum);
+}
+
+void launch_select_scan(const Launch& L, const Soa& X, const MphSelection& s, bool with_mask, const SelectDev& D)
+{
+    const int n = L.P->n;
+    launch(L.prof, "sel_flag", L.stream, k_sel_flag<false>, dim3(blocks(n, kSelThreads)), dim3(kSelThreads),
+           SelFlagN<false>{n}, L.P->dim, s, with_mask ? 1 : 0, X, L.A.id, D);
+    select_scan(L, n, D);
 }
 
 void launch_select_fill(const Launch& L, const SelectDev& D)
 {
     const int n = L.P->n;
     launch(L.prof, "sel_fill", L.stream, k_sel_fill, dim3(select_blocks(n)), dim3(kSelThreads), n, D);
+}
+
+void launch_dist_select_scan(const Launch& L, int n, int n_glob, const Soa& X, const MphSelection& s, bool with_mask,
+                             const SelectDev& D)
+{
+    const int n4 = blocks(n_glob, 4);
+    launch(L.prof, "sel_clear", L.stream, k_sel_clear, dim3(blocks(n4, kSelThreads)), dim3(kSelThreads), n4,
+           reinterpret_cast<int4*>(D.flag));
+    if (n > 0)
+        launch(L.prof, "sel_flag_slab", L.stream, k_sel_flag<true>, dim3(blocks(n, kSelThreads)), dim3(kSelThreads),
+               SelFlagN<true>{n, n_glob}, L.P->dim, s, with_mask ? 1 : 0, X, L.A.id, D);
+    select_scan(L, n_glob, D);
+}
+
+void launch_dist_select_fill(const Launch& L, int n_glob, const SelectDev& D)
+{
+    launch(L.prof, "sel_fill", L.stream, k_sel_fill, dim3(select_blocks(n_glob)), dim3(kSelThreads), n_glob, D);
 }
 
 // ----------------------------------------------------------------------------------- gather ---

@@ -73,6 +73,9 @@ EXPORTED_SYMBOLS = [
     "mph_monitor_combine", "mph_dist_monitor_read",
     "mph_slab_lattice_owner", "mph_dist_sample_grid_partial", "mph_dist_sample_grid",
     "mph_dist_gauge_grid_partial", "mph_gauge_combine", "mph_dist_gauge_grid",
+    "mph_dist_select", "mph_dist_selected_ids", "mph_dist_get_selected", "mph_dist_selection_totals_partial",
+    "mph_totals_combine", "mph_dist_selection_totals", "mph_dist_gather_selected", "mph_dist_write_vtk_selected",
+    "mph_dist_write_vtu_selected",
 ]
 
 ABI_VERSION = 6   # MPH_ABI_VERSION of include/mph_gpu.h that these bindings follow
@@ -189,6 +192,17 @@ def selection_accepts(sel: MphSelection, dim: int, index: int, ptype: int, pos=N
     return _check(load_library().mph_selection_accepts(ctypes.byref(sel), int(dim), int(index), int(ptype),
                                                        None if p is None else p.ctypes.data,
                                                        None if p0 is None else p0.ctypes.data))
+
+
+def totals_combine(records) -> np.ndarray:
+    """mph_totals_combine: the ranks' records of dist_selection_totals(partial=True) ([nranks, 24], rank
+    order) made one record [24] -- rank 0's combined with ranks 1, 2, ... in order: the sums add, the
+    minima take the minimum, the maxima and VMAX2 the maximum.  Host only."""
+    recs = [np.ascontiguousarray(r, np.float64).reshape(TOTALS) for r in records]
+    ptrs = (ctypes.c_void_p * max(len(recs), 1))(*[r.ctypes.data for r in recs])
+    out = np.zeros(TOTALS)
+    _check(load_library().mph_totals_combine(len(recs), ptrs, out.ctypes.data))
+    return out
 
 
 class MphKinematics(ctypes.Structure):
@@ -453,6 +467,15 @@ def load_library() -> ctypes.CDLL:
         "mph_dist_gauge_grid_partial": (ip, [vp, ctypes.POINTER(MphGaugeGrid), vp]),
         "mph_gauge_combine": (ip, [ip, ctypes.c_longlong, vp, vp]),
         "mph_dist_gauge_grid": (ip, [vp, ctypes.POINTER(MphGaugeGrid), vp]),
+        "mph_dist_select": (ip, [vp, ctypes.POINTER(MphSelection), ctypes.POINTER(ctypes.c_int)]),
+        "mph_dist_selected_ids": (ip, [vp, vp]),
+        "mph_dist_get_selected": (ip, [vp, ip, vp]),
+        "mph_dist_selection_totals_partial": (ip, [vp, vp, vp]),
+        "mph_totals_combine": (ip, [ip, vp, vp]),
+        "mph_dist_selection_totals": (ip, [vp, vp, vp]),
+        "mph_dist_gather_selected": (ctypes.c_longlong, [vp, ip, vp, vp, ctypes.c_longlong]),
+        "mph_dist_write_vtk_selected": (ip, [vp, ctypes.c_char_p]),
+        "mph_dist_write_vtu_selected": (ip, [vp, ctypes.c_char_p]),
     }
     # entry points an older library may lack (A/B runs against earlier builds)
     optional = {"mph_phase_timing", "mph_phase_times", "mph_set_step_batching", "mph_neighbor_rows",
@@ -471,7 +494,10 @@ def load_library() -> ctypes.CDLL:
                 "mph_dist_monitor_configure", "mph_dist_monitor_record_doubles", "mph_dist_monitor_read_partial",
                 "mph_monitor_combine", "mph_dist_monitor_read",
                 "mph_slab_lattice_owner", "mph_dist_sample_grid_partial", "mph_dist_sample_grid",
-                "mph_dist_gauge_grid_partial", "mph_gauge_combine", "mph_dist_gauge_grid"}
+                "mph_dist_gauge_grid_partial", "mph_gauge_combine", "mph_dist_gauge_grid",
+                "mph_dist_select", "mph_dist_selected_ids", "mph_dist_get_selected",
+                "mph_dist_selection_totals_partial", "mph_totals_combine", "mph_dist_selection_totals",
+                "mph_dist_gather_selected", "mph_dist_write_vtk_selected", "mph_dist_write_vtu_selected"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue
@@ -1050,6 +1076,71 @@ class MphSolver:
                                               ctypes.addressof(names)), self._h)
         raw = names.raw
         return [(raw[32 * i:32 * (i + 1)].split(b"\0", 1)[0].decode(), float(ms[i])) for i in range(min(k, 64))]
+
+    # -- particle selections on slab ranks ----------------------------------------------------------
+    def dist_select(self, types=None, box=None, on: str = "position", every: int = 1, phase: int = 0, spec=None) -> int:
+        """mph_dist_select: select() for a slab context, no communication -- among the particles this
+        rank owns now (owned_ids()); returns this rank's count.  The ranks' selections partition the
+        whole problem's.  Stale after step() / set() like a single context's."""
+        if spec is None:
+            sel = make_selection(types, box, on, every, phase)
+        else:
+            sel = spec if isinstance(spec, MphSelection) else parse_selection(spec)
+        cnt = ctypes.c_int(0)
+        _check(self._L.mph_dist_select(self._h, ctypes.byref(sel), ctypes.byref(cnt)), self._h)
+        self._sel_count = cnt.value
+        return cnt.value
+
+    def dist_selected_ids(self) -> np.ndarray:
+        """This rank's selected original indices (of the whole problem), ascending."""
+        out = np.zeros(getattr(self, "_sel_count", 0), np.int32)
+        _check(self._L.mph_dist_selected_ids(self._h, out.ctypes.data), self._h)
+        return out
+
+    def dist_get_selected(self, name: str) -> np.ndarray:
+        """get(name)[dist_selected_ids()] of this rank, bit for bit, gathered on the device; no
+        communication."""
+        fid, w, dt = FIELDS[name]
+        m = getattr(self, "_sel_count", 0)
+        out = np.zeros((m,) if w == 1 else ((m, 3) if w == 3 else (m, 3, 3)), dt)
+        _check(self._L.mph_dist_get_selected(self._h, fid, out.ctypes.data), self._h)
+        return out
+
+    def dist_selection_totals(self, center=(0.0, 0.0, 0.0), partial: bool = False):
+        """mph_dist_selection_totals, collective: rank 0 returns {TOTAL_SLOTS name: value} over the
+        whole problem's selection -- totals_combine of the ranks' records -- every other rank None.
+        partial (mph_dist_selection_totals_partial, no communication): this rank's record [24]."""
+        c = np.ascontiguousarray(center, np.float64).reshape(3)
+        out = np.zeros(TOTALS)
+        if partial:
+            _check(self._L.mph_dist_selection_totals_partial(self._h, c.ctypes.data, out.ctypes.data), self._h)
+            return out
+        _check(self._L.mph_dist_selection_totals(self._h, c.ctypes.data, out.ctypes.data), self._h)
+        if self.dist_info()["rank"] != 0:
+            return None
+        return {k: float(out[i]) for k, i in TOTAL_SLOTS.items()}
+
+    def dist_gather_selected(self, name: str):
+        """mph_dist_gather_selected, collective: rank 0 returns (ids, rows) -- every rank's selected
+        rows of `name` merged by ascending original index -- every other rank None.  Only selected
+        rows travel."""
+        fid, w, dt = FIELDS[name]
+        if self.dist_info()["rank"] != 0:
+            _check(self._L.mph_dist_gather_selected(self._h, fid, None, None, 0), self._h)
+            return None
+        cap = self.n
+        ids = np.zeros(max(cap, 1), np.int32)
+        out = np.zeros((max(cap, 1),) if w == 1 else ((max(cap, 1), 3) if w == 3 else (max(cap, 1), 3, 3)), dt)
+        k = _check(self._L.mph_dist_gather_selected(self._h, fid, out.ctypes.data, ids.ctypes.data, cap), self._h)
+        return ids[:k].copy(), out[:k].copy()
+
+    def dist_write_vtk_selected(self, path: str):
+        """mph_dist_write_vtk_selected, collective: rank 0 writes the array writer's file of the merged
+        selected rows."""
+        _check(self._L.mph_dist_write_vtk_selected(self._h, path.encode()), self._h)
+
+    def dist_write_vtu_selected(self, path: str):
+        _check(self._L.mph_dist_write_vtu_selected(self._h, path.encode()), self._h)
 
     # -- velocity gradient, vorticity and free-surface fields ---------------------------------------
     def kinematics(self, radius: float = 0.0, classes: int = 0, beta: float = 0.0, det_floor: float = 0.0,
